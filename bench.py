@@ -12,8 +12,12 @@ running under a launcher; launched by torch.distributed.run directly it uses the
 --gpus disagrees with WORLD_SIZE).  Windows are independent, so ranks hold disjoint
 window batches (replicas, weak scaling, no data-path collective); the factor-sharded mode (laser blocks of each
 window split across ranks, RCCL all-reduce of the laser partial sums per LM iteration) is measured separately on
-the C4-shaped window and reported under "factor_sharded" at EVERY N (same total work: strong scaling; N = 1 is the
+the C4-shaped window and reported under "factor_sharded" at EVERY N with --full (same total work: strong scaling; N = 1 is the
 un-sharded reference point of that curve).
+
+A plain run (`--gpus N --steps K --warmup W`) builds the batch, warms up, times K steps and prints the headline line (`value`,
+`ms_per_step`, the workload); `--dump-outputs DIR` also writes what the last timed step returned.  Everything else — the parity gate,
+rooflines, CPU baselines, the latency / tracking / ragged / replay legs, per-kernel times and the factor-sharded section — runs with `--full`.
 """
 import argparse
 import importlib
@@ -31,6 +35,7 @@ sys.path.insert(0, ROOT)
 BYTES_LASER_BOTH, BYTES_LASER_ONE, BYTES_IMU, BYTES_WHEEL, BYTES_GROUND, BYTES_STATE = 312, 216, 7448, 520, 60, 120
 PIS_BYTES, PWS_BYTES, LP_BYTES, PGS_BYTES, PIFS_BYTES = 496 * 8, 92 * 8, 128 * 8, 28 * 8, 376 * 8   # partial-sum records (csrc/liw_kernels.hpp; PIFS: per-frame IMU record of batches >= 1 024 windows)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_WINDOWS = 4096    # --dump-outputs: windows written at most (~24 MB at n = 30); the full 49 152-window states alone are 177 MB
 
 
 def algorithmic_bytes(n, L, both_free):
@@ -81,6 +86,29 @@ def input_floor_bytes(n, L):
 
 def input_floor_packed_bytes(n, L):
     return L * 72 + (n - 1) * (1536 + 208) + n * 120
+
+
+def dump_outputs(path, bs, marg):
+    """What the timed path hands its caller after the last step, for windows sample_windows(B): the solved states (BatchSolver.states),
+    the marginalisation's sqrt_H / Delta_H / Delta_g and the per-window LM summary, one float64 .npy per array."""
+    B, n = bs.B, bs.n
+    idx = sample_windows(B)
+    sel = bs.torch.from_numpy(idx).to(bs.t["x"].device)
+    sH, dH, dg = (t[sel].cpu().numpy() for t in marg)
+    summ = bs.summaries()
+    arrays = {"states": bs.t["x"].reshape(B, n, 15)[sel].cpu().numpy(), "marg_sqrt_H": sH, "marg_Delta_H": dH.reshape(-1, 15, 15), "marg_Delta_g": dg}
+    for k in ("iterations", "successful", "termination", "initial_cost", "final_cost"):
+        arrays["lm_" + k] = np.array([summ[b][k] for b in idx])
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def sample_windows(B):
+    """every window of a batch of up to DUMP_WINDOWS, else a fixed seeded sample of DUMP_WINDOWS of them (ascending)"""
+    if B <= DUMP_WINDOWS:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(0).choice(B, DUMP_WINDOWS, replace=False))
 
 
 def _free_port():
@@ -763,6 +791,25 @@ def parity_gate(liw, prm, windows, gate_ids, bs, marg_out, iters_cap, dev):
     return out
 
 
+def headline(args, world, B, n, L, elapsed, iters, term):
+    """the result line's measurement of the timed steps and the workload it ran; --full adds the side measurements to it"""
+    capped = int((term == 4).sum())
+    return {"metric": "sliding-window solves/sec (30 KF, 2k scan pts)", "value": round(B * world * args.steps / elapsed, 3), "unit": "solves/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "C2 synthetic: %d windows/GPU x (n=%d frames, L=%d laser_factor blocks, %d IMU + %d wheel, %d ground); "
+                                   "step = init-topology LM solve (cap %d iters) + marginalization per window" % (B, n, L, n - 1, n - 1, 2 * n * n, args.iters),
+                       "windows_per_gpu": B, "frames": n, "laser_blocks": L, "lm_iteration_cap": args.iters,
+                       "parallelism": "windows replicated over %d GPU(s), no data-path collective" % world,
+                       "lm_iterations_mean": float(iters.mean()), "terminations": {str(int(k)): int((term == k).sum()) for k in np.unique(term)},
+                       "lm_iterations_histogram": {str(int(k)): int((iters == k).sum()) for k in np.unique(iters)},
+                       "distinct_windows_per_gpu": min(args.distinct, B),
+                       "lm_hits_iteration_cap_pct": round(100.0 * capped / len(term), 1),
+                       "note": ("%.0f %% of the windows run into the %d-iteration cap on the GPU and on the CPU oracle alike (cone-shaped ground_factor_q "
+                                "residual, DESIGN 6); the marginalisation follows the init solve as in trajectory.cpp:446-479, where no prior rows exist yet "
+                                "(SURVEY 8d's 15 synthetic prior rows are exercised by tracking_frame_latency and the parity tests)" % (100.0 * capped / len(term), args.iters))}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -799,7 +846,15 @@ def main():
     ap.add_argument("--track-gate-windows", type=int, default=6, help="robots of the TRACK leg whose every frame is checked teacher-forced against the oracle")
     ap.add_argument("--record-md", default=None, help="after the timed region, write a reference-shaped `record` table (labels "
                     "'solve' / 'marginalization', src/utilies/record.h) of per-batch durations to this path")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every side measurement and check: parity gate, rooflines, "
+                    "CPU baselines, fixed-10 / converging / B=1 / tracking / keep-30 / ragged / TRACK-batch / replay legs, per-kernel times, "
+                    "the factor-sharded C4 section; without it a run times the headline workload and prints its line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step returned (states, "
+                    "marginalisation, LM summaries) as DIR/<name>.npy, float64; rank 0's batch, a fixed seeded sample of %d windows when "
+                    "the batch is larger" % DUMP_WINDOWS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -860,7 +915,7 @@ def main():
     for _ in range(args.warmup):
         one_step()
     barrier()
-    bs.set_timing(True)
+    bs.set_timing(True)   # on in every run, so that a plain run times the same launches (HIP-event pairs included) that --full prices rooflines from
     t0 = time.perf_counter()
     for _ in range(args.steps):
         one_step()
@@ -873,6 +928,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bs, last_marg[0])
+    summ = bs.summaries()
+    iters = np.array([s["iterations"] for s in summ])
+    term = np.array([s["termination"] for s in summ])
     if args.record_md and rank == 0:   # outside the timed region: the extra events would serialise solve and marginalisation
         rec = liw.outputs.Record()
         for _ in range(max(2, args.steps)):
@@ -884,9 +944,12 @@ def main():
             rec.add_time("marginalization", ev[1].elapsed_time(ev[2]) * 1e3)
             rec.add_record("windows_per_batch", B)
         rec.write(args.record_md)
-    summ = bs.summaries()
-    iters = np.array([s["iterations"] for s in summ])
-    term = np.array([s["termination"] for s in summ])
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, B, n, L, elapsed, iters, term)))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- parity gate on the timed batch itself (rank 0; the oracle is the checker, never the thing measured)
     gate = None
@@ -1395,25 +1458,10 @@ def main():
         rss_all = [None] * world
         dist.all_gather_object(rss_all, peak_rss_mb())
     if rank == 0:
-        total = B * world * args.steps
-        out = {"metric": "sliding-window solves/sec (30 KF, 2k scan pts)", "value": round(total / elapsed, 3), "unit": "solves/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": "C2 synthetic: %d windows/GPU x (n=%d frames, L=%d laser_factor blocks, %d IMU + %d wheel, %d ground); "
-                                      "step = init-topology LM solve (cap %d iters) + marginalization per window" % (B, n, L, n - 1, n - 1, 2 * n * n, args.iters),
-                          "windows_per_gpu": B, "frames": n, "laser_blocks": L, "lm_iteration_cap": args.iters,
-                          "parallelism": "windows replicated over %d GPU(s), no data-path collective" % world,
-                          "lm_iterations_mean": float(iters.mean()), "terminations": {str(int(k)): int((term == k).sum()) for k in np.unique(term)}},
-               "roofline": roofline, "roofline_lm_step": step_roof, "hbm_bytes_per_window_iteration": hbm_iter, "cpu_baseline": cpu, "parity_gate": gate}
+        out = headline(args, world, B, n, L, elapsed, iters, term)
+        out.update({"roofline": roofline, "roofline_lm_step": step_roof, "hbm_bytes_per_window_iteration": hbm_iter, "cpu_baseline": cpu, "parity_gate": gate})
         out["host_peak_rss_mb_per_rank"] = {"after_batch_setup_rank0": rss_setup, "end_of_run": rss_all,
                                             "note": "the batch is tiled in HBM from the distinct windows (BatchSolver(tile=...)); ru_maxrss of every rank"}
-        capped = int((term == 4).sum())
-        out["config"]["lm_iterations_histogram"] = {str(int(k)): int((iters == k).sum()) for k in np.unique(iters)}
-        out["config"]["distinct_windows_per_gpu"] = min(args.distinct, B)
-        out["config"]["lm_hits_iteration_cap_pct"] = round(100.0 * capped / len(term), 1)
-        out["config"]["note"] = ("%.0f %% of the windows run into the %d-iteration cap on the GPU and on the CPU oracle alike (cone-shaped ground_factor_q "
-                                 "residual, DESIGN 6); the marginalisation follows the init solve as in trajectory.cpp:446-479, where no prior rows exist yet "
-                                 "(SURVEY 8d's 15 synthetic prior rows are exercised by tracking_frame_latency and the parity tests)" % (100.0 * capped / len(term), args.iters))
         if gate is not None and not gate["passed"]:
             # a timing is only accepted after the equality gate; no `value` without it
             out["value"] = None

@@ -71,3 +71,12 @@ def test_marg_reference_scales_and_prior_argument(liw, synth, pyoracle):
     # an explicit prior argument = the prior the first pass left
     r1 = bench.marg_reference(pyoracle, orc, d, x, mp, 1, prior=(r2[0]["X"], r2[0]["J"], r2[0]["R"]))
     assert np.array_equal(r1[0]["dH"], r2[1]["dH"]) and np.array_equal(r1[0]["dg"], r2[1]["dg"])
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    bench = importlib.import_module("bench")
+    assert np.array_equal(bench.sample_windows(100), np.arange(100))
+    a, b = bench.sample_windows(49152), bench.sample_windows(49152)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_WINDOWS == len(np.unique(a)) and (np.diff(a) > 0).all() and a.max() < 49152
+    # the largest dump of bench.py's C2 shape (n = 30): states + sqrt_H + Delta_H + Delta_g + five LM summary values, float64
+    assert bench.DUMP_WINDOWS * (30 * 15 + 36 + 225 + 15 + 5) * 8 <= 64 * 2 ** 20

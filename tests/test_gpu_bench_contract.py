@@ -20,7 +20,7 @@ def last_json(out):
 
 
 def test_single_rank_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "1", "--warmup", "0", "--cpu-reps", "2", "--cpu-warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "64", "--steps", "1", "--warmup", "0", "--cpu-reps", "2", "--cpu-warmup", "0",
                         "--cpu-procs", "2", "--distinct", "8"],
                        capture_output=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -36,6 +36,27 @@ def test_single_rank_line():
     assert "lm_hits_iteration_cap_pct" in d["config"] and "lm_iterations_histogram" in d["config"]
     fs = d["factor_sharded"]                                     # N = 1: the un-sharded reference point of the factor-parallel curve
     assert "error" not in fs and fs["ranks"] == 1 and fs["scaling"] == "strong" and fs["solves_per_s"] > 0
+
+
+def test_plain_run_line_and_dumped_outputs(tmp_path):
+    """without --full: the headline line only, --steps timed steps, and --dump-outputs writes the last step's results (float64)"""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "2", "--warmup", "1", "--distinct", "8",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    d = last_json(r.stdout)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"} <= set(d)
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+    assert abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    assert not {"parity_gate", "cpu_baseline", "roofline", "factor_sharded", "kernel_times"} & set(d)
+    shapes = {"states": (64, 30, 15), "marg_sqrt_H": (64, 36), "marg_Delta_H": (64, 15, 15), "marg_Delta_g": (64, 15), "lm_iterations": (64,),
+              "lm_successful": (64,), "lm_termination": (64,), "lm_initial_cost": (64,), "lm_final_cost": (64,)}
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in shapes)
+    for k, sh in shapes.items():
+        a = np.load(os.path.join(tmp_path, k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == sh and np.isfinite(a).all(), k
+    it = np.load(os.path.join(tmp_path, "lm_iterations.npy"))
+    assert abs(it.mean() - d["config"]["lm_iterations_mean"]) < 1e-9 and it.max() <= d["config"]["lm_iteration_cap"]
 
 
 def _check_two_ranks(d):
@@ -56,7 +77,7 @@ def test_two_rank_control_flow_on_one_gpu():
     """launched the way the driver launches N > 1: torch.distributed.run around bench.py"""
     env = dict(os.environ, LIW_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-                        "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0", "--distinct", "4"],
+                        "29533", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0", "--distinct", "4"],
                        capture_output=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     _check_two_ranks(last_json(r.stdout))
@@ -67,7 +88,7 @@ def test_gpus_flag_spawns_its_own_ranks():
     env = dict(os.environ, LIW_BENCH_SHARE_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0", "--distinct", "4"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "64", "--steps", "1", "--warmup", "0", "--distinct", "4"],
                        capture_output=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     _check_two_ranks(last_json(r.stdout))
@@ -87,7 +108,7 @@ def test_eight_rank_control_flow_on_one_gpu():
     env = dict(os.environ, LIW_BENCH_SHARE_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--batch", "512", "--steps", "1", "--warmup", "0", "--distinct", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--batch", "512", "--steps", "1", "--warmup", "0", "--distinct", "4",
                         "--sharded-windows", "32"],
                        capture_output=True, cwd=ROOT, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
