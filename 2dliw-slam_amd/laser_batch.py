@@ -1,0 +1,291 @@
+"""Batched laser front-end on the device (C ABI include/liw_laser_batch.h): `BatchFrontEnd` runs the tracking-time work of
+`laser.LaserManager` for B robots at once on torch device tensors — ranges -> points -> de-skew -> lines -> matches against
+the reference sub-map -> sub-map update -> the laser arrays `BatchSolver.rebind` takes.  The host front-end (`laser`) is its
+parity reference.  There is no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device."""
+import ctypes as C
+
+import numpy as np
+
+from .laser import LaserParamsC, laser_params_struct
+
+# every symbol include/liw_laser_batch.h declares (checked by tests/test_laser_batch_abi.py)
+LFE_EXPORTS = [
+    "liw_lfe_store_layout", "liw_lfe_create", "liw_lfe_destroy", "liw_lfe_last_error", "liw_lfe_set_geometry", "liw_lfe_store_reset",
+    "liw_lfe_ranges_to_points", "liw_lfe_deskew", "liw_lfe_spawn", "liw_lfe_match", "liw_lfe_add_scan", "liw_lfe_pack_track",
+    "liw_lfe_status", "liw_lfe_num_lines", "liw_lfe_get_lines", "liw_lfe_cell_lines", "liw_lfe_submap_pose",
+]
+
+ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID = 1, 2, 4, 8, 16
+REF, SPAWNING, ROBOT = -1, -2, -3
+NONE = -61   # LIW_LFE_NONE: a getter's "no such sub-map / outside the grid" (the Python getters turn it into -1 / None)
+
+
+class DimsC(C.Structure):
+    _fields_ = [("B", C.c_int), ("slots", C.c_int), ("max_points", C.c_int), ("max_lines", C.c_int), ("max_cell_entries", C.c_int)]
+
+
+def dims_struct(dims):
+    if isinstance(dims, DimsC):
+        return dims
+    s = DimsC()
+    for k, _ in DimsC._fields_:
+        setattr(s, k, int(dims[k]))
+    return s
+
+
+def _lib():
+    from . import lib
+    L = lib()
+    if not getattr(L, "_lfe_ready", False):
+        vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
+        L.liw_lfe_store_layout.argtypes = [C.POINTER(DimsC), C.POINTER(C.c_size_t)]
+        L.liw_lfe_create.restype = vp
+        L.liw_lfe_create.argtypes = [C.POINTER(LaserParamsC), C.POINTER(DimsC), C.c_int]
+        L.liw_lfe_destroy.argtypes = [vp]
+        L.liw_lfe_last_error.restype = C.c_char_p
+        L.liw_lfe_last_error.argtypes = [vp]
+        L.liw_lfe_set_geometry.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+        L.liw_lfe_store_reset.argtypes = [vp, vp, vp, vp]
+        L.liw_lfe_ranges_to_points.argtypes = [vp] * 8
+        L.liw_lfe_deskew.argtypes = [vp] * 8
+        L.liw_lfe_spawn.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+        L.liw_lfe_match.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_add_scan.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+        L.liw_lfe_pack_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_status.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.liw_lfe_num_lines.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.liw_lfe_get_lines.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int]
+        L.liw_lfe_cell_lines.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, ip, C.c_int]
+        L.liw_lfe_submap_pose.argtypes = [vp, vp, C.c_int, C.c_int, dp, dp]
+        L._lfe_ready = True
+    return L
+
+
+def store_bytes(dims):
+    """bytes of the store for dims (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
+    from . import LiwError
+    n = C.c_size_t(0)
+    r = _lib().liw_lfe_store_layout(C.byref(dims_struct(dims)), C.byref(n))
+    if r < 0:
+        raise LiwError(r, "liw_lfe_store_layout")
+    return int(n.value)
+
+
+def pad_points(point_lists, max_points):
+    """variable-length host point lists ([m_b, 3]) -> (pts [B, max_points, 3], n_pts [B]) in the device layout"""
+    B = len(point_lists)
+    pts = np.zeros((B, max_points, 3))
+    n = np.zeros(B, dtype=np.int32)
+    for b, p in enumerate(point_lists):
+        p = np.asarray(p, dtype=np.float64).reshape(-1, 3)
+        m = min(p.shape[0], max_points)
+        pts[b, :m] = p[:m]
+        n[b] = p.shape[0]
+    return pts, n
+
+
+def pad_times(time_lists, max_points):
+    B = len(time_lists)
+    out = np.zeros((B, max_points))
+    for b, t in enumerate(time_lists):
+        t = np.asarray(t, dtype=np.float64).reshape(-1)[:max_points]
+        out[b, :t.size] = t
+    return out
+
+
+class BatchFrontEnd:
+    """laser_manager's tracking-time front-end for B robots, resident on one GPU.
+
+    prm_laser: laser parameters (laser.office_laser_params layout); dims: dict(B, slots, max_points, max_lines, max_cell_entries).
+    The store is a torch uint8 tensor; every method takes / returns torch tensors on `device` and launches on torch's current
+    stream.  Slots are 0 .. slots-1; REF names the manager's reference sub-map."""
+
+    def __init__(self, prm_laser, dims, device="cuda:0"):
+        import torch
+        from . import LiwError
+        self.torch, self.LiwError = torch, LiwError
+        self.L = _lib()
+        self.dev = torch.device(device)
+        self.dims = dims_struct(dims)
+        self.B, self.slots, self.max_points = self.dims.B, self.dims.slots, self.dims.max_points
+        self._ps = laser_params_struct(prm_laser)
+        nbytes = store_bytes(self.dims)
+        index = self.dev.index if self.dev.index is not None else 0
+        self.h = C.c_void_p(self.L.liw_lfe_create(C.byref(self._ps), C.byref(self.dims), C.c_int(index)))
+        if not self.h:
+            raise LiwError(-22, "liw_lfe_create")
+        self.store = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)
+        self.n_rays = None
+        self.reset()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.liw_lfe_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, r):
+        if r < 0:
+            raise self.LiwError(r, self.L.liw_lfe_last_error(self.h).decode())
+        return r
+
+    def _s(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _t(self, a, dtype, shape=None):
+        t = self.torch.as_tensor(a, dtype=dtype, device=self.dev)
+        t = t.contiguous()
+        if shape is not None:
+            t = t.view(*shape)
+        return t
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def _mask(self, mask):
+        return None if mask is None else self._t(mask, self.torch.uint8, (self.B,))
+
+    # -------------------------------------------------------------------------------------------------------- compute
+    def set_geometry(self, n_rays, angle_min, angle_increment, time_increment):
+        self._chk(self.L.liw_lfe_set_geometry(self.h, int(n_rays), float(angle_min), float(angle_increment), float(time_increment)))
+        self.n_rays = int(n_rays)
+
+    def reset(self, mask=None):
+        """laser_manager::clear_all_scan for the masked robots (all when mask is None)"""
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_store_reset(self.h, self._p(self.store), self._p(m), self._s()))
+
+    def ranges_to_points(self, ranges, stamps, angle_min=None, angle_increment=None, time_increment=None, out=None):
+        """ranges [B, n_rays] float32, stamps [B] -> (pts [B, max_points, 3], times [B, max_points], n_pts [B] int32); `out` may be
+        such a tuple to write into (entries past n_pts are left as they are)"""
+        torch = self.torch
+        r = self._t(ranges, torch.float32)
+        if angle_min is not None:
+            self.set_geometry(r.shape[-1], angle_min, angle_increment, time_increment)
+        assert self.n_rays is not None and r.numel() == self.B * self.n_rays, "ranges must be [B, n_rays] of the geometry"
+        st = self._t(stamps, torch.float64, (self.B,))
+        if out is None:
+            pts = torch.zeros(self.B, self.max_points, 3, dtype=torch.float64, device=self.dev)
+            times = torch.zeros(self.B, self.max_points, dtype=torch.float64, device=self.dev)
+            n = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        else:
+            pts, times, n = out
+            assert pts.is_contiguous() and times.is_contiguous() and n.is_contiguous()
+            assert pts.dtype == times.dtype == torch.float64 and n.dtype == torch.int32
+            assert pts.numel() >= self.B * self.max_points * 3 and times.numel() >= self.B * self.max_points and n.numel() >= self.B
+        self._chk(self.L.liw_lfe_ranges_to_points(self.h, self._p(self.store), self._p(r), self._p(st), self._p(pts), self._p(times), self._p(n), self._s()))
+        return pts, times, n
+
+    def deskew(self, pts, times, n_pts, stamps, linear, angular):
+        """in place on pts [B, max_points, 3]; linear / angular [B, 3]"""
+        torch = self.torch
+        assert pts.is_contiguous() and pts.dtype == torch.float64 and pts.numel() == self.B * self.max_points * 3
+        tm, n = self._t(times, torch.float64), self._t(n_pts, torch.int32)
+        st, li, an = self._t(stamps, torch.float64, (self.B,)), self._t(linear, torch.float64, (self.B, 3)), self._t(angular, torch.float64, (self.B, 3))
+        self._chk(self.L.liw_lfe_deskew(self.h, self._p(pts), self._p(tm), self._p(n), self._p(st), self._p(li), self._p(an), self._s()))
+        return pts
+
+    def spawn(self, slot, pts, n_pts, times=None):
+        """laser_manager::spawn_scan into `slot`: pts [B, max_points, 3], n_pts [B], times [B] (scan time) or None"""
+        torch = self.torch
+        p = self._t(pts, torch.float64, (self.B, self.max_points, 3))
+        n = self._t(n_pts, torch.int32, (self.B,))
+        t = None if times is None else self._t(times, torch.float64, (self.B,))
+        self._chk(self.L.liw_lfe_spawn(self.h, self._p(self.store), int(slot), self._p(p), self._p(n), self._p(t), self._s()))
+
+    def match(self, slot1, slot2, pose1, pose2, kk=0, cap=256, out=None):
+        """laser_manager::do_match per robot -> dict(count [B], recs [B, cap, 12], idx1 / idx2 [B, cap], match_pose [B, 12]);
+        `out` may supply any of those (contiguous device tensors of at least that size)"""
+        torch = self.torch
+        p1 = None if pose1 is None else self._t(pose1, torch.float64, (self.B, 6))
+        p2 = self._t(pose2, torch.float64, (self.B, 6))
+        z = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device=self.dev)
+        o = dict(count=z(self.B, dt=torch.int32), recs=z(self.B, cap, 12), idx1=z(self.B, cap, dt=torch.int32), idx2=z(self.B, cap, dt=torch.int32),
+                 match_pose=z(self.B, 12)) if out is None else dict(out)
+        for k, shape, dt in (("count", (self.B,), torch.int32), ("recs", (self.B, cap, 12), torch.float64), ("idx1", (self.B, cap), torch.int32),
+                             ("idx2", (self.B, cap), torch.int32), ("match_pose", (self.B, 12), torch.float64)):
+            if k not in o:
+                o[k] = z(*shape, dt=dt)
+            assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() >= int(np.prod(shape)), k
+        o["cap"] = int(cap)
+        self._chk(self.L.liw_lfe_match(self.h, self._p(self.store), int(slot1), int(slot2), self._p(p1), self._p(p2), int(kk), int(cap),
+                                       self._p(o["count"]), self._p(o["recs"]), self._p(o["idx1"]), self._p(o["idx2"]), self._p(o["match_pose"]), self._s()))
+        return o
+
+    def match_with_ref(self, slot, pose, cap=256):
+        """laser_manager::match_with_ref of scan `slot` at pose [B, 6]"""
+        return self.match(REF, slot, None, pose, 0, cap)
+
+    def add_scan(self, slot, pose, mask=None):
+        """laser_manager::add_scan of scan `slot` at pose [B, 6] (the key-frame deque stays with the caller)"""
+        p = self._t(pose, self.torch.float64, (self.B, 6))
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_add_scan(self.h, self._p(self.store), int(slot), self._p(p), self._p(m), self._s()))
+
+    def pack_track(self, m, n=2, frame=1, out=None, L_cap=None, bufs=None):
+        """the laser arrays of B n-frame windows whose laser frame is `frame`, from a match() result.  out: dict with `match_pose`
+        [B * n * 12] and `has_match` [B * n] to write the frame's rows into (fresh zero tensors when None); bufs: laser_off [B + 1],
+        laser_frame [L_cap], laser_pts [12 * L_cap] to reuse (a double buffer across frames).  -> (dict of
+        laser_off, laser_frame, laser_pts, match_pose, has_match, Ltot); the dict can go into BatchSolver.rebind with the other inputs."""
+        torch = self.torch
+        cap = int(m["cap"])
+        L_cap = self.B * cap if L_cap is None else int(L_cap)
+        out = dict(out or {})
+        if "match_pose" not in out:
+            out["match_pose"] = torch.zeros(self.B * n * 12, dtype=torch.float64, device=self.dev)
+        if "has_match" not in out:
+            out["has_match"] = torch.zeros(self.B * n, dtype=torch.uint8, device=self.dev)
+        if bufs is None:   # every entry the result exposes is written by the call
+            bufs = dict(laser_off=torch.empty(self.B + 1, dtype=torch.int32, device=self.dev),
+                        laser_frame=torch.empty(max(L_cap, 1), dtype=torch.int32, device=self.dev),
+                        laser_pts=torch.empty(12 * max(L_cap, 1), dtype=torch.float64, device=self.dev))
+        off, lf, lp = bufs["laser_off"], bufs["laser_frame"], bufs["laser_pts"]
+        assert off.numel() >= self.B + 1 and lf.numel() >= max(L_cap, 1) and lp.numel() >= 12 * max(L_cap, 1)
+        Ltot = self._chk(self.L.liw_lfe_pack_track(self.h, int(n), int(frame), cap, self._p(m["count"]), self._p(m["recs"]), self._p(m["match_pose"]),
+                                                   L_cap, self._p(off), self._p(lf), self._p(lp), self._p(out["match_pose"]), self._p(out["has_match"]), self._s()))
+        res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
+        return res, Ltot
+
+    # -------------------------------------------------------------------------------------------------------- getters
+    def status(self, robot, slot=ROBOT):
+        """status word (-1 for a missing sub-map)"""
+        return self._chk_get(self.L.liw_lfe_status(self.h, self._p(self.store), int(robot), int(slot)), allow_missing=True)
+
+    def _chk_get(self, r, allow_missing=False):
+        if allow_missing and r == NONE:
+            return -1
+        if r < 0:
+            raise self.LiwError(r, self.L.liw_lfe_last_error(self.h).decode())
+        return r
+
+    def num_lines(self, robot, slot):
+        """number of lines (-1 for a missing sub-map)"""
+        return self._chk_get(self.L.liw_lfe_num_lines(self.h, self._p(self.store), int(robot), int(slot)), allow_missing=True)
+
+    def get_lines(self, robot, slot):
+        """[num_lines, 10] = p1 p2 abc len in scan::lines order (None for a missing sub-map)"""
+        n = self.num_lines(robot, slot)
+        if n < 0:
+            return None
+        out = np.zeros((max(n, 1), 10))
+        k = self._chk_get(self.L.liw_lfe_get_lines(self.h, self._p(self.store), int(robot), int(slot), out.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return out[:k].copy()
+
+    def cell_lines(self, robot, slot, x, y, cap=64):
+        """(cell size, ids) as laser.Scan.cell_lines: size -1 outside the grid or for a missing sub-map"""
+        ids = np.zeros(cap, dtype=np.int32)
+        k = self._chk_get(self.L.liw_lfe_cell_lines(self.h, self._p(self.store), int(robot), int(slot), float(x), float(y),
+                                                    ids.ctypes.data_as(C.POINTER(C.c_int)), int(cap)), allow_missing=True)
+        return k, ids[:max(0, min(k, cap))].copy()
+
+    def submap_pose(self, robot, slot=REF):
+        p, q = np.zeros(3), np.zeros(3)
+        r = self._chk_get(self.L.liw_lfe_submap_pose(self.h, self._p(self.store), int(robot), int(slot), p.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     q.ctypes.data_as(C.POINTER(C.c_double))), allow_missing=True)
+        return None if r < 0 else (p, q)

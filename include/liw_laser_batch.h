@@ -1,0 +1,136 @@
+/* liw_laser_batch.h — C ABI of the batched laser front-end on the device: the tracking-time work of liw_laser.h for B robots
+ * at once (ranges -> points -> de-skew -> lines -> matches against the reference sub-map -> sub-map update -> the laser arrays
+ * of a liw_batch), so that a fleet's frame never leaves device memory.  The single-scan host front-end (liw_laser.h) is the
+ * parity reference of every entry point here.
+ *
+ * Conventions as the batch API of liw_window.h:
+ *   - the caller owns all device memory: the store (sized by liw_lfe_store_layout) and every input / output array;
+ *   - every launch goes on the caller's `stream` (a hipStream_t; NULL = the null stream);
+ *   - calls return 0 (or a documented count) on success and a negative LIW_E* code otherwise;
+ *   - there is NO CPU fallback: without a gfx950 device liw_lfe_create still returns a ctx, but every compute entry returns
+ *     LIW_ENODEV.  liw_lfe_store_layout is host-only and works anywhere.
+ * fp64 everywhere except the LaserScan ranges (float32, as sensor_msgs/LaserScan).  Points are [robot][max_points][3] in the
+ * LASER frame; poses [robot][6] = (p, q = rotation vector) of the IMU in the world, as in liw_laser.h.
+ *
+ * The store holds, per robot: a status word and the laser_manager state (reference / spawning sub-maps and their poses,
+ * last_add_tf, current_count), and `slots` scan slots plus the two sub-map slots.  A scan slot holds the scan time, its
+ * lines in scan::lines order ([p1 p2 abc len]) and the sparse line_map as sorted (cell, line index) entries.
+ *
+ * Capacity: a scan with more than max_lines lines or max_cell_entries cell entries, a robot with more than max_points points
+ * and a match with more than `cap` pairs set a LIW_LFE_ST_* bit in the robot's status word (and in the slot's, for a slot).  A
+ * slot with a bit set is invalid: a match against it has count 0.  Nothing is ever written outside the robot's own region of
+ * the store or of an output array; other robots are unaffected.
+ *
+ * Numerics: the front-end kernels are compiled without FMA contraction, like the host.  ranges_to_points, spawn and the
+ * end points of the lines are bit-identical to the host; transforms built by make_tf (deskew, match, add_scan) use the device
+ * sin / cos and agree to round-off.  Decisions through acos (segment merge, the 10 degree gate, the argmin, and the motion
+ * filter's rotation angle, via log_SO3) use the device acos, which may differ from glibc's by an ulp: a decision can only
+ * differ from the host where two quantities are within an ulp of each other.
+ */
+#ifndef LIW_LASER_BATCH_H
+#define LIW_LASER_BATCH_H
+#include <stddef.h>
+
+#include "liw_laser.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* status bits (robot word and slot word) */
+#define LIW_LFE_ST_POINTS 1    /* more kept points than max_points (the point arrays hold the first max_points) */
+#define LIW_LFE_ST_LINES 2     /* more lines than max_lines */
+#define LIW_LFE_ST_CELLS 4     /* more cell entries than max_cell_entries */
+#define LIW_LFE_ST_MATCH 8     /* a match had more pairs than `cap` (count = 0 written) */
+#define LIW_LFE_ST_INVALID 16  /* an operation read an invalid slot */
+
+/* slot selectors besides 0 .. slots-1 */
+#define LIW_LFE_REF (-1)       /* the manager's current reference sub-map */
+#define LIW_LFE_SPAWNING (-2)  /* the manager's spawning sub-map (getters only) */
+#define LIW_LFE_ROBOT (-3)     /* liw_lfe_status: the robot's accumulated status word */
+
+/* getter result for a sub-map that does not exist or a point outside the grid (distinct from every LIW_E* code) */
+#define LIW_LFE_NONE (-61)
+
+typedef struct liw_lfe_dims {
+    int B;                 /* robots */
+    int slots;             /* scan slots per robot (besides the two sub-map slots) */
+    int max_points;        /* points per robot (ranges_to_points / deskew / spawn arrays) */
+    int max_lines;         /* lines per slot (scan slots and sub-maps) */
+    int max_cell_entries;  /* line_map entries per slot */
+} liw_lfe_dims;
+
+typedef struct liw_lfe_ctx liw_lfe_ctx;
+
+/* bytes of the store for `dims`; LIW_EINVAL for a non-positive dimension.  Host-only. */
+int liw_lfe_store_layout(const liw_lfe_dims* dims, size_t* bytes);
+
+/* a ctx bound to the laser parameters and dims (device = HIP device ordinal).  NULL only on a bad argument. */
+liw_lfe_ctx* liw_lfe_create(const liw_laser_params* prm, const liw_lfe_dims* dims, int device);
+void liw_lfe_destroy(liw_lfe_ctx* ctx);
+const char* liw_lfe_last_error(liw_lfe_ctx* ctx);
+
+/* LaserScan geometry shared by all robots: the host computes the (cosf, sinf) table of the n_rays angles once with the host libm
+ * (what liw_laser_to_points uses) and keeps it on the device; synchronous. */
+int liw_lfe_set_geometry(liw_lfe_ctx* ctx, int n_rays, float angle_min, float angle_increment, float time_increment);
+
+/* laser_manager::clear_all_scan for the robots with mask[b] != 0 (all when mask is NULL): empties their scan slots, sub-maps,
+ * manager state and status word.  A fresh store must be reset once before use. */
+int liw_lfe_store_reset(liw_lfe_ctx* ctx, void* store, const unsigned char* mask, void* stream);
+
+/* liw_laser_to_points per robot: ranges [B][n_rays] float32, stamps [B] -> pts [B][max_points][3], times [B][max_points],
+ * n_pts [B].  Bit-identical to the host.  A robot with more than max_points kept points gets n_pts = max_points + 1 (the arrays
+ * hold its first max_points points), which liw_lfe_spawn rejects: the slot is invalid.  `store` may be NULL; otherwise an
+ * overflow also sets LIW_LFE_ST_POINTS in the robot word. */
+int liw_lfe_ranges_to_points(liw_lfe_ctx* ctx, void* store, const float* ranges, const double* stamps, double* pts, double* times,
+                             int* n_pts, void* stream);
+
+/* liw_laser_correct per robot, in place: linear [B][3], angular [B][3] body twist at stamps [B]. */
+int liw_lfe_deskew(liw_lfe_ctx* ctx, double* pts, const double* times, const int* n_pts, const double* stamps, const double* linear,
+                   const double* angular, void* stream);
+
+/* liw_scan_spawn per robot into scan slot `slot` (0 .. slots-1): pts [B][max_points][3], n_pts [B], times [B] (scan time, may be
+ * NULL = 0).  n_pts outside 0 .. max_points leaves the slot empty and invalid (LIW_LFE_ST_POINTS).  Corners are not computed
+ * (only the back-end reads them). */
+int liw_lfe_spawn(liw_lfe_ctx* ctx, void* store, int slot, const double* pts, const int* n_pts, const double* times, void* stream);
+
+/* liw_laser_do_match(slot1, slot2, pose1, pose2, kk) per robot.  slot1 = LIW_LFE_REF matches against the reference sub-map with
+ * its stored pose as p1, q1 (pose1 is ignored and may be NULL), as laser_manager::match_with_ref; no reference gives count 0 and
+ * the pose record (p2 q2 p2 q2) of an empty match.  Outputs: count [B], recs [B][cap][12] (lines1.p1 p1.p2 lines2.p1 lines2.p2),
+ * idx1 / idx2 [B][cap] (indices in scan::lines; either may be NULL), match_pose [B][12] = p1 q1 p2 q2. */
+int liw_lfe_match(liw_lfe_ctx* ctx, void* store, int slot1, int slot2, const double* pose1, const double* pose2, int kk, int cap,
+                  int* count, double* recs, int* idx1, int* idx2, double* match_pose, void* stream);
+
+/* laser_manager::add_scan of scan slot `src_slot` at pose [B][6] for the robots with mask[b] != 0 (all when NULL): motion filter,
+ * first-scan sub-map, rasterisation into the reference and spawning sub-maps, the ref_n_accumulation swap.  The key-frame deque
+ * stays with the caller.  An invalid source slot makes every sub-map the call writes invalid (its status and
+ * LIW_LFE_ST_INVALID), so matches against it have count 0 until that sub-map is replaced. */
+int liw_lfe_add_scan(liw_lfe_ctx* ctx, void* store, int src_slot, const double* pose, const unsigned char* mask, void* stream);
+
+/* The laser arrays of a liw_batch of B n-frame windows whose laser blocks all belong to frame `frame` (n = 2 tracking: 1), from a
+ * liw_lfe_match output (count, recs with row stride cap, match_pose):
+ *   laser_off [B+1], laser_frame [Ltot] (= frame), laser_pts [12][Ltot] component-major, match_pose_out [B][n][12] row `frame`,
+ *   has_match [B][n] row `frame` (= 1).  Rows of other frames are not touched.
+ * laser_frame / laser_pts must hold L_cap blocks; Ltot > L_cap is LIW_ENOMEM (nothing but laser_off written).  Returns Ltot:
+ * the one host read-back (a 4-byte copy and a synchronisation of `stream`). */
+int liw_lfe_pack_track(liw_lfe_ctx* ctx, int n, int frame, int cap, const int* count, const double* recs, const double* match_pose,
+                       int L_cap, int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match,
+                       void* stream);
+
+/* getters (synchronous device -> host copies; tests and tools).  slot: 0 .. slots-1, LIW_LFE_REF or LIW_LFE_SPAWNING. */
+/* status word of robot / slot (slot = LIW_LFE_ROBOT: the robot word); a missing sub-map reads LIW_LFE_NONE */
+int liw_lfe_status(liw_lfe_ctx* ctx, const void* store, int robot, int slot);
+/* number of lines (LIW_LFE_NONE: missing sub-map) */
+int liw_lfe_num_lines(liw_lfe_ctx* ctx, const void* store, int robot, int slot);
+/* lines [num_lines][10] = p1 p2 abc len in scan::lines order; returns the number written (<= cap) */
+int liw_lfe_get_lines(liw_lfe_ctx* ctx, const void* store, int robot, int slot, double* out, int cap);
+/* line_map of the cell containing (x, y), as liw_scan_cell_lines: ids (scan::lines indices, push order), returns the cell's size,
+ * LIW_LFE_NONE outside the grid or for a missing sub-map */
+int liw_lfe_cell_lines(liw_lfe_ctx* ctx, const void* store, int robot, int slot, double x, double y, int* ids, int cap);
+/* pose p3, q3 of a sub-map slot (LIW_LFE_REF / LIW_LFE_SPAWNING); 0 if it exists, LIW_LFE_NONE if not */
+int liw_lfe_submap_pose(liw_lfe_ctx* ctx, const void* store, int robot, int slot, double* p3, double* q3);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,167 @@
+"""Device time of the batched laser front-end (laser_batch.BatchFrontEnd) per stage, one JSON line.
+
+B robots (default 4 096 and 49 152) with 1 080-ray scans tiled from 64 distinct rooms / poses.  Per B: ranges -> points, spawn,
+match against the reference sub-map, add_scan (the accumulating call: the reference exists) and pack_track, each timed with
+HIP events on the current stream (median of --reps after one warm-up); scans/s = B / ms.  For comparison the same line carries
+the host front-end (liw.laser through ctypes) per scan over 256 robots: laser_to_points, Scan.spawn, match_with_ref, add_scan.
+
+  python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+N_RAYS = 1080
+ANG_MIN = np.float32(-2.0 * np.pi * 0.75 / 2)
+ANG_INC = np.float32(2.0 * np.pi * 0.75 / (N_RAYS - 1))
+T_INC = np.float32(1.0 / (40.0 * N_RAYS))
+
+
+def _T(p, q):
+    th = np.linalg.norm(q)
+    R = np.eye(3)
+    if th > 1e-15:
+        k = q / th
+        K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+        R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, p
+    return T
+
+
+def scenes(liw, lp, nd, seed=4242):
+    """nd distinct (ranges at pose a, ranges at pose b, pose a, pose b)"""
+    rng = np.random.default_rng(seed)
+    Til = np.asarray(lp["T_imu_to_laser"], dtype=np.float64).reshape(4, 4)
+    ra, rb, pa, pb = [], [], [], []
+    for j in range(nd):
+        segs = liw.laser.room_segments(5000 + j)
+        a = np.concatenate([rng.uniform(-1, 1, 2), [0.0, 0.0, 0.0], rng.uniform(-np.pi, np.pi, 1)])
+        b = a.copy()
+        b[:2] += rng.uniform(-0.15, 0.15, 2)
+        b[5] += rng.uniform(-0.07, 0.07)
+        ra.append(liw.laser.cast_scan(segs, _T(a[:3], a[3:]) @ Til, n_rays=N_RAYS, seed=2 * j)[0])
+        rb.append(liw.laser.cast_scan(segs, _T(b[:3], b[3:]) @ Til, n_rays=N_RAYS, seed=2 * j + 1)[0])
+        pa.append(a)
+        pb.append(b)
+    return np.stack(ra), np.stack(rb), np.stack(pa), np.stack(pb)
+
+
+def timed(torch, fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts))
+
+
+def device_run(liw, torch, lp, B, sc, reps, cap=256):
+    ra, rb, pa, pb = sc
+    nd = ra.shape[0]
+    rob = np.arange(B) % nd
+    fe = liw.laser_batch.BatchFrontEnd(lp, dict(B=B, slots=2, max_points=N_RAYS, max_lines=256, max_cell_entries=8192))
+    fe.set_geometry(N_RAYS, ANG_MIN, ANG_INC, T_INC)
+    RA = torch.from_numpy(ra).cuda()[torch.from_numpy(rob).cuda()].contiguous()
+    RB = torch.from_numpy(rb).cuda()[torch.from_numpy(rob).cuda()].contiguous()
+    PA, PB = torch.from_numpy(pa[rob]).cuda(), torch.from_numpy(pb[rob]).cuda()
+    stamps = torch.zeros(B, dtype=torch.float64, device="cuda")
+    out = {}
+    a = fe.ranges_to_points(RA, stamps)
+    b = fe.ranges_to_points(RB, stamps)
+    out["ranges_to_points_ms"] = timed(torch, lambda: fe.ranges_to_points(RB, stamps, out=b), reps)
+    out["spawn_ms"] = timed(torch, lambda: fe.spawn(1, b[0], b[2]), reps)
+
+    def fresh():   # reset, both scans spawned, the first scan added (the reference sub-map exists)
+        fe.reset()
+        fe.spawn(0, a[0], a[2])
+        fe.spawn(1, b[0], b[2])
+        fe.add_scan(0, PA)
+
+    def add_b():   # the accumulating add_scan; the first-scan call is not part of the timing
+        fresh()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fe.add_scan(1, PB)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+    add_b()
+    out["add_scan_ms"] = float(np.median([add_b() for _ in range(reps)]))
+    fresh()
+    m = fe.match_with_ref(1, PB, cap=cap)
+    mbufs = {k: m[k] for k in ("count", "recs", "idx1", "idx2", "match_pose")}   # outputs allocated outside the timed region
+    out["match_with_ref_ms"] = timed(torch, lambda: fe.match(liw.laser_batch.REF, 1, None, PB, 0, cap, out=mbufs), reps)
+    pk, Ltot = fe.pack_track(m)
+    bufs = dict(laser_off=pk["laser_off"], laser_frame=torch.empty(B * cap, dtype=torch.int32, device="cuda"),
+                laser_pts=torch.empty(12 * B * cap, dtype=torch.float64, device="cuda"))
+    mo = dict(match_pose=pk["match_pose"], has_match=pk["has_match"])
+    out["pack_track_ms"] = timed(torch, lambda: fe.pack_track(m, out=mo, bufs=bufs), reps)   # includes the Ltot read-back
+    out["frame_ms"] = out["ranges_to_points_ms"] + out["spawn_ms"] + out["match_with_ref_ms"] + out["add_scan_ms"] + out["pack_track_ms"]
+    for k in ("ranges_to_points", "spawn", "match_with_ref", "add_scan", "pack_track", "frame"):
+        out[k + "_scans_per_s"] = B / (out[k + "_ms"] * 1e-3)
+    out["Ltot"] = int(Ltot)
+    out["pairs_per_robot"] = Ltot / B
+    del fe
+    torch.cuda.empty_cache()
+    return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
+
+
+def host_run(liw, lp, sc, n=256):
+    ra, rb, pa, pb = sc
+    nd = ra.shape[0]
+    t = dict(ranges_to_points=0.0, spawn=0.0, match_with_ref=0.0, add_scan=0.0)
+    for i in range(n):
+        j = i % nd
+        m = liw.laser.LaserManager(lp)
+        pts, _ = liw.laser.laser_to_points(ra[j], ANG_MIN, ANG_INC, T_INC, 0.0)
+        m.add_scan(liw.laser.Scan.spawn(lp, pts), pa[j, :3], pa[j, 3:])
+        t0 = time.perf_counter()
+        pts, _ = liw.laser.laser_to_points(rb[j], ANG_MIN, ANG_INC, T_INC, 0.0)
+        t1 = time.perf_counter()
+        s = liw.laser.Scan.spawn(lp, pts)
+        t2 = time.perf_counter()
+        m.match_with_ref(s, pb[j, :3], pb[j, 3:])
+        t3 = time.perf_counter()
+        m.add_scan(s, pb[j, :3], pb[j, 3:])
+        t4 = time.perf_counter()
+        for k, v in zip(t, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+            t[k] += v
+    out = {k + "_us": round(v / n * 1e6, 2) for k, v in t.items()}
+    out["frame_us"] = round(sum(t.values()) / n * 1e6, 2)
+    out["robots"] = n
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", default="4096,49152")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--distinct", type=int, default=64)
+    a = ap.parse_args()
+    import torch
+    liw = importlib.import_module("2dliw-slam_amd")
+    lp = liw.laser.office_laser_params()
+    sc = scenes(liw, lp, a.distinct)
+    res = dict(tool="bench_laser_batch", n_rays=N_RAYS, distinct=a.distinct, device=torch.cuda.get_device_name(0), batch={})
+    for B in [int(x) for x in a.B.split(",")]:
+        res["batch"][str(B)] = device_run(liw, torch, lp, B, sc, a.reps)
+    res["host_per_scan"] = host_run(liw, lp, sc)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
