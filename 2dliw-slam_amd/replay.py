@@ -27,6 +27,19 @@ def replay_room():
     return [(np.array(a, dtype=np.float64), np.array(b, dtype=np.float64)) for a, b in segs]
 
 
+def pillar_room():
+    """replay_room plus twelve 0.4 m square pillars off the circle (8 outside it, 4 between it and the inner box): corners for
+    loop detection"""
+    segs = replay_room()
+    centres = [(7.0 * np.cos(a), 5.0 + 7.0 * np.sin(a)) for a in np.arange(8) * np.pi / 4]
+    centres += [(3.0 * np.cos(a), 5.0 + 3.0 * np.sin(a)) for a in np.arange(4) * np.pi / 2 + np.pi / 4]
+    h = 0.2
+    for x, y in centres:
+        pts = [(x - h, y - h), (x + h, y - h), (x + h, y + h), (x - h, y + h)]
+        segs += [(np.array(pts[k], dtype=np.float64), np.array(pts[(k + 1) % 4], dtype=np.float64)) for k in range(4)]
+    return segs
+
+
 def cast_scan_moving(segs, pose_of_time, t0, n_rays, fov, time_increment, noise, rng, max_range=30.0):
     """Ray i is cast from the laser pose at t0 + i * time_increment (a real spinning lidar): float32 ranges."""
     angle_min, inc = -fov / 2, fov / (n_rays - 1)
@@ -63,13 +76,13 @@ def cast_scan_moving(segs, pose_of_time, t0, n_rays, fov, time_increment, noise,
 
 
 def make_log(prm, duration=3.0, seed=0, imu_rate=200.0, wheel_rate=20.0, laser_rate=10.0, n_rays=720, scan_time=0.04,
-             motion="arc", odom_noise=2e-4, **truth_kw):
+             motion="arc", odom_noise=2e-4, room=None, **truth_kw):
     """-> list of messages (dicts with 'type', 'time', ...), strictly increasing distinct stamps.
     motion / truth_kw: synth._Truth (e.g. "standstill_then_go" with t_go, "stop_and_go" with t_stop / pause); odom_noise = 0 gives the
-    bit-identical odometry readings of a robot at rest."""
+    bit-identical odometry readings of a robot at rest.  room: wall segments (default replay_room())."""
     rng = np.random.default_rng(seed)
     tr = synth._Truth(prm, motion=motion, **truth_kw)
-    room = replay_room()
+    room = replay_room() if room is None else room
     bias = rng.normal(0.0, 1e-3, 6)
     msgs = []
     for k in range(int(duration * imu_rate)):

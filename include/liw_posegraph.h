@@ -8,7 +8,7 @@
  * On the MI355X: one 16-lane group per edge evaluates residual + Jacobian (dual numbers, direction per lane), the normal
  * equations are assembled as a dense fp64 matrix in HBM (6 unknowns per key frame) and factorised by a blocked right-
  * looking Cholesky whose trailing update runs on the fp64 matrix cores; the trust-region bookkeeping runs on the host.
- * Loop DETECTION (keyframe_manager.cpp:642-712, :945-1183) is not part of this library.
+ * Loop DETECTION (keyframe_manager.cpp:642-712, :945-1183) is include/liw_loop.h.
  */
 #ifndef LIW_POSEGRAPH_H
 #define LIW_POSEGRAPH_H

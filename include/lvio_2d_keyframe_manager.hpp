@@ -6,21 +6,25 @@
 //   solve                              :722-838             -> liw_posegraph_solve (the MI355X relinearisation)
 //   is_time_to_solve                   :839-848             "a loop is pending and 10 s have passed since the last solve"
 //   ~keyframe_manager                  :370-397             back_end.txt (TUM) of every key frame
-// Out of scope: loop DETECTION (laser_loop_detect, :642-712 and the descriptor code behind it).  A detector is a
-// callback here: when key frame `index` arrives it may return an edge (index1 = index, index2 = an older key frame, tf12) — the
-// shape laser_loop_detect returns (:664-665, :702).  Two deliberate differences of this offline form: the back-end runs on the
-// caller's thread (the reference has its own thread, keyframe_manager.cpp:859-881) and is_time_to_solve compares key-frame
-// STAMPS instead of ros::WallTime, so that a replay is deterministic.
+//   laser_loop_detect                  :642-712             opt-in built-in detector (enable_loop_detection -> include/lvio_2d_loop.hpp,
+//                                                           the MI355X descriptor match), fed here because it needs tfs_tracking
+// A detector may instead be a callback: when key frame `index` arrives it may return an edge (index1 = index, index2 = an older key
+// frame, tf12) — the shape laser_loop_detect returns (:664-665, :702); a callback, when set, takes precedence.  When the built-in
+// detector holds max_keyframes key frames, detection stops (loop_stopped) and the back-end goes on.  Two deliberate differences of
+// this offline form: the back-end runs on the caller's thread (the reference has its own thread, keyframe_manager.cpp:859-881) and
+// is_time_to_solve compares key-frame STAMPS instead of ros::WallTime, so that a replay is deterministic.
 #pragma once
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "liw_io.h"
 #include "liw_lie.h"
 #include "liw_posegraph.h"
+#include "lvio_2d_loop.hpp"
 #include "lvio_2d_solver.hpp"
 
 namespace lvio_2d {
@@ -48,12 +52,19 @@ public:
     }
     ~keyframe_manager() {
         if (kp_.output_tum) write_tum((kp_.output_dir + "back_end.txt").c_str());
+        loop_.reset();   // the detector is bound to ctx_
         liw_destroy(ctx_);
     }
     keyframe_manager(const keyframe_manager&) = delete;
     keyframe_manager& operator=(const keyframe_manager&) = delete;
 
     void set_loop_detector(loop_detector d) { detector_ = std::move(d); }
+    // the built-in laser loop detector (liw_loop.h) on this manager's ctx; false if the parameters or dims are rejected
+    bool enable_loop_detection(const liw_loop_params& p, const liw_loop_dims& d) {
+        loop_.reset(new laser_loop_detector(ctx_, p, d));
+        if (!loop_->ok()) { loop_.reset(); return false; }
+        return true;
+    }
 
     // add_keyframe (:400-407) + do_add_keyframe (:419-482) in one call: no worker thread in the offline form
     void add_keyframe(const frame_info::ptr& frame_ptr) {
@@ -64,6 +75,16 @@ public:
         double corrected[12];
         liw_lie_mul(modify_delta_tf, tr, corrected);
         liw_lie_log_SE3(corrected, frame_ptr->p, frame_ptr->q);
+        int loop_status = 0;
+        bool detect_now = false;
+        if (loop_ && !detector_ && !loop_stopped) {   // the laser map feature of every key frame (:428-437)
+            if (loop_->full()) loop_stopped = true;   // capacity reached: detection ends, the back-end goes on with the loops it has
+            else {
+                const int r = loop_->add_keyframe(frame_ptr->type == frame_info::laser, tr, frame_ptr->laser_concers);
+                if (r < 0) loop_status = r;
+                else detect_now = true;
+            }
+        }
         if (keyframe_queue.size() > 1) {
             const int index1 = (int)keyframe_queue.size() - 2, index2 = index1 + 1;
             edge e{index1, index2, {}};
@@ -79,6 +100,22 @@ public:
                 has_loop_wait_for_solve = true;
                 last_loop_index = (int)keyframe_queue.size() - 1;
             }
+        } else if (frame_ptr->type == frame_info::laser && detect_now) {
+            liw_loop_edge le{};
+            const int r = loop_->detect(&le);
+            if (r < 0) loop_status = r;
+            else if (r == 1) {
+                edge lp{le.index1, le.index2, {}};
+                std::memcpy(lp.tf12, le.tf12, sizeof lp.tf12);
+                loop_edges.push_back(lp);
+                has_loop_wait_for_solve = true;
+                last_loop_index = (int)keyframe_queue.size() - 1;
+            }
+        }
+        if (loop_status) {   // a detector error stops the back-end like a failed solve
+            last_status = loop_status;
+            loop_error_ = loop_->last_error();
+            return;
         }
         double last_frame_tf[12];
         std::memcpy(last_frame_tf, tr, sizeof last_frame_tf);
@@ -135,7 +172,8 @@ public:
         return true;
     }
 
-    const char* last_error() const { return liw_last_error(ctx_); }
+    const laser_loop_detector* laser_loop() const { return loop_.get(); }
+    const char* last_error() const { return loop_error_.empty() ? liw_last_error(ctx_) : loop_error_.c_str(); }
 
     std::deque<frame_info::ptr> keyframe_queue;
     struct tf12 { double v[12]; };
@@ -143,6 +181,7 @@ public:
     std::vector<edge> seq_edges, loop_edges;
     double modify_delta_tf[12];
     bool has_loop_wait_for_solve = false;
+    bool loop_stopped = false;   // the built-in detector held max_keyframes key frames: no detection after that
     int last_loop_index = -1, solves = 0;
     double last_solve_time = -1e300;
     int last_status = 0;
@@ -154,6 +193,8 @@ private:
     keyframe_manager_params kp_;
     liw_ctx* ctx_;
     loop_detector detector_;
+    std::unique_ptr<laser_loop_detector> loop_;
+    std::string loop_error_;
     double zero3_[3] = {0, 0, 0};
 };
 

@@ -3,14 +3,20 @@
 //   usage: replay_log <log.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file>] [--solve-period S] [--pg-iters K]
 //     --keep N         frames kept in the window after a tracking solve (trajectory_params::keep_window_size; 1 = reference)
 //     --loops <file>   enables the back-end (include/lvio_2d_keyframe_manager.hpp -> liw_posegraph_solve) with a loop-edge schedule
-//                      standing in for loop detection: int32 count, then per edge int32 trigger key frame, int32 older key frame,
-//                      float64 tf12[12]
+//                      given by hand: int32 count, then per edge int32 trigger key frame, int32 older key frame, float64 tf12[12]
+//     --detect-loops   enables the back-end with the built-in laser loop detector instead (include/lvio_2d_loop.hpp, the values of
+//                      config/office.yaml:98-108); not together with --loops.  Also writes <output_dir>loop_edges.bin: int32 count,
+//                      then per edge int32 index1, index2, float64 tf12[12]
+//     --loop-dims K P  detector capacity: K key frames, P points per sub-map (default 2048 256).  After K key frames detection
+//                      stops (the back-end goes on with the loops found so far); a sub-map of more than P points is never matched.
+//                      Both are reported on stderr at the end.
 // writes <output_dir>fornt_end.txt (TUM trajectory, the reference's file name), <output_dir>traj.md (record tables),
 // <output_dir>result.bin: int32 status, frames, tracked, initializations, keyframes, solver_status; float64 time, state[15], and with
 // --loops <output_dir>back_end.txt (TUM of the key frames, keyframe_manager.cpp:370-397) + <output_dir>backend.bin: int32 key frames,
 // loop edges, solves, LM iterations of the last solve; float64 modify_delta_tf[12], current pose in the corrected frame [6], poses [N][6].
 //   replay_log --backend-only <keyframes.bin> <output_dir/> --loops <file> [...]: no front-end; the key frames (int32 N, then per key
 //   frame float64 time, p[3], q[3]) are handed to lvio_2d::keyframe_manager one by one (same outputs: back_end.txt, backend.bin).
+//   Not with --detect-loops: those key frames carry no corners.
 // Parameters are the values of reference config/office.yaml.  Exit code 19 (LIW_ENODEV) when no MI355X is usable.
 #include <cstdio>
 #include <cstdlib>
@@ -30,7 +36,7 @@ static const double OFFICE_T_IMU_TO_LASER[16] = {0.0019070, -0.9999900, 0.004043
 int main(int argc, char** argv) {
     bool backend_only = false;
     if (argc > 1 && std::string(argv[1]) == "--backend-only") { backend_only = true; --argc; ++argv; }
-    if (argc < 3) { fprintf(stderr, "usage: replay_log [--backend-only] <log.bin | keyframes.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file>]\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: replay_log [--backend-only] <log.bin | keyframes.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file> | --detect-loops]\n"); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
     liw_params prm{};
@@ -49,6 +55,8 @@ int main(int argc, char** argv) {
     tp.output_dir = argv[2];
     int look_ahead = 40;
     const char* loops_path = nullptr;
+    bool detect_loops = false;
+    liw_loop_dims loop_dims{2048, 256};
     lvio_2d::keyframe_manager_params kp;
     for (int k = 0; k < 3; ++k) { kp.pg.loop_sigma_p[k] = 0.1; kp.pg.loop_sigma_q[k] = 0.01; }   // config/office.yaml:106-115
     kp.pg.loop_edge_k = 10.0; kp.pg.use_ground_p_factor = 1; kp.pg.use_ground_q_factor = 1;
@@ -57,11 +65,15 @@ int main(int argc, char** argv) {
         const std::string s = argv[a];
         if (s == "--keep" && a + 1 < argc) tp.keep_window_size = atoi(argv[++a]);
         else if (s == "--loops" && a + 1 < argc) loops_path = argv[++a];
+        else if (s == "--detect-loops") detect_loops = true;
+        else if (s == "--loop-dims" && a + 2 < argc) { loop_dims.max_keyframes = atoi(argv[a + 1]); loop_dims.max_points = atoi(argv[a + 2]); a += 2; }
         else if (s == "--solve-period" && a + 1 < argc) kp.solve_period = atof(argv[++a]);
         else if (s == "--pg-iters" && a + 1 < argc) kp.max_iterations = atoi(argv[++a]);
         else if (a == 3 && s[0] != '-') look_ahead = atoi(argv[a]);
         else { fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
     }
+    if (detect_loops && loops_path) { fprintf(stderr, "--detect-loops and --loops exclude each other\n"); return 2; }
+    if (detect_loops && backend_only) { fprintf(stderr, "--backend-only key frames carry no corners: use --loops, not --detect-loops\n"); return 2; }
     struct loop_rec { int trigger, older; double tf12[12]; };
     std::vector<loop_rec> schedule;
     if (loops_path) {
@@ -86,6 +98,10 @@ int main(int argc, char** argv) {
                     if (l.trigger == index) { e->index1 = index; e->index2 = l.older; std::memcpy(e->tf12, l.tf12, sizeof l.tf12); return true; }
                 return false;
             });
+            traj.set_other_frame_sink([&](const std::deque<lvio_2d::frame_info::ptr>& fi) { km->update_other_frame(fi, backend_pose, backend_pose + 3); });
+        } else if (detect_loops) {
+            km.reset(new lvio_2d::keyframe_manager(prm, kp));
+            if (!km->enable_loop_detection(lvio_2d::office_loop_params(), loop_dims)) { fprintf(stderr, "bad --loop-dims\n"); return 2; }
             traj.set_other_frame_sink([&](const std::deque<lvio_2d::frame_info::ptr>& fi) { km->update_other_frame(fi, backend_pose, backend_pose + 3); });
         }
         traj.set_keyframe_sink([&](const lvio_2d::frame_info::ptr& f) { ++keyframes; if (km) km->add_keyframe(f); });
@@ -158,6 +174,33 @@ int main(int argc, char** argv) {
                 fwrite(backend_pose, sizeof(double), 6, b);
                 for (const auto& f : km->keyframe_queue) { fwrite(f->p, sizeof(double), 3, b); fwrite(f->q, sizeof(double), 3, b); }
                 fclose(b);
+            }
+            if (detect_loops) {
+                FILE* le = fopen((std::string(argv[2]) + "loop_edges.bin").c_str(), "wb");
+                if (le) {
+                    const int n = (int)km->loop_edges.size();
+                    fwrite(&n, sizeof(int), 1, le);
+                    for (const auto& e : km->loop_edges) {
+                        const int ii[2] = {e.index1, e.index2};
+                        fwrite(ii, sizeof(int), 2, le);
+                        fwrite(e.tf12, sizeof(double), 12, le);
+                    }
+                    fclose(le);
+                }
+                int nf = 0, pmin = 1 << 30, pmax = 0, nover = 0;
+                long long psum = 0;
+                liw_loop* lh = km->laser_loop() ? km->laser_loop()->handle() : nullptr;
+                for (int k = 0; lh && k < liw_loop_num_keyframes(lh); ++k) {
+                    int np = 0;
+                    const int st = liw_loop_status(lh, k, &np, nullptr);
+                    if (st == LIW_LOOP_NULL) continue;
+                    if (st == LIW_LOOP_OVER_CAP) ++nover;
+                    ++nf; psum += np; pmin = np < pmin ? np : pmin; pmax = np > pmax ? np : pmax;
+                }
+                if (nf) fprintf(stderr, "loop detector: %d sub-maps, points per sub-map min %d mean %.1f max %d\n", nf, pmin, (double)psum / nf, pmax);
+                if (nover) fprintf(stderr, "loop detector: warning: %d sub-maps had more than %d points and were never matched (raise --loop-dims P)\n", nover, loop_dims.max_points);
+                if (km->loop_stopped)
+                    fprintf(stderr, "loop detector: warning: detection stopped after %d key frames (raise --loop-dims K)\n", loop_dims.max_keyframes);
             }
             fprintf(stderr, "back-end: %d key frames, %d loop edges, %d solve(s)\n", (int)km->keyframe_queue.size(), (int)km->loop_edges.size(), km->solves);
         }
