@@ -351,4 +351,4 @@ class HostPreint:
 
 
 from .batch import BatchPreint, BatchSolver, shard_laser  # noqa: E402,F401
-from . import laser, laser_batch, loop, outputs, posegraph  # noqa: E402,F401
+from . import gridmap, laser, laser_batch, loop, outputs, posegraph  # noqa: E402,F401

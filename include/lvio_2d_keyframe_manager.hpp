@@ -8,12 +8,18 @@
 //   ~keyframe_manager                  :370-397             back_end.txt (TUM) of every key frame
 //   laser_loop_detect                  :642-712             opt-in built-in detector (enable_loop_detection -> include/lvio_2d_loop.hpp,
 //                                                           the MI355X descriptor match), fed here because it needs tfs_tracking
+//   show_laser_map                     :483-511             opt-in occupancy-grid map (enable_laser_map -> liw_map.h, the MI355X ray
+//                                                           caster): every laser key frame with a laser_match_ptr gives its scan2
+//                                                           points (uploaded once, when the key frame arrives) and its current p, q
 // A detector may instead be a callback: when key frame `index` arrives it may return an edge (index1 = index, index2 = an older key
 // frame, tf12) — the shape laser_loop_detect returns (:664-665, :702); a callback, when set, takes precedence.  When the built-in
 // detector holds max_keyframes key frames, detection stops (loop_stopped) and the back-end goes on.  Two deliberate differences of
 // this offline form: the back-end runs on the caller's thread (the reference has its own thread, keyframe_manager.cpp:859-881) and
-// is_time_to_solve compares key-frame STAMPS instead of ros::WallTime, so that a replay is deterministic.
+// is_time_to_solve compares key-frame STAMPS instead of ros::WallTime, so that a replay is deterministic.  For the same reason
+// show_laser_map is called after every back-end solve and by the caller at the end of a log, not every 10 s of wall time; when the map
+// store is full (max_submaps / max_points) later key frames are left out of it (map_stopped) and the back-end goes on.
 #pragma once
+#include <cstdio>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -23,7 +29,9 @@
 
 #include "liw_io.h"
 #include "liw_lie.h"
+#include "liw_map.h"
 #include "liw_posegraph.h"
+#include "lvio_2d_laser.hpp"
 #include "lvio_2d_loop.hpp"
 #include "lvio_2d_solver.hpp"
 
@@ -53,6 +61,7 @@ public:
     ~keyframe_manager() {
         if (kp_.output_tum) write_tum((kp_.output_dir + "back_end.txt").c_str());
         loop_.reset();   // the detector is bound to ctx_
+        liw_map_destroy(map_);   // and so is the map
         liw_destroy(ctx_);
     }
     keyframe_manager(const keyframe_manager&) = delete;
@@ -66,6 +75,46 @@ public:
         return true;
     }
 
+    // the occupancy-grid map (liw_map.h) on this manager's ctx; false if the parameters or dims are rejected.  Needs scans that keep
+    // their points (trajectory_params::enable_laser_vis).
+    bool enable_laser_map(const liw_map_params& p, const liw_map_dims& d) {
+        liw_map_destroy(map_);
+        map_ = liw_map_create(ctx_, &p, &d);
+        map_keyframes.clear();
+        map_stopped = false;
+        return map_ != nullptr;
+    }
+
+    // show_laser_map (:483-511): the map of every laser key frame's scan at its current (corrected) pose; the points are on the
+    // device already, only the poses are sent.  Returns the liw_map_render status (also kept in map_status).
+    int show_laser_map() {
+        if (!map_) return map_status = LIW_ESTATE;
+        std::vector<double> poses(map_keyframes.size() * 6);
+        for (size_t k = 0; k < map_keyframes.size(); ++k) {
+            std::memcpy(&poses[k * 6], keyframe_queue[(size_t)map_keyframes[k]]->p, 24);
+            std::memcpy(&poses[k * 6 + 3], keyframe_queue[(size_t)map_keyframes[k]]->q, 24);
+        }
+        map_status = liw_map_render(map_, (int)map_keyframes.size(), poses.data(), &last_map_info);
+        if (map_status >= 0) { ++map_renders; map_poses = poses; }
+        return map_status;
+    }
+
+    // the exact input of the last render: int32 K, then per sub-map float64 pose[6] (p, q), int32 n, float64 points[n][3]
+    bool write_map_input(const char* path) const {
+        FILE* f = fopen(path, "wb");
+        if (!f) return false;
+        const int K = (int)(map_poses.size() / 6);
+        fwrite(&K, sizeof(int), 1, f);
+        for (int k = 0; k < K; ++k) {
+            const std::vector<double>& pts = keyframe_queue[(size_t)map_keyframes[(size_t)k]]->laser_match_ptr->scan2->points;
+            const int n = (int)(pts.size() / 3);
+            fwrite(&map_poses[(size_t)k * 6], sizeof(double), 6, f);
+            fwrite(&n, sizeof(int), 1, f);
+            if (n) fwrite(pts.data(), sizeof(double), (size_t)n * 3, f);
+        }
+        return fclose(f) == 0;
+    }
+
     // add_keyframe (:400-407) + do_add_keyframe (:419-482) in one call: no worker thread in the offline form
     void add_keyframe(const frame_info::ptr& frame_ptr) {
         keyframe_queue.push_back(frame_ptr);
@@ -75,6 +124,13 @@ public:
         double corrected[12];
         liw_lie_mul(modify_delta_tf, tr, corrected);
         liw_lie_log_SE3(corrected, frame_ptr->p, frame_ptr->q);
+        if (map_ && !map_stopped && frame_ptr->type == frame_info::laser && frame_ptr->laser_match_ptr && frame_ptr->laser_match_ptr->scan2) {
+            const std::vector<double>& pts = frame_ptr->laser_match_ptr->scan2->points;
+            const int r = liw_map_add_submap(map_, (int)(pts.size() / 3), pts.data());
+            if (r >= 0) map_keyframes.push_back((int)keyframe_queue.size() - 1);
+            else if (r == LIW_ENOMEM) map_stopped = true;
+            else map_status = r;
+        }
         int loop_status = 0;
         bool detect_now = false;
         if (loop_ && !detector_ && !loop_stopped) {   // the laser map feature of every key frame (:428-437)
@@ -130,6 +186,7 @@ public:
             }
             has_loop_wait_for_solve = false;
             ++solves;
+            if (map_ && last_status == 0) show_laser_map();   // every pose moved: the map is rendered again from all of them
         }
     }
 
@@ -172,6 +229,7 @@ public:
         return true;
     }
 
+    liw_map* laser_map() const { return map_; }
     const laser_loop_detector* laser_loop() const { return loop_.get(); }
     const char* last_error() const { return loop_error_.empty() ? liw_last_error(ctx_) : loop_error_.c_str(); }
 
@@ -186,6 +244,11 @@ public:
     double last_solve_time = -1e300;
     int last_status = 0;
     liw_summary last_summary{};
+    std::vector<int> map_keyframes;    // key-frame index of sub-map k of the map
+    std::vector<double> map_poses;     // [K][6] the poses of the last render
+    liw_map_info last_map_info{};
+    bool map_stopped = false;          // the map store is full: later key frames are not in the map
+    int map_status = 0, map_renders = 0;
 
 private:
     bool is_time_to_solve(double time_now) const { return has_loop_wait_for_solve && time_now - last_solve_time > kp_.solve_period; }
@@ -194,6 +257,7 @@ private:
     liw_ctx* ctx_;
     loop_detector detector_;
     std::unique_ptr<laser_loop_detector> loop_;
+    liw_map* map_ = nullptr;
     std::string loop_error_;
     double zero3_[3] = {0, 0, 0};
 };

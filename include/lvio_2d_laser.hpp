@@ -20,6 +20,7 @@ struct scan {
     std::vector<line> lines;                 // p1, p2 (abc / len: lines_abc_len)
     std::vector<double> lines_abc_len;       // [lines.size()][4]
     std::vector<double> concers;             // [k][3]
+    std::vector<double> points;              // [n][3] laser frame; kept only when laser_manager::keep_points is on (laser_manager.cpp:358-359)
     liw_scan* handle = nullptr;
     ~scan() { liw_scan_destroy(handle); }
     scan() = default;
@@ -52,6 +53,7 @@ public:
         auto s = std::make_shared<scan>();
         s->time = time;
         s->handle = liw_scan_spawn(&prm_, points, n, time);
+        if (keep_points && n > 0) s->points.assign(points, points + (size_t)n * 3);
         s->refresh();
         return s;
     }
@@ -68,6 +70,8 @@ public:
     int num_keyframes() const { return liw_laser_manager_num_keyframes(h_); }
     // get_keyframs()[i]->current_p / current_q = ... (trajectory.cpp:452-461)
     void set_keyframe_pose(int i, const double* p, const double* q) { liw_laser_manager_set_keyframe_pose(h_, i, p, q); }
+
+    bool keep_points = false;   // the reference's enable_laser_vis: spawn_scan keeps the scan's points for the map (default off)
 
 private:
     static laser_match::ptr take(liw_laser_match* m, const scan::ptr& scan2) {

@@ -52,6 +52,7 @@ struct trajectory_params {   // the trajectory part of param::manager (config/of
     // their information is counted in the prior AND as factors.  Parity claims are made for 1 only; the keep-N tests compare product and
     // oracle twin on the SAME policy (teacher-forced solves), not against the reference.
     int keep_window_size = 1;
+    bool enable_laser_vis = false;   // scans keep their points (laser_manager::keep_points) for keyframe_manager::show_laser_map
     bool output_tum = false;
     std::string output_dir;
 };
@@ -66,6 +67,7 @@ public:
         : prm_(prm), tprm_(tprm), imu_preintegraption_(prm), wheel_odom_preintegration_(prm), laser_manger_(lprm), opt_solver(prm) {
         liw_lie_from_matrix16(prm.T_imu_to_wheel, prm.normalize_extrinsics, T_imu_to_wheel);
         liw_lie_from_matrix16(prm.T_imu_to_laser, prm.normalize_extrinsics, T_imu_to_laser);
+        laser_manger_.keep_points = tprm.enable_laser_vis;
         recorder = liw_record_create();
         init_current_status();
         wheel_odom_inited = imu_inited = false;

@@ -1,6 +1,6 @@
 // replay_log — offline replay of a flat sensor log (format: 2dliw-slam_amd/replay.py) through lvio_2d::trajectory
 // (include/lvio_2d_trajectory.hpp): the reference's front-end driver with the MI355X estimator underneath, without ROS.
-//   usage: replay_log <log.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file>] [--solve-period S] [--pg-iters K]
+//   usage: replay_log <log.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file>] [--solve-period S] [--pg-iters K] [--map STEM]
 //     --keep N         frames kept in the window after a tracking solve (trajectory_params::keep_window_size; 1 = reference)
 //     --loops <file>   enables the back-end (include/lvio_2d_keyframe_manager.hpp -> liw_posegraph_solve) with a loop-edge schedule
 //                      given by hand: int32 count, then per edge int32 trigger key frame, int32 older key frame, float64 tf12[12]
@@ -10,6 +10,12 @@
 //     --loop-dims K P  detector capacity: K key frames, P points per sub-map (default 2048 256).  After K key frames detection
 //                      stops (the back-end goes on with the loops found so far); a sub-map of more than P points is never matched.
 //                      Both are reported on stderr at the end.
+//     --map STEM       enables the occupancy-grid map of the laser key frames (include/liw_map.h, 5 cm as the reference; needs the
+//                      back-end: --loops or --detect-loops): rendered after every back-end solve and at the end of the log, when
+//                      STEM.pgm / STEM.yaml (the pair ROS' map_server reads) and STEM.in are written.  STEM.in is the exact input of
+//                      that last render: int32 K, then per sub-map float64 pose[6] (p, q of the key frame), int32 n, float64 points[n][3]
+//     --map-dims K P C map capacity: K sub-maps, P points in all, C cells (default 4096 4194304 16777216); key frames beyond K / P
+//                      are left out of the map (reported on stderr)
 // writes <output_dir>fornt_end.txt (TUM trajectory, the reference's file name), <output_dir>traj.md (record tables),
 // <output_dir>result.bin: int32 status, frames, tracked, initializations, keyframes, solver_status; float64 time, state[15], and with
 // --loops <output_dir>back_end.txt (TUM of the key frames, keyframe_manager.cpp:370-397) + <output_dir>backend.bin: int32 key frames,
@@ -36,7 +42,7 @@ static const double OFFICE_T_IMU_TO_LASER[16] = {0.0019070, -0.9999900, 0.004043
 int main(int argc, char** argv) {
     bool backend_only = false;
     if (argc > 1 && std::string(argv[1]) == "--backend-only") { backend_only = true; --argc; ++argv; }
-    if (argc < 3) { fprintf(stderr, "usage: replay_log [--backend-only] <log.bin | keyframes.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file> | --detect-loops]\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: replay_log [--backend-only] <log.bin | keyframes.bin> <output_dir/> [look_ahead] [--keep N] [--loops <file> | --detect-loops] [--map STEM]\n"); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
     liw_params prm{};
@@ -57,6 +63,8 @@ int main(int argc, char** argv) {
     const char* loops_path = nullptr;
     bool detect_loops = false;
     liw_loop_dims loop_dims{2048, 256};
+    const char* map_stem = nullptr;
+    liw_map_dims map_dims{4096, 1ll << 22, 1ll << 24};
     lvio_2d::keyframe_manager_params kp;
     for (int k = 0; k < 3; ++k) { kp.pg.loop_sigma_p[k] = 0.1; kp.pg.loop_sigma_q[k] = 0.01; }   // config/office.yaml:106-115
     kp.pg.loop_edge_k = 10.0; kp.pg.use_ground_p_factor = 1; kp.pg.use_ground_q_factor = 1;
@@ -67,6 +75,8 @@ int main(int argc, char** argv) {
         else if (s == "--loops" && a + 1 < argc) loops_path = argv[++a];
         else if (s == "--detect-loops") detect_loops = true;
         else if (s == "--loop-dims" && a + 2 < argc) { loop_dims.max_keyframes = atoi(argv[a + 1]); loop_dims.max_points = atoi(argv[a + 2]); a += 2; }
+        else if (s == "--map" && a + 1 < argc) map_stem = argv[++a];
+        else if (s == "--map-dims" && a + 3 < argc) { map_dims.max_submaps = atoi(argv[a + 1]); map_dims.max_points = atoll(argv[a + 2]); map_dims.max_cells = atoll(argv[a + 3]); a += 3; }
         else if (s == "--solve-period" && a + 1 < argc) kp.solve_period = atof(argv[++a]);
         else if (s == "--pg-iters" && a + 1 < argc) kp.max_iterations = atoi(argv[++a]);
         else if (a == 3 && s[0] != '-') look_ahead = atoi(argv[a]);
@@ -74,6 +84,9 @@ int main(int argc, char** argv) {
     }
     if (detect_loops && loops_path) { fprintf(stderr, "--detect-loops and --loops exclude each other\n"); return 2; }
     if (detect_loops && backend_only) { fprintf(stderr, "--backend-only key frames carry no corners: use --loops, not --detect-loops\n"); return 2; }
+    if (map_stem && !detect_loops && !loops_path) { fprintf(stderr, "--map needs the back-end: --loops or --detect-loops\n"); return 2; }
+    if (map_stem && backend_only) { fprintf(stderr, "--backend-only key frames carry no scans: no --map\n"); return 2; }
+    tp.enable_laser_vis = map_stem != nullptr;
     struct loop_rec { int trigger, older; double tf12[12]; };
     std::vector<loop_rec> schedule;
     if (loops_path) {
@@ -104,6 +117,7 @@ int main(int argc, char** argv) {
             if (!km->enable_loop_detection(lvio_2d::office_loop_params(), loop_dims)) { fprintf(stderr, "bad --loop-dims\n"); return 2; }
             traj.set_other_frame_sink([&](const std::deque<lvio_2d::frame_info::ptr>& fi) { km->update_other_frame(fi, backend_pose, backend_pose + 3); });
         }
+        if (map_stem && !km->enable_laser_map(liw_map_params{0.05}, map_dims)) { fprintf(stderr, "bad --map-dims\n"); return 2; }
         traj.set_keyframe_sink([&](const lvio_2d::frame_info::ptr& f) { ++keyframes; if (km) km->add_keyframe(f); });
         lvio_2d::dispatch_queue dq(&traj, look_ahead);
         int type;
@@ -164,6 +178,18 @@ int main(int argc, char** argv) {
             fwrite(&tm, sizeof(double), 1, o);
             fwrite(traj.p(), sizeof(double), 3, o); fwrite(traj.q(), sizeof(double), 3, o); fwrite(traj.v(), sizeof(double), 3, o); fwrite(traj.bs(), sizeof(double), 6, o);
             fclose(o);
+        }
+        if (km && map_stem && !rc) {   // the final map: every key frame at its last corrected pose
+            const int r = km->show_laser_map();
+            if (r < 0) { rc = -r; fprintf(stderr, "map: %s\n", liw_map_last_error(km->laser_map())); }
+            else {
+                const int w = liw_map_write_pgm(km->laser_map(), map_stem, nullptr);
+                if (w < 0 || !km->write_map_input((std::string(map_stem) + ".in").c_str())) { rc = 2; fprintf(stderr, "map: cannot write %s.*\n", map_stem); }
+                const liw_map_info& mi = km->last_map_info;
+                fprintf(stderr, "map: %d sub-maps, %lld rays, %lld samples, %d x %d cells at %.3f m (%lld free, %lld hit once, %lld hit more), %d render(s)\n",
+                        (int)km->map_keyframes.size(), mi.rays, mi.samples, mi.width, mi.height, mi.resolution, mi.free_cells, mi.hit_once, mi.hit_more, km->map_renders);
+                if (km->map_stopped) fprintf(stderr, "map: warning: the map store was full, later key frames are not in the map (raise --map-dims)\n");
+            }
         }
         if (km) {
             FILE* b = fopen((std::string(argv[2]) + "backend.bin").c_str(), "wb");
