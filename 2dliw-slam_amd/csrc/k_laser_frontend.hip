@@ -1,14 +1,25 @@
 // k_laser_frontend.hip — the batched laser front-end on the MI355X (C ABI include/liw_laser_batch.h): liw_laser.cpp's
 // tracking-time work for B robots at once, its output landing in the device arrays liw_batch takes.
 //
-// Mapping: one lane per (robot, scan).  Every step of the host front-end is a serial chain over one scan (the 1 cm filter
-// compares against the previously KEPT point, the corner maxima skip `step` after each maximum, the segment merge carries
-// `last`, a line's cells are de-duplicated against its earlier cells, the mean match distance is summed in match order),
-// so a lane walks its scan in the host's order and rounds as the host does; the batch is the parallelism.
+// Mapping: one lane per (robot, scan), except spawn.  Every step of the host front-end is a serial chain over one scan (the 1 cm
+// filter compares against the previously KEPT point, the segment merge carries `last`, a line's cells are de-duplicated against
+// its earlier cells, the mean match distance is summed in match order), so a lane walks its scan in the host's order and rounds
+// as the host does; the batch is the parallelism.
 //   k_lfe_ranges   ranges -> points (+ times): the (cosf, sinf) table of the geometry comes from the host libm (ctx)
 //   k_lfe_deskew   one lane per point: make_tf(dt * twist) * p
-//   k_lfe_spawn    continuous runs -> corner response -> strict local maxima -> merge -> add_line (moment matrix, cyclic
-//                  Jacobi, create_line, gates) -> cell entries; then the slot's entries are heap-sorted by (cell, line)
+//   k_lfe_spawn_wave  spawn_scan, one wavefront per scan, points and intermediates in LDS (layout at wave_lds): runs, corner
+//                  response and the maxima's window test a lane per point; the skip after a maximum one lane over the maxima
+//                  bits; the merge 64 tests at a time from the standing `last`; add_line a lane per candidate segment for the
+//                  sums the host makes in index order (moment matrix, cyclic Jacobi, create_line), a lane per point for max_dis
+//                  and the cells; ids by ballot prefix; the (cell, line) entries through a hash set in the dead point array,
+//                  compacted and bitonic-sorted in LDS; scan::concers from the sorted entries.  Same store bytes as k_lfe_spawn
+//                  for every valid slot (tests/test_gpu_laser_spawn_wave.py); an overflowed slot is left empty and invalid.
+//                  105 VGPRs, no scratch, 39 840 B of LDS at 1 080 points / 256 lines: four work-groups per CU (one wave per
+//                  SIMD; the fp64 points alone are 25.9 KB, so LDS, not registers, sets the occupancy).
+//   k_lfe_spawn    the lane-per-scan spawn (continuous runs -> corner response -> strict local maxima -> merge -> add_line ->
+//                  cell entries, heap-sorted): the checker behind LIW_LFE_SPAWN=lane, and the path of dimensions whose LDS
+//                  need exceeds a work-group's 64 KiB.  No corners.
+//   k_lfe_corners_world  the corners of a tracked scan into the world frame, appended per robot
 //   k_lfe_match    per line of s2 in scan::lines order: candidates of the (2kk+3)^2 cells by binary search of the sorted
 //                  entries (dr, dc, push order), strict-< argmin of the angle, 10 degree gate; two passes (mean, then keep)
 //   k_lfe_add_scan laser_manager::add_scan: motion filter, fresh sub-maps, add_segment rasterisation, the swap
@@ -16,13 +27,15 @@
 // The line_map of a slot is a list of 64-bit entries (cell key << 32 | line index) kept sorted: within a cell the host
 // pushes line ids in increasing order (ids only grow and a cell never takes the same id twice in a row), so sorting by
 // (cell, line index) reproduces the host's push order exactly.
-// No floating-point atomics, no inter-lane communication in the per-robot kernels: runs are bitwise reproducible.
+// No floating-point atomics on sums (the one LDS atomic is a maximum of non-negative doubles, and the hash set's content does
+// not depend on the insertion order): runs are bitwise reproducible.
 #pragma clang fp contract(off)   // the x86-64 host build of liw_laser.cpp does not contract; hipcc contracts device code by default
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -371,6 +384,407 @@ __global__ void __launch_bounds__(kBlock) k_lfe_spawn(void* store, Lay L, DP P, 
     if (st) m->status |= st;
 }
 
+// ------------------------------------------------------------------------------------------ wave-per-scan spawn (+ corners)
+// One work-group of one wave per (robot, scan); everything a step reads more than once lives in LDS (offsets in bytes):
+//   X     [max_points][3] doubles   the scan's points; after the last add_line the same bytes are the hash set / sort buffer of the entries
+//   brk   bit i: a continuous run starts at point i          mx   bit i: point i is a strict local maximum of the response
+//   misc  counters, then per candidate of a chunk max_dis (bit pattern of a non-negative double, LDS atomic max) and `has a cell`
+//   lbase / lcnt [max_lines]       where line id keeps its cells in `cell`, and how many
+//   U     resp [max_points] doubles, until the maxima are known; afterwards
+//         cell [max_points * 3 / 2 + 2] (first the `ends` lists of the runs; then a candidate i1 .. i2 with index j owns
+//         cell[i1 + j ..]: ranges of consecutive candidates share at most one point) and cand [max_points / 2 + 1] (i1, i2) of
+//         the candidate segments with i2 - i1 >= 2
+struct WaveLds { unsigned x, brk, mx, misc, lbase, lcnt, u, cand; int tcap; size_t total; };
+__host__ __device__ inline size_t up8(size_t x) { return (x + 7) / 8 * 8; }
+inline WaveLds wave_lds(const Lay& L) {
+    const size_t MP = (size_t)L.max_points, W = (MP + 63) / 64, ML = (size_t)L.max_lines;
+    WaveLds O;
+    size_t o = 0;
+    O.x = (unsigned)o; o += 24 * MP;
+    O.brk = (unsigned)o; o += 8 * W;
+    O.mx = (unsigned)o; o += 8 * W;
+    O.misc = (unsigned)o; o += 16 + 12 * kBlock;
+    O.lbase = (unsigned)o; o += up8(4 * ML);
+    O.lcnt = (unsigned)o; o += up8(4 * ML);
+    O.u = (unsigned)o;
+    const size_t cells = up8(4 * (MP + MP / 2 + 2)), cands = 8 * (MP / 2 + 1);
+    O.cand = (unsigned)(o + cells);
+    const size_t u = cells + cands > 8 * MP ? cells + cands : 8 * MP;
+    O.total = o + u;
+    O.tcap = 1;   // slots of the hash set in X's bytes: the largest power of two <= 3 * max_points, more than the 1.5 * max_points
+    while ((size_t)O.tcap * 2 <= 3 * MP) O.tcap *= 2;   // (cell, line) pairs the candidates' points can make
+    return O;
+}
+constexpr size_t kWaveLdsMax = 64 * 1024;   // a work-group's limit (two of them still share a CU); larger dimensions go to the lane kernel
+
+// largest run start <= i (0 when there is none), and the last point of the run that holds i
+__device__ inline int run_start(const u64* brk, int i) {
+    int w = i >> 6;
+    u64 m = brk[w] & (~0ull >> (63 - (i & 63)));
+    while (!m) { if (--w < 0) return 0; m = brk[w]; }
+    return (w << 6) + 63 - __clzll((long long)m);
+}
+// first set bit at an index >= j in words [0, W), or -1
+__device__ inline int next_bit(const u64* a, int W, int j) {
+    int w = j >> 6;
+    if (w >= W) return -1;
+    u64 m = a[w] & (~0ull << (j & 63));
+    while (!m) { if (++w >= W) return -1; m = a[w]; }
+    return (w << 6) + __ffsll((unsigned long long)m) - 1;
+}
+__device__ inline int run_end(const u64* brk, int W, int N, int i) { const int j = next_bit(brk, W, i + 1); return j < 0 ? N - 1 : j - 1; }
+// exclusive prefix sum over the wave (all 64 lanes must call it)
+__device__ inline int wave_excl(int v, int lane, int& total) {
+    int x = v;
+#pragma unroll
+    for (int d = 1; d < kBlock; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d) x += y; }
+    total = __shfl(x, kBlock - 1);
+    return x - v;
+}
+// ascending sort of n unique keys by one wave: bitonic network whose exchanges all put the smaller key at the lower index, so
+// the keys behind n behave as +inf without being stored
+__device__ void wave_sort(u64* a, int n, int lane) {
+    auto pass = [&](int mask) {
+        for (int i = lane; i < n; i += kBlock) {
+            const int l = i ^ mask;
+            if (l > i && l < n) { const u64 p = a[i], q = a[l]; if (q < p) { a[i] = q; a[l] = p; } }
+        }
+        __syncthreads();
+    };
+    for (int k = 2; (k >> 1) < n; k <<= 1) {
+        pass(k - 1);
+        for (int j = k >> 2; j > 0; j >>= 1) pass(j);
+    }
+}
+// calc_angle_and_intersection + the neighbourhood test of scan::add_line for lines l0, l1 ([p1 p2 abc len]) meeting in cell (r, c)
+__device__ inline bool corner_of(const DP& P, const double* l0, const double* l1, int r, int c, double& ix, double& iy) {
+    if (!(l0[9] > 0.1 && l1[9] > 0.1)) return false;
+    const double angle = acos(vdot(vunit_div(vsub(ld3(l0), ld3(l0 + 3))), vunit_div(vsub(ld3(l1), ld3(l1 + 3)))));
+    if (!(angle < 150.0 / 180.0 * kPi && angle > 30.0 / 180.0 * kPi)) return false;
+    const double det = l0[6] * l1[7] - l0[7] * l1[6];
+    ix = (-l0[8] * l1[7] + l1[8] * l0[7]) / det;
+    iy = (-l0[6] * l1[8] + l1[6] * l0[8]) / det;
+    int cc, cr;
+    xy_to_index(P, ix, iy, cc, cr);
+    const int dr = cr - r, dc = cc - c;
+    return dr >= -1 && dr <= 1 && dc >= -1 && dc <= 1;
+}
+
+__global__ void __launch_bounds__(kBlock) k_lfe_spawn_wave(void* store, Lay L, DP P, WaveLds O, int slot, const double* pts, const int* n_pts,
+                                                          const double* times, int max_corners, double* corners, int* n_corners) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= L.B) return;
+    double* X = (double*)(lds + O.x);
+    u64* brk = (u64*)(lds + O.brk);
+    u64* mx = (u64*)(lds + O.mx);
+    int* misc = (int*)(lds + O.misc);
+    int* lbase = (int*)(lds + O.lbase);
+    int* lcnt = (int*)(lds + O.lcnt);
+    double* resp = (double*)(lds + O.u);
+    unsigned* cell = (unsigned*)(lds + O.u);
+    int2* cand = (int2*)(lds + O.cand);
+    Slot sl = slot_at(store, L, b, slot);
+    Mgr* m = (Mgr*)robot_ptr(store, L, b);
+    const double time = times ? times[b] : 0.0;
+    const int N = n_pts[b];
+    auto invalid = [&](unsigned st) {
+        if (lane == 0) {
+            slot_clear(sl, time);
+            sl.h->status = (int)st;
+            m->status |= st;
+            if (n_corners) n_corners[b] = 0;
+        }
+    };
+    if (N < 0 || N > L.max_points) { invalid(LIW_LFE_ST_POINTS); return; }
+    const int W = (N + 63) >> 6;
+    {
+        const double* G = pts + (size_t)b * L.max_points * 3;
+        for (int k = lane; k < 3 * N; k += kBlock) X[k] = G[k];
+    }
+    __syncthreads();
+    auto Pt = [&](int i) { return ld3(X + 3 * i); };
+    // continuous runs (:361-374): a lane per point, the run boundaries from the ballot
+    for (int c = 0; c < W; ++c) {
+        const int i = (c << 6) + lane;
+        const bool bk = i >= 1 && i < N && !(vnorm(vsub(Pt(i - 1), Pt(i))) <= P.cont_thr);
+        const u64 mask = __ballot(bk);
+        if (lane == 0) brk[c] = mask;
+    }
+    __syncthreads();
+    // corner response, once per interior point of a run
+    for (int c = 0; c < W; ++c) {
+        const int i = (c << 6) + lane;
+        if (i < N) {
+            const int s = run_start(brk, i), e = run_end(brk, W, N, i);
+            double r = -1.0;
+            if (i >= s + 1 && i <= e - 1) r = clac_cos(Pt(i), Pt(i - kStep > s ? i - kStep : s), Pt(i + kStep < e ? i + kStep : e));
+            resp[i] = r;
+        }
+    }
+    __syncthreads();
+    // the window test of the strict local maxima (it does not depend on the skip after a maximum)
+    for (int c = 0; c < W; ++c) {
+        const int i = (c << 6) + lane;
+        bool is_max = false;
+        if (i < N) {
+            const int s = run_start(brk, i), e = run_end(brk, W, N, i);
+            if (i >= s + 1 && i <= e - 1) {
+                const double ri = resp[i];
+                is_max = true;
+                const int bj = i - kStep > s + 1 ? i - kStep : s + 1, ej = i + kStep < e - 1 ? i + kStep : e - 1;
+                for (int j = bj; j <= ej; ++j)
+                    if (j != i && resp[j] >= ri) { is_max = false; break; }
+            }
+        }
+        const u64 mask = __ballot(is_max);
+        if (lane == 0) mx[c] = mask;
+    }
+    __syncthreads();
+    // the skip after a maximum is a serial walk over the maxima bits: lane 0 lists, per run of at least three points, its
+    // `ends` as [m, s, maxima .., e] in the cell region
+    int* ends = (int*)cell;
+    if (lane == 0) {
+        int k = 0;
+        for (int s = 0; s < N;) {
+            const int e = run_end(brk, W, N, s);
+            if (e - s >= 2) {
+                const int hdr = k++;
+                ends[k++] = s;
+                for (int gi = s + 1; gi <= e - 1;) {
+                    const int i = next_bit(mx, W, gi);
+                    if (i < 0 || i > e - 1) break;
+                    ends[k++] = i;
+                    gi = i + kStep + 1;
+                }
+                ends[k++] = e;
+                ends[hdr] = k - hdr - 1;
+            }
+            s = e + 1;
+        }
+        misc[1] = k;
+    }
+    __syncthreads();
+    // the merge over `ends` (:294-302): while `last` stands, the tests of the following ends are independent, so the wave makes
+    // 64 of them at once and the first that passes is the host's next split
+    int nc_ = 0;
+    {
+        const int total = misc[1];
+        auto emit = [&](int i1, int i2) { if (i2 - i1 >= 2) { if (lane == 0) cand[nc_] = make_int2(i1, i2); ++nc_; } };
+        for (int k = 0; k < total;) {
+            const int m = ends[k];
+            const int* E = ends + k + 1;
+            int last = 0;
+            for (int i = 1; i + 1 < m;) {
+                const int ii = i + lane;
+                bool split = false;
+                if (ii + 1 < m) {
+                    const double angle = acos(clac_cos(Pt(E[ii]), Pt(E[last]), Pt(E[ii + 1])));
+                    split = fabs(angle) < P.tol;
+                }
+                const u64 mask = __ballot(split);
+                if (mask) {
+                    const int hit = i + __ffsll((unsigned long long)mask) - 1;
+                    emit(E[last], E[hit]);
+                    last = hit;
+                    i = hit + 1;
+                } else {
+                    i += kBlock;
+                }
+            }
+            emit(E[last], E[m - 1]);
+            k += m + 1;
+        }
+    }
+    __syncthreads();
+    const int nc = nc_;
+    // add_line: a lane per candidate segment for what the host sums in index order (the six moment sums) and for the line's
+    // cell list; the distances for max_dis (a maximum: any order gives the host's value, a NaN distance never wins on the host
+    // either) and the points' cells are a lane per point.  Ids and entry offsets by prefix over the wave.
+    u64* maxb = (u64*)(misc + 4);
+    int* anyb = misc + 4 + 2 * kBlock;
+    int id_base = 0;
+    unsigned st = 0;
+    for (int c0 = 0; c0 < nc; c0 += kBlock) {
+        const int j = c0 + lane, cend = c0 + kBlock < nc ? c0 + kBlock : nc;
+        bool accepted = false;
+        int i1 = 0, i2 = 0;
+        Vec p1(0, 0, 0), p2(0, 0, 0), abc(0, 0, 0), a(0, 0, 0), bb(0, 0, 0);
+        double len = 0;
+        if (j < nc) {
+            i1 = cand[j].x; i2 = cand[j].y;
+            double M[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+            for (int i = i1; i <= i2; ++i) {
+                const double x = X[i * 3], y = X[i * 3 + 1];
+                M[0][0] += x * x; M[0][1] += x * y; M[0][2] += x; M[1][1] += y * y; M[1][2] += y; M[2][2] += 1.0;
+            }
+            M[1][0] = M[0][1]; M[2][0] = M[0][2]; M[2][1] = M[1][2];
+            abc = smallest_eigvec3(M);
+            if (fabs(abc.y) < 0.5) {
+                a.y = 0; a.x = -abc.z / abc.x; bb.y = 1; bb.x = (-abc.z - abc.y) / abc.x;
+            } else {
+                a.x = 0; bb.x = 1; a.y = -abc.z / abc.y; bb.y = (-abc.z - abc.x) / abc.y;
+            }
+            p1 = project_to_line(Pt(i1), a, bb);
+            p2 = project_to_line(Pt(i2), a, bb);
+            len = vnorm(vsub(p1, p2));
+        }
+        maxb[lane] = 0;
+        anyb[lane] = 0;
+        __syncthreads();
+        // a lane per point of the chunk's candidates; a point that ends one candidate and starts the next serves both
+        const int lo = cand[c0].x, hi = cand[cend - 1].y;
+        for (int i0 = lo; i0 <= hi; i0 += kBlock) {
+            const bool in = i0 + lane <= hi;
+            const int ii = in ? i0 + lane : hi;
+            int jl = c0, jh = cend - 1;       // the last candidate of the chunk that starts at or before ii
+            while (jl < jh) { const int mid = (jl + jh + 1) >> 1; if (cand[mid].x <= ii) jl = mid; else jh = mid - 1; }
+            int c = 0, r = 0;
+            xy_to_index(P, X[3 * ii], X[3 * ii + 1], c, r);
+            const unsigned key = valid(P, r, c) ? (unsigned)(r * P.w + c) : ~0u;
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass) {
+                const int jj = jl - pass;
+                const bool ok = in && (pass == 0 ? ii <= cand[jl].y : (jl > c0 && cand[jl - 1].y == ii));
+                const int src = ok ? jj - c0 : 0;
+                Vec la(__shfl(a.x, src), __shfl(a.y, src), 0.0), lb(__shfl(bb.x, src), __shfl(bb.y, src), 0.0);
+                if (ok) {
+                    const double d = dis_from_line(Pt(ii), la, lb);
+                    if (d == d) atomicMax(&maxb[src], (u64)__double_as_longlong(d));
+                    cell[ii + jj] = key;
+                    if (key != ~0u) anyb[src] = 1;
+                }
+            }
+        }
+        __syncthreads();
+        if (j < nc) {
+            const double max_dis = __longlong_as_double((long long)maxb[lane]);
+            accepted = !(max_dis > P.max_dis) && !(len < P.min_len);
+        }
+        const bool reg = accepted && anyb[lane] != 0;   // registers at least one valid cell: the line takes an id
+        const u64 rm = __ballot(reg);
+        const int id = id_base + __popcll(rm & ((1ull << lane) - 1));
+        if (__ballot(accepted && id >= L.max_lines)) st |= LIW_LFE_ST_LINES;
+        if (reg && id < L.max_lines) {
+            double* o = sl.lines + 10 * (size_t)id;
+            o[0] = p1.x; o[1] = p1.y; o[2] = p1.z; o[3] = p2.x; o[4] = p2.y; o[5] = p2.z; o[6] = abc.x; o[7] = abc.y; o[8] = abc.z; o[9] = len;
+            lbase[id] = i1 + j;
+            lcnt[id] = i2 - i1 + 1;
+        }
+        id_base += __popcll(rm);
+        __syncthreads();
+    }
+    if (st) { invalid(st); return; }
+    const int nl = id_base;
+    // The line_map entries are the distinct (cell, line) pairs.  The points are dead: their bytes become a hash set the wave fills
+    // a line at a time (lanes over the line's points), which is then compacted and sorted in place.
+    u64* S = (u64*)X;
+    const unsigned tmask = (unsigned)O.tcap - 1;
+    for (int k = lane; k < O.tcap; k += kBlock) S[k] = ~0ull;
+    __syncthreads();
+    for (int id = 0; id < nl; ++id) {
+        const int base = lbase[id], n = lcnt[id];
+        for (int t = lane; t < n; t += kBlock) {
+            const unsigned key = cell[base + t];
+            if (key == ~0u) continue;
+            const u64 item = ((u64)key << 32) | (unsigned)id;
+            unsigned h = (unsigned)((item * 0x9E3779B97F4A7C15ull) >> 40) & tmask;
+            for (unsigned probe = 0; probe <= tmask; ++probe) {   // the set is never full: fewer pairs than slots (wave_lds)
+                const u64 old = atomicCAS((unsigned long long*)&S[h], ~0ull, (unsigned long long)item);
+                if (old == ~0ull || old == item) break;
+                h = (h + 1) & tmask;
+            }
+        }
+    }
+    __syncthreads();
+    int ne = 0;
+    for (int k0 = 0; k0 < O.tcap; k0 += kBlock) {
+        const u64 v = k0 + lane < O.tcap ? S[k0 + lane] : ~0ull;
+        const bool has = v != ~0ull;
+        const u64 mask = __ballot(has);
+        __syncthreads();
+        if (has) S[ne + __popcll(mask & ((1ull << lane) - 1))] = v;
+        ne += __popcll(mask);
+        __syncthreads();
+    }
+    if (ne > L.max_entries) { invalid(LIW_LFE_ST_CELLS); return; }
+    wave_sort(S, ne, lane);
+    for (int k = lane; k < ne; k += kBlock) sl.ent[k] = S[k];
+    if (lane == 0) { sl.h->status = 0; sl.h->n_lines = nl; sl.h->n_entries = ne; sl.h->time = time; }
+    if (!corners) return;
+    // scan::concers: the entry that is second in its cell belongs to the line l1 that made the host's test there, the entry before
+    // it to l0.  Push order = (l1, first point of l1 in the cell): the hits are listed behind the entries as (l1, point, l0) (16
+    // bits each for point and l0: max_points and max_lines are far below that where the LDS fits), sorted and written.
+    double* C = corners + (size_t)b * max_corners * 3;
+    u64* R = S + ne;
+    int nr = 0;
+    for (int p0 = 0; p0 < ne; p0 += kBlock) {
+        const int p = p0 + lane;
+        u64 rec = 0;
+        bool hit = false;
+        if (p >= 1 && p < ne) {
+            const u64 e1 = S[p], e0 = S[p - 1];
+            const unsigned key = (unsigned)(e1 >> 32);
+            if ((unsigned)(e0 >> 32) == key && (p < 2 || (unsigned)(S[p - 2] >> 32) != key)) {
+                const unsigned l1 = (unsigned)(e1 & 0xffffffffull), l0 = (unsigned)(e0 & 0xffffffffull);
+                double ix, iy;
+                if (corner_of(P, sl.lines + 10 * (size_t)l0, sl.lines + 10 * (size_t)l1, (int)(key / (unsigned)P.w), (int)(key % (unsigned)P.w), ix, iy)) {
+                    const int base = lbase[l1], n = lcnt[l1];
+                    int t = 0;
+                    while (t < n - 1 && cell[base + t] != key) ++t;
+                    rec = ((u64)l1 << 32) | ((u64)(unsigned)t << 16) | l0;
+                    hit = true;
+                }
+            }
+        }
+        const u64 mask = __ballot(hit);
+        if (hit) R[nr + __popcll(mask & ((1ull << lane) - 1))] = rec;
+        nr += __popcll(mask);
+    }
+    __syncthreads();
+    wave_sort(R, nr, lane);
+    for (int q = lane; q < nr && q < max_corners; q += kBlock) {
+        const u64 rec = R[q];
+        const double* l0 = sl.lines + 10 * (size_t)(rec & 0xffffull);
+        const double* l1 = sl.lines + 10 * (size_t)(rec >> 32);
+        const double det = l0[6] * l1[7] - l0[7] * l1[6];
+        C[3 * q] = (-l0[8] * l1[7] + l1[8] * l0[7]) / det;
+        C[3 * q + 1] = (-l0[6] * l1[8] + l1[6] * l0[8]) / det;
+        C[3 * q + 2] = 0.0;
+    }
+    if (lane == 0) {
+        n_corners[b] = nr > max_corners ? max_corners + 1 : nr;
+        if (nr > max_corners) m->status |= LIW_LFE_ST_CORNERS;
+    }
+}
+
+// lvio_2d::trajectory's accumulation of the corners between key frames: world = make_tf(pose) * T_imu_to_laser * corner
+__global__ void __launch_bounds__(kBlock) k_lfe_corners_world(void* store, Lay L, DP P, int max_corners, const double* corners, const int* n_corners,
+                                                             const double* pose, const unsigned char* mask, const unsigned char* clear, int acc_cap,
+                                                             double* acc, int* n_acc) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B) return;
+    int n = (clear && clear[b]) ? 0 : n_acc[b];
+    if (n < 0) n = 0;
+    if (!mask || mask[b]) {
+        const int nc = n_corners[b];
+        if (n > acc_cap || nc > max_corners || (nc > 0 && n + nc > acc_cap)) {
+            n = acc_cap + 1;
+            if (store) ((Mgr*)robot_ptr(store, L, b))->status |= LIW_LFE_ST_CORNERS;
+        } else if (nc > 0) {
+            const Iso<double> T = liw::mul(tf6(pose + 6 * (size_t)b), til(P));
+            const double* C = corners + (size_t)b * max_corners * 3;
+            double* A = acc + ((size_t)b * acc_cap + n) * 3;
+            for (int k = 0; k < nc; ++k) {
+                const Vec y = apply(T, ld3(C + 3 * k));
+                A[3 * k] = y.x; A[3 * k + 1] = y.y; A[3 * k + 2] = y.z;
+            }
+            n += nc;
+        }
+    }
+    n_acc[b] = n;
+}
+
 // laser_manager::do_match (:244-348) for one robot
 __global__ void __launch_bounds__(kBlock) k_lfe_match(void* store, Lay L, DP P, int slot1, int slot2, const double* pose1, const double* pose2, int kk,
                                                      int cap, int* count, double* recs, int* idx1, int* idx2, double* match_pose) {
@@ -626,6 +1040,26 @@ int host_slot(liw_lfe_ctx* c, const void* store, int robot, int slot, SlotHdr& h
     if (hipMemcpy(&h, rp + slot_off(c->L, phys), sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, LIW_EHIP, "hipMemcpy");
     return 0;
 }
+// liw_lfe_spawn / liw_lfe_spawn_corners: the wave-per-scan kernel unless LIW_LFE_SPAWN=lane (read per call) asks for the
+// lane-per-scan kernel, or the dimensions need more LDS than a work-group has (then the lane kernel; it knows no corners)
+int spawn_launch(liw_lfe_ctx* c, void* store, int slot, const double* pts, const int* n_pts, const double* times, int max_corners, double* corners,
+                 int* n_corners, void* stream) {
+    const char* env = std::getenv("LIW_LFE_SPAWN");
+    bool lane = false;
+    if (env && *env) {
+        if (!std::strcmp(env, "lane")) lane = true;
+        else if (std::strcmp(env, "wave")) return fail(c, LIW_EINVAL, "LIW_LFE_SPAWN must be lane or wave");
+    }
+    const WaveLds O = wave_lds(c->L);
+    if (corners && lane) return fail(c, LIW_EINVAL, "liw_lfe_spawn_corners: the lane kernel (LIW_LFE_SPAWN=lane) does not compute corners");
+    if (corners && O.total > kWaveLdsMax) return fail(c, LIW_EINVAL, "liw_lfe_spawn_corners: max_points / max_lines need more than 64 KiB of LDS");
+    if (lane || O.total > kWaveLdsMax)
+        hipLaunchKernelGGL(k_lfe_spawn, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, slot, pts, n_pts, times);
+    else
+        hipLaunchKernelGGL(k_lfe_spawn_wave, dim3(c->L.B), dim3(kBlock), O.total, (hipStream_t)stream, store, c->L, c->P, O, slot, pts, n_pts, times,
+                           max_corners, corners, n_corners);
+    return launched(c);
+}
 }  // namespace
 
 extern "C" {
@@ -720,7 +1154,23 @@ int liw_lfe_deskew(liw_lfe_ctx* c, double* pts, const double* times, const int* 
 int liw_lfe_spawn(liw_lfe_ctx* c, void* store, int slot, const double* pts, const int* n_pts, const double* times, void* stream) {
     LFE_DEV(c);
     if (!store || !pts || !n_pts || slot < 0 || slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_spawn: bad argument");
-    hipLaunchKernelGGL(k_lfe_spawn, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, slot, pts, n_pts, times);
+    return spawn_launch(c, store, slot, pts, n_pts, times, 0, nullptr, nullptr, stream);
+}
+
+int liw_lfe_spawn_corners(liw_lfe_ctx* c, void* store, int slot, const double* pts, const int* n_pts, const double* times, int max_corners,
+                          double* corners, int* n_corners, void* stream) {
+    LFE_DEV(c);
+    if (!store || !pts || !n_pts || slot < 0 || slot >= c->L.slots || max_corners < 1 || !corners || !n_corners)
+        return fail(c, LIW_EINVAL, "liw_lfe_spawn_corners: bad argument");
+    return spawn_launch(c, store, slot, pts, n_pts, times, max_corners, corners, n_corners, stream);
+}
+
+int liw_lfe_corners_to_world(liw_lfe_ctx* c, void* store, int max_corners, const double* corners, const int* n_corners, const double* pose,
+                             const unsigned char* mask, const unsigned char* clear, int acc_cap, double* acc, int* n_acc, void* stream) {
+    LFE_DEV(c);
+    if (max_corners < 1 || !corners || !n_corners || !pose || acc_cap < 1 || !acc || !n_acc) return fail(c, LIW_EINVAL, "liw_lfe_corners_to_world: bad argument");
+    hipLaunchKernelGGL(k_lfe_corners_world, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, max_corners, corners,
+                       n_corners, pose, mask, clear, acc_cap, acc, n_acc);
     return launched(c);
 }
 

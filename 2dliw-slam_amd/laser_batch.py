@@ -13,9 +13,10 @@ LFE_EXPORTS = [
     "liw_lfe_store_layout", "liw_lfe_create", "liw_lfe_destroy", "liw_lfe_last_error", "liw_lfe_set_geometry", "liw_lfe_store_reset",
     "liw_lfe_ranges_to_points", "liw_lfe_deskew", "liw_lfe_spawn", "liw_lfe_match", "liw_lfe_add_scan", "liw_lfe_pack_track",
     "liw_lfe_status", "liw_lfe_num_lines", "liw_lfe_get_lines", "liw_lfe_cell_lines", "liw_lfe_submap_pose",
+    "liw_lfe_spawn_corners", "liw_lfe_corners_to_world",
 ]
 
-ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID = 1, 2, 4, 8, 16
+ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID, ST_CORNERS = 1, 2, 4, 8, 16, 32
 REF, SPAWNING, ROBOT = -1, -2, -3
 NONE = -61   # LIW_LFE_NONE: a getter's "no such sub-map / outside the grid" (the Python getters turn it into -1 / None)
 
@@ -49,6 +50,8 @@ def _lib():
         L.liw_lfe_ranges_to_points.argtypes = [vp] * 8
         L.liw_lfe_deskew.argtypes = [vp] * 8
         L.liw_lfe_spawn.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+        L.liw_lfe_spawn_corners.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
+        L.liw_lfe_corners_to_world.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
         L.liw_lfe_match.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_add_scan.argtypes = [vp, vp, C.c_int, vp, vp, vp]
         L.liw_lfe_pack_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -191,13 +194,44 @@ class BatchFrontEnd:
         self._chk(self.L.liw_lfe_deskew(self.h, self._p(pts), self._p(tm), self._p(n), self._p(st), self._p(li), self._p(an), self._s()))
         return pts
 
-    def spawn(self, slot, pts, n_pts, times=None):
-        """laser_manager::spawn_scan into `slot`: pts [B, max_points, 3], n_pts [B], times [B] (scan time) or None"""
+    def spawn(self, slot, pts, n_pts, times=None, corners=None, out=None):
+        """laser_manager::spawn_scan into `slot`: pts [B, max_points, 3], n_pts [B], times [B] (scan time) or None.
+        corners=max_corners also computes scan::concers and returns (corners [B, max_corners, 3] in the laser frame, n_corners [B]
+        int32; max_corners + 1 marks an overflow); `out` may be such a pair to write into.  The environment's LIW_LFE_SPAWN=lane
+        selects the lane-per-scan kernel (no corners) for the call."""
         torch = self.torch
         p = self._t(pts, torch.float64, (self.B, self.max_points, 3))
         n = self._t(n_pts, torch.int32, (self.B,))
         t = None if times is None else self._t(times, torch.float64, (self.B,))
-        self._chk(self.L.liw_lfe_spawn(self.h, self._p(self.store), int(slot), self._p(p), self._p(n), self._p(t), self._s()))
+        if corners is None:
+            self._chk(self.L.liw_lfe_spawn(self.h, self._p(self.store), int(slot), self._p(p), self._p(n), self._p(t), self._s()))
+            return None
+        mc = int(corners)
+        if out is None:
+            cz = torch.zeros(self.B, max(mc, 1), 3, dtype=torch.float64, device=self.dev)
+            cn = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        else:
+            cz, cn = out
+            assert cz.is_contiguous() and cn.is_contiguous() and cz.dtype == torch.float64 and cn.dtype == torch.int32
+            assert cz.numel() >= self.B * mc * 3 and cn.numel() >= self.B
+        self._chk(self.L.liw_lfe_spawn_corners(self.h, self._p(self.store), int(slot), self._p(p), self._p(n), self._p(t), mc, self._p(cz), self._p(cn),
+                                               self._s()))
+        return cz, cn
+
+    def corners_to_world(self, corners, n_corners, pose, acc, n_acc, mask=None, clear=None):
+        """lvio_2d::trajectory's corner accumulation: robots with clear[b] restart from n_acc[b] = 0, then the masked robots (all
+        when None) append make_tf(pose[b]) * T_imu_to_laser * corners[b, :n_corners[b]] to acc [B, acc_cap, 3] at n_acc [B] int32,
+        both updated in place.  An append that does not fit leaves n_acc[b] = acc_cap + 1 and sets ST_CORNERS."""
+        torch = self.torch
+        assert corners.is_contiguous() and corners.dtype == torch.float64 and corners.dim() == 3 and corners.shape[0] == self.B
+        assert acc.is_contiguous() and acc.dtype == torch.float64 and acc.dim() == 3 and acc.shape[0] == self.B and acc.shape[2] == 3
+        assert n_acc.is_contiguous() and n_acc.dtype == torch.int32 and n_acc.numel() >= self.B
+        nc = self._t(n_corners, torch.int32, (self.B,))
+        p = self._t(pose, torch.float64, (self.B, 6))
+        m, c = self._mask(mask), self._mask(clear)
+        self._chk(self.L.liw_lfe_corners_to_world(self.h, self._p(self.store), int(corners.shape[1]), self._p(corners), self._p(nc), self._p(p),
+                                                  self._p(m), self._p(c), int(acc.shape[1]), self._p(acc), self._p(n_acc), self._s()))
+        return acc, n_acc
 
     def match(self, slot1, slot2, pose1, pose2, kk=0, cap=256, out=None):
         """laser_manager::do_match per robot -> dict(count [B], recs [B, cap, 12], idx1 / idx2 [B, cap], match_pose [B, 12]);

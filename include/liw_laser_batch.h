@@ -23,9 +23,9 @@
  *
  * Numerics: the front-end kernels are compiled without FMA contraction, like the host.  ranges_to_points, spawn and the
  * end points of the lines are bit-identical to the host; transforms built by make_tf (deskew, match, add_scan) use the device
- * sin / cos and agree to round-off.  Decisions through acos (segment merge, the 10 degree gate, the argmin, and the motion
- * filter's rotation angle, via log_SO3) use the device acos, which may differ from glibc's by an ulp: a decision can only
- * differ from the host where two quantities are within an ulp of each other.
+ * sin / cos and agree to round-off.  Decisions through acos (segment merge, the 10 degree gate, the argmin, the corners'
+ * 30 / 150 degree gate, and the motion filter's rotation angle, via log_SO3) use the device acos, which may differ from glibc's
+ * by an ulp: a decision can only differ from the host where two quantities are within an ulp of each other.
  */
 #ifndef LIW_LASER_BATCH_H
 #define LIW_LASER_BATCH_H
@@ -43,6 +43,7 @@ extern "C" {
 #define LIW_LFE_ST_CELLS 4     /* more cell entries than max_cell_entries */
 #define LIW_LFE_ST_MATCH 8     /* a match had more pairs than `cap` (count = 0 written) */
 #define LIW_LFE_ST_INVALID 16  /* an operation read an invalid slot */
+#define LIW_LFE_ST_CORNERS 32  /* more corners than max_corners / acc_cap (robot word only: the slot stays valid) */
 
 /* slot selectors besides 0 .. slots-1 */
 #define LIW_LFE_REF (-1)       /* the manager's current reference sub-map */
@@ -90,9 +91,32 @@ int liw_lfe_deskew(liw_lfe_ctx* ctx, double* pts, const double* times, const int
                    const double* angular, void* stream);
 
 /* liw_scan_spawn per robot into scan slot `slot` (0 .. slots-1): pts [B][max_points][3], n_pts [B], times [B] (scan time, may be
- * NULL = 0).  n_pts outside 0 .. max_points leaves the slot empty and invalid (LIW_LFE_ST_POINTS).  Corners are not computed
- * (only the back-end reads them). */
+ * NULL = 0).  n_pts outside 0 .. max_points leaves the slot empty and invalid (LIW_LFE_ST_POINTS); so does a scan with more than
+ * max_lines lines or max_cell_entries entries (its n_lines / n_entries read 0).  Corners: liw_lfe_spawn_corners.
+ * One wavefront works on one scan, with the scan's points and the intermediate arrays in LDS: about 34 bytes per point of
+ * max_points and 8 per line of max_lines (39 KiB at 1 080 points and 256 lines); the line_map entries are collected, made unique
+ * and sorted in the bytes of the point array once the points are no longer needed.  Dimensions that need more than the 64 KiB of a
+ * work-group, and every call made while the environment has LIW_LFE_SPAWN=lane (read per call), go to the lane-per-scan kernel
+ * instead, which writes the same bytes for every valid slot (header, lines[0 .. n_lines), entries[0 .. n_entries)). */
 int liw_lfe_spawn(liw_lfe_ctx* ctx, void* store, int slot, const double* pts, const int* n_pts, const double* times, void* stream);
+
+/* liw_lfe_spawn that also writes scan::concers: corners [B][max_corners][3] (laser frame, z = 0) in the host's push order,
+ * duplicates included, and n_corners [B].  A scan with more than max_corners corners gets n_corners = max_corners + 1 (the array
+ * holds the first max_corners) and LIW_LFE_ST_CORNERS in the robot word.  An invalid scan has n_corners = 0.  The slot is written
+ * exactly as by liw_lfe_spawn.  The coordinates are bit-identical to the host's; the 30 / 150 degree gate goes through the device
+ * acos (the caveat above).  Only the wave-per-scan kernel computes corners: LIW_EINVAL with LIW_LFE_SPAWN=lane or when the
+ * dimensions need more than 64 KiB of LDS. */
+int liw_lfe_spawn_corners(liw_lfe_ctx* ctx, void* store, int slot, const double* pts, const int* n_pts, const double* times,
+                          int max_corners, double* corners, int* n_corners, void* stream);
+
+/* What lvio_2d::trajectory does with the corners after a tracking solve.  Robots with clear[b] != 0 (clear may be NULL) start from
+ * n_acc[b] = 0 (a key frame handed its corners over), whatever the mask says.  Then, for the robots with mask[b] != 0 (all when
+ * NULL), make_tf(pose[b]) * T_imu_to_laser * corner is appended to acc [B][acc_cap][3] at n_acc[b], and n_acc[b] advances.  An
+ * append that does not fit writes nothing, leaves n_acc[b] = acc_cap + 1 (which stays until the robot is cleared) and sets
+ * LIW_LFE_ST_CORNERS in the robot word (store may be NULL: no word); n_corners[b] > max_corners does the same. */
+int liw_lfe_corners_to_world(liw_lfe_ctx* ctx, void* store, int max_corners, const double* corners, const int* n_corners,
+                             const double* pose, const unsigned char* mask, const unsigned char* clear, int acc_cap, double* acc,
+                             int* n_acc, void* stream);
 
 /* liw_laser_do_match(slot1, slot2, pose1, pose2, kk) per robot.  slot1 = LIW_LFE_REF matches against the reference sub-map with
  * its stored pose as p1, q1 (pose1 is ignored and may be NULL), as laser_manager::match_with_ref; no reference gives count 0 and

@@ -1,6 +1,8 @@
 """Device time of the batched laser front-end (laser_batch.BatchFrontEnd) per stage, one JSON line.
 
-B robots (default 4 096 and 49 152) with 1 080-ray scans tiled from 64 distinct rooms / poses.  Per B: ranges -> points, spawn,
+B robots (default 4 096 and 49 152) with 1 080-ray scans tiled from 64 distinct rooms / poses.  Per B: ranges -> points, spawn
+(spawn_ms: the default wave-per-scan kernel, with min / max of the repetitions; spawn_lane_ms: the lane-per-scan kernel selected
+by LIW_LFE_SPAWN=lane; spawn_corners_ms: the default kernel also writing the corners, corners_per_robot of them),
 match against the reference sub-map, add_scan (the accumulating call: the reference exists) and pack_track, each timed with
 HIP events on the current stream (median of --reps after one warm-up); scans/s = B / ms.  For comparison the same line carries
 the host front-end (liw.laser through ctypes) per scan over 256 robots: laser_to_points, Scan.spawn, match_with_ref, add_scan.
@@ -55,7 +57,8 @@ def scenes(liw, lp, nd, seed=4242):
     return np.stack(ra), np.stack(rb), np.stack(pa), np.stack(pb)
 
 
-def timed(torch, fn, reps):
+def timed(torch, fn, reps, spread=None):
+    """median of reps (after one warm-up); spread: a list that receives (min, max)"""
     fn()
     torch.cuda.synchronize()
     ts = []
@@ -66,10 +69,25 @@ def timed(torch, fn, reps):
         e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
+    if spread is not None:
+        spread[:] = [float(min(ts)), float(max(ts))]
     return float(np.median(ts))
 
 
-def device_run(liw, torch, lp, B, sc, reps, cap=256):
+def with_env(name, value, fn):
+    """fn() with the environment variable set (the library reads its A/B knobs per call)"""
+    old = os.environ.get(name)
+    os.environ[name] = value
+    try:
+        return fn()
+    finally:
+        if old is None:
+            del os.environ[name]
+        else:
+            os.environ[name] = old
+
+
+def device_run(liw, torch, lp, B, sc, reps, cap=256, max_corners=64):
     ra, rb, pa, pb = sc
     nd = ra.shape[0]
     rob = np.arange(B) % nd
@@ -83,7 +101,16 @@ def device_run(liw, torch, lp, B, sc, reps, cap=256):
     a = fe.ranges_to_points(RA, stamps)
     b = fe.ranges_to_points(RB, stamps)
     out["ranges_to_points_ms"] = timed(torch, lambda: fe.ranges_to_points(RB, stamps, out=b), reps)
-    out["spawn_ms"] = timed(torch, lambda: fe.spawn(1, b[0], b[2]), reps)
+    # spawn: the default (wave-per-scan) kernel, the lane-per-scan kernel behind the knob, and the default kernel with corners
+    sp = []
+    out["spawn_ms"] = timed(torch, lambda: fe.spawn(1, b[0], b[2]), reps, sp)
+    out["spawn_min_ms"], out["spawn_max_ms"] = sp
+    out["spawn_lane_ms"] = with_env("LIW_LFE_SPAWN", "lane", lambda: timed(torch, lambda: fe.spawn(1, b[0], b[2]), reps, sp))
+    out["spawn_lane_min_ms"], out["spawn_lane_max_ms"] = sp
+    cbuf = fe.spawn(1, b[0], b[2], corners=max_corners)
+    out["spawn_corners_ms"] = timed(torch, lambda: fe.spawn(1, b[0], b[2], corners=max_corners, out=cbuf), reps, sp)
+    out["spawn_corners_min_ms"], out["spawn_corners_max_ms"] = sp
+    out["corners_per_robot"] = float(cbuf[1].clamp(max=max_corners).sum().item()) / B
 
     def fresh():   # reset, both scans spawned, the first scan added (the reference sub-map exists)
         fe.reset()
