@@ -1,7 +1,7 @@
 // k_laser_frontend.hip — the batched laser front-end on the MI355X (C ABI include/liw_laser_batch.h): liw_laser.cpp's
 // tracking-time work for B robots at once, its output landing in the device arrays liw_batch takes.
 //
-// Mapping: one lane per (robot, scan), except spawn.  Every step of the host front-end is a serial chain over one scan (the 1 cm
+// Mapping: one lane per (robot, scan), except spawn and the INIT window's match.  Every step of the host front-end is a serial chain over one scan (the 1 cm
 // filter compares against the previously KEPT point, the segment merge carries `last`, a line's cells are de-duplicated against
 // its earlier cells, the mean match distance is summed in match order), so a lane walks its scan in the host's order and rounds
 // as the host does; the batch is the parallelism.
@@ -22,8 +22,13 @@
 //   k_lfe_corners_world  the corners of a tracked scan into the world frame, appended per robot
 //   k_lfe_match    per line of s2 in scan::lines order: candidates of the (2kk+3)^2 cells by binary search of the sorted
 //                  entries (dr, dc, push order), strict-< argmin of the angle, 10 degree gate; two passes (mean, then keep)
+//   k_lfe_match_wave  match_with_front of a whole INIT window, one wavefront per (robot, frame): lanes over the frame's lines, each
+//                  line's search once (best, d in LDS); the mean in line order, the pairs by ballot prefix on a running base:
+//                  bit-identical to k_lfe_match (tests/test_gpu_laser_init.py)
 //   k_lfe_add_scan laser_manager::add_scan: motion filter, fresh sub-maps, add_segment rasterisation, the swap
+//   k_lfe_reset_mgr   clear_all_scan that keeps the scan slots (liw_lfe_rebuild = this + add_scan per frame)
 //   k_lfe_scan / k_lfe_pack   laser_off exclusive scan (one block), then the component-major laser arrays
+//   k_lfe_scan_init / k_lfe_pack_init   the same for INIT windows: blocks of frames 1 .. n-1, a work-group per window
 // The line_map of a slot is a list of 64-bit entries (cell key << 32 | line index) kept sorted: within a cell the host
 // pushes line ids in increasing order (ids only grow and a cell never takes the same id twice in a row), so sorting by
 // (cell, line index) reproduces the host's push order exactly.
@@ -316,6 +321,15 @@ __global__ void __launch_bounds__(kBlock) k_lfe_reset(void* store, Lay L, const 
     char* mz = (char*)m;
     for (size_t k = 0; k < kMgrBytes; ++k) mz[k] = 0;
     for (int k = 0; k < L.slots + 2; ++k) { Slot s = slot_at(store, L, b, k); slot_clear(s, 0.0); }
+}
+
+// clear_all_scan's effect on the manager alone: state, status word and both sub-maps; the scan slots stay (liw_lfe_rebuild)
+__global__ void __launch_bounds__(kBlock) k_lfe_reset_mgr(void* store, Lay L, const unsigned char* mask) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B || (mask && !mask[b])) return;
+    char* mz = robot_ptr(store, L, b);
+    for (size_t k = 0; k < kMgrBytes; ++k) mz[k] = 0;
+    for (int k = L.slots; k < L.slots + 2; ++k) { Slot s = slot_at(store, L, b, k); slot_clear(s, 0.0); }
 }
 
 __global__ void __launch_bounds__(kBlock) k_lfe_ranges(void* store, Lay L, const float* ranges, int n_rays, const float2* cs, float tinc,
@@ -872,6 +886,103 @@ __global__ void __launch_bounds__(kBlock) k_lfe_match(void* store, Lay L, DP P, 
     count[b] = n;
 }
 
+// laser_manager::match_with_front for a whole INIT window: one wavefront per (robot, frame) task, task (b, k) =
+// k_lfe_match(front_slot, first_slot + k) with frame k's pose at poses + b * rs + k * fs.  Lanes stride over the lines of the
+// frame's scan; a lane does for its line exactly the arithmetic of k_lfe_match's `pair`, once (best and d stay in LDS:
+// 12 bytes per line of max_lines).  Two steps stay ordered so that the result equals the lane kernel's bit for bit: the mean
+// distance is summed in increasing line order (every lane walks the d values in LDS, so no broadcast is needed), and the kept
+// pairs are written in increasing line order by a ballot / prefix count per 64-line chunk on a running base, to which the cap
+// test applies.  Outputs are indexed by task: count [B][F], recs [B][F][cap][12], idx1 / idx2 [B][F][cap], match_pose [B][F][12].
+__global__ void __launch_bounds__(kBlock) k_lfe_match_wave(void* store, Lay L, DP P, int front_slot, int first_slot, int F, const double* pose_front,
+                                                          const double* poses, long long rs, long long fs, int kk, int cap, int* count, double* recs,
+                                                          int* idx1, int* idx2, double* match_pose) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    double* dL = (double*)lds;
+    int* bestL = (int*)(lds + 8 * (size_t)L.max_lines);
+    const int lane = threadIdx.x;
+    const size_t task = blockIdx.x;
+    const int b = (int)(task / (unsigned)F), k = (int)(task % (unsigned)F);
+    if (b >= L.B) return;
+    Mgr* m = (Mgr*)robot_ptr(store, L, b);
+    const double* p1 = pose_front + 6 * (size_t)b;
+    const double* p2 = poses + (long long)b * rs + (long long)k * fs;
+    double* mp = match_pose + 12 * task;
+    if (lane < 6) { mp[lane] = p1[lane]; mp[6 + lane] = p2[lane]; }
+    const Slot s1 = slot_at(store, L, b, front_slot), s2 = slot_at(store, L, b, first_slot + k);
+    if (s1.h->status || s2.h->status) {
+        if (lane == 0) { atomicOr(&m->status, LIW_LFE_ST_INVALID); count[task] = 0; }
+        return;
+    }
+    const Iso<double> Ti = til(P);
+    const Iso<double> T12 = liw::mul(liw::inverse(liw::mul(tf6(p1), Ti)), liw::mul(tf6(p2), Ti));
+    const int n2 = n_lines(s2, L), ne = n_entries(s1, L), n1 = n_lines(s1, L);
+    const int a = 1 + kk;
+    for (int i = lane; i < n2; i += kBlock) {
+        const double* l2 = s2.lines + 10 * (size_t)i;
+        const Vec l2p1 = ld3(l2), l2p2 = ld3(l2 + 3);
+        const Vec mid((l2p1.x + l2p2.x) / 2, (l2p1.y + l2p2.y) / 2, (l2p1.z + l2p2.z) / 2);
+        const Vec tm = apply(T12, mid);
+        int c, r;
+        xy_to_index(P, tm.x, tm.y, c, r);
+        int best = -1;
+        bool any = false;
+        double best_angle = kPi * 2;
+        const Vec v2 = vsub(apply(T12, l2p2), apply(T12, l2p1));
+        for (int dr = -a; dr <= a; ++dr)
+            for (int dc = -a; dc <= a; ++dc) {
+                const int rr = r + dr, cc = c + dc;
+                if (!valid(P, rr, cc)) continue;
+                const u64 key = (u64)(unsigned)(rr * P.w + cc);
+                for (int j = lower_bound(s1.ent, ne, key << 32); j < ne && (s1.ent[j] >> 32) == key; ++j) {
+                    const unsigned id = (unsigned)(s1.ent[j] & 0xffffffffull);
+                    if (id >= (unsigned)n1) continue;
+                    any = true;
+                    const double* l1 = s1.lines + 10 * (size_t)id;
+                    const double angle = acos(fabs(vdot(vunit_div(vsub(ld3(l1 + 3), ld3(l1))), vunit_div(v2))));
+                    if (angle < best_angle) { best = (int)id; best_angle = angle; }
+                }
+            }
+        double d = 0.0;
+        if (!any || best_angle / kPi * 180 > 10) {
+            best = -1;
+        } else {
+            const double* l1 = s1.lines + 10 * (size_t)best;
+            const Vec a1 = ld3(l1), a2 = ld3(l1 + 3);
+            d = 0.5 * (dis_from_line(apply(T12, l2p1), a1, a2) + dis_from_line(apply(T12, l2p2), a1, a2));
+        }
+        bestL[i] = best;
+        dL[i] = d;
+    }
+    __syncthreads();
+    double aver = 0;   // in line order, as the lane kernel sums it
+    int nm = 0;
+    for (int i = 0; i < n2; ++i)
+        if (bestL[i] >= 0) { aver += dL[i]; ++nm; }
+    aver /= (double)nm;
+    const double thr = aver * 1.2;
+    int base = 0;
+    for (int c0 = 0; c0 < n2; c0 += kBlock) {
+        const int i = c0 + lane;
+        const int best = i < n2 ? bestL[i] : -1;
+        const bool keep = best >= 0 && dL[i] < thr;
+        const u64 mask = __ballot(keep);
+        const int n = base + __popcll(mask & ((1ull << lane) - 1));
+        if (keep && n < cap) {   // a pair past cap is never written: the match then counts 0
+            const double* l1 = s1.lines + 10 * (size_t)best;
+            const double* l2 = s2.lines + 10 * (size_t)i;
+            double* o = recs + (task * cap + n) * 12;
+            for (int q = 0; q < 6; ++q) { o[q] = l1[q]; o[6 + q] = l2[q]; }
+            if (idx1) idx1[task * cap + n] = best;
+            if (idx2) idx2[task * cap + n] = i;
+        }
+        base += __popcll(mask);
+    }
+    if (lane == 0) {
+        if (base > cap) { atomicOr(&m->status, LIW_LFE_ST_MATCH); base = 0; }
+        count[task] = base;
+    }
+}
+
 // fresh_submap (laser_manager.cpp / liw_laser.cpp): the scan's lines as segments, untransformed
 // src_st: the source scan's status (nonzero: the sub-map is invalid as well)
 __device__ void fresh_submap(void* store, const Lay& L, const DP& P, int b, Mgr* m, int sub, const Slot& src, unsigned src_st, const double* pose) {
@@ -890,7 +1001,9 @@ __device__ inline void set_last(Mgr* m, const Iso<double>& T) {
 }
 
 // laser_manager::add_scan (:424-496) without the key-frame deque
-__global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP P, int src_slot, const double* pose, const unsigned char* mask) {
+// pose of robot b at pose + b * pose_stride doubles (6 for a packed [B][6] array)
+__global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP P, int src_slot, const double* pose, long long pose_stride,
+                                                        const unsigned char* mask) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= L.B || (mask && !mask[b])) return;
     Mgr* m = (Mgr*)robot_ptr(store, L, b);
@@ -898,7 +1011,7 @@ __global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP 
     // an invalid source scan invalidates every sub-map this call writes (until that sub-map is replaced)
     const unsigned src_st = src.h->status ? ((unsigned)src.h->status | LIW_LFE_ST_INVALID) : 0u;
     m->status |= src_st;
-    const double* pq = pose + 6 * (size_t)b;
+    const double* pq = pose + (long long)b * pose_stride;
     const Iso<double> cur = tf6(pq);
     if (m->has_ref) {
         const Iso<double> last = liw::cast_iso<double>(m->last_R, m->last_t);
@@ -989,6 +1102,75 @@ __global__ void __launch_bounds__(256) k_lfe_pack(int B, int n, int frame, int c
     laser_frame[o] = frame;
     const double* r = recs + g * 12;
     for (int k = 0; k < 12; ++k) laser_pts[(size_t)k * Ltot + o] = r[k];
+}
+
+// laser_off of B INIT windows = exclusive scan over the robots of their F = n - 1 clamped counts (frame 0 has no blocks, so the
+// offset of (b, frame 0) is the window's); one block of 1024 as k_lfe_scan
+__global__ void __launch_bounds__(1024) k_lfe_scan_init(int B, int F, int cap, const int* count, int* off) {
+    __shared__ long long part[1024];
+    const int t = threadIdx.x;
+    const int per = (B + 1023) / 1024;
+    const int lo = t * per, hi = lo + per < B ? lo + per : B;
+    auto total = [&](int b) {
+        long long s = 0;
+        for (int k = 0; k < F; ++k) { const int c = count[(size_t)b * F + k]; s += c < 0 ? 0 : (c > cap ? cap : c); }
+        return s;
+    };
+    long long s = 0;
+    for (int b = lo; b < hi; ++b) s += total(b);
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const long long v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    long long run = part[t] - s;
+    for (int b = lo; b < hi; ++b) {
+        off[b] = (int)run;
+        run += total(b);
+    }
+    if (t == 1023) off[B] = (int)part[1023];
+}
+
+// one work-group per window: the frames' offsets inside the window in LDS (fo [n + 1], frame 0 empty), then a thread per block of
+// the window, ascending by owning frame; match_pose / has_match rows of all n frames and init_ok
+__global__ void __launch_bounds__(256) k_lfe_pack_init(int B, int n, int cap, int Ltot, const int* off, const int* count, const double* recs,
+                                                      const double* match_pose, const double* pose_front, int* laser_frame, double* laser_pts,
+                                                      double* mp_out, unsigned char* has_match, unsigned char* init_ok) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    int* fo = (int*)lds;
+    const int b = blockIdx.x, t = threadIdx.x, F = n - 1;
+    if (b >= B) return;
+    const int* cnt = count + (size_t)b * F;
+    if (t == 0) {
+        int run = 0, ok = 1;
+        fo[0] = 0;
+        for (int f = 1; f <= F; ++f) {
+            fo[f] = run;
+            const int c = cnt[f - 1];
+            if (c < 2) ok = 0;
+            run += c < 0 ? 0 : (c > cap ? cap : c);
+        }
+        fo[n] = run;
+        if (init_ok) init_ok[b] = (unsigned char)ok;
+    }
+    for (int e = t; e < n * 12; e += 256) {
+        const int f = e / 12, q = e % 12;
+        mp_out[(size_t)b * n * 12 + e] = f == 0 ? pose_front[6 * (size_t)b + q % 6] : match_pose[((size_t)b * F + f - 1) * 12 + q];
+    }
+    for (int f = t; f < n; f += 256) has_match[(size_t)b * n + f] = 1;
+    __syncthreads();
+    const int o0 = off[b], tot = fo[n];
+    for (int j = t; j < tot; j += 256) {
+        int lo = 1, hi = F;   // the last frame f in 1 .. F with fo[f] <= j
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (fo[mid] <= j) lo = mid; else hi = mid - 1; }
+        const int f = lo, o = o0 + j;
+        laser_frame[o] = f;
+        const double* r = recs + (((size_t)b * F + f - 1) * cap + (j - fo[f])) * 12;
+        for (int q = 0; q < 12; ++q) laser_pts[(size_t)q * Ltot + o] = r[q];
+    }
 }
 
 }  // namespace lfe
@@ -1188,7 +1370,7 @@ int liw_lfe_match(liw_lfe_ctx* c, void* store, int slot1, int slot2, const doubl
 int liw_lfe_add_scan(liw_lfe_ctx* c, void* store, int src_slot, const double* pose, const unsigned char* mask, void* stream) {
     LFE_DEV(c);
     if (!store || !pose || src_slot < 0 || src_slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_add_scan: bad argument");
-    hipLaunchKernelGGL(k_lfe_add_scan, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, src_slot, pose, mask);
+    hipLaunchKernelGGL(k_lfe_add_scan, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, src_slot, pose, 6LL, mask);
     return launched(c);
 }
 
@@ -1210,6 +1392,56 @@ int liw_lfe_pack_track(liw_lfe_ctx* c, int n, int frame, int cap, const int* cou
                        laser_frame, laser_pts, match_pose_out, has_match);
     if (int r = launched(c)) return r;
     return Ltot;
+}
+
+int liw_lfe_match_front(liw_lfe_ctx* c, void* store, int front_slot, int first_slot, int F, const double* pose_front, const double* poses,
+                        long long robot_stride, long long frame_stride, int kk, int cap, int* count, double* recs, int* idx1, int* idx2,
+                        double* match_pose, void* stream) {
+    LFE_DEV(c);
+    if (!store || !pose_front || !poses || !count || !recs || !match_pose || cap < 1 || kk < 0 || F < 1 || first_slot < 0 ||
+        (long long)first_slot + F > c->L.slots || front_slot < 0 || front_slot >= c->L.slots)
+        return fail(c, LIW_EINVAL, "liw_lfe_match_front: bad argument");
+    if ((long long)c->L.B * F >= (1LL << 31)) return fail(c, LIW_EINVAL, "liw_lfe_match_front: B * F must fit in int32");
+    const size_t lds = 12 * (size_t)c->L.max_lines;   // best and d per line of the frame's scan
+    if (lds > kWaveLdsMax) return fail(c, LIW_EINVAL, "liw_lfe_match_front: max_lines needs more than 64 KiB of LDS");
+    hipLaunchKernelGGL(k_lfe_match_wave, dim3((unsigned)((size_t)c->L.B * F)), dim3(kBlock), lds, (hipStream_t)stream, store, c->L, c->P, front_slot,
+                       first_slot, F, pose_front, poses, robot_stride, frame_stride, kk, cap, count, recs, idx1, idx2, match_pose);
+    return launched(c);
+}
+
+int liw_lfe_pack_init(liw_lfe_ctx* c, int n, int cap, const int* count, const double* recs, const double* match_pose, const double* pose_front,
+                      int L_cap, int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match,
+                      unsigned char* init_ok, void* stream) {
+    LFE_DEV(c);
+    if (n < 2 || cap < 1 || L_cap < 0 || !count || !recs || !match_pose || !pose_front || !laser_off || !laser_frame || !laser_pts ||
+        !match_pose_out || !has_match)
+        return fail(c, LIW_EINVAL, "liw_lfe_pack_init: bad argument");
+    if ((long long)c->L.B * (n - 1) * cap >= (1LL << 31)) return fail(c, LIW_EINVAL, "liw_lfe_pack_init: B * (n - 1) * cap must fit in int32");
+    const size_t lds = 4 * ((size_t)n + 1);
+    if (lds > kWaveLdsMax) return fail(c, LIW_EINVAL, "liw_lfe_pack_init: n needs more than 64 KiB of LDS");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_lfe_scan_init, dim3(1), dim3(1024), 0, s, c->L.B, n - 1, cap, count, laser_off);
+    if (int r = launched(c)) return r;
+    int Ltot = 0;
+    if (hipMemcpyAsync(&Ltot, laser_off + c->L.B, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(c, LIW_EHIP, "liw_lfe_pack_init: read-back of Ltot");
+    if (Ltot > L_cap) return fail(c, LIW_ENOMEM, "liw_lfe_pack_init: Ltot exceeds L_cap");
+    hipLaunchKernelGGL(k_lfe_pack_init, dim3(c->L.B), dim3(256), lds, s, c->L.B, n, cap, Ltot, laser_off, count, recs, match_pose, pose_front,
+                       laser_frame, laser_pts, match_pose_out, has_match, init_ok);
+    if (int r = launched(c)) return r;
+    return Ltot;
+}
+
+int liw_lfe_rebuild(liw_lfe_ctx* c, void* store, int first_slot, int F, const double* poses, long long robot_stride, long long frame_stride,
+                    const unsigned char* mask, void* stream) {
+    LFE_DEV(c);
+    if (!store || !poses || F < 1 || first_slot < 0 || (long long)first_slot + F > c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_rebuild: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_lfe_reset_mgr, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, s, store, c->L, mask);
+    for (int k = 0; k < F; ++k)
+        hipLaunchKernelGGL(k_lfe_add_scan, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, s, store, c->L, c->P, first_slot + k,
+                           poses + (long long)k * frame_stride, robot_stride, mask);
+    return launched(c);
 }
 
 int liw_lfe_status(liw_lfe_ctx* c, const void* store, int robot, int slot) {

@@ -1,7 +1,8 @@
 """Batched laser front-end on the device (C ABI include/liw_laser_batch.h): `BatchFrontEnd` runs the tracking-time work of
 `laser.LaserManager` for B robots at once on torch device tensors — ranges -> points -> de-skew -> lines -> matches against
-the reference sub-map -> sub-map update -> the laser arrays `BatchSolver.rebind` takes.  The host front-end (`laser`) is its
-parity reference.  There is no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device."""
+the reference sub-map -> sub-map update -> the laser arrays `BatchSolver.rebind` takes — and a fleet's initialisation: the
+matches of a whole INIT window against the front key frame (`match_front`), its laser arrays (`pack_init`) and the sub-map
+rebuild at the solved poses (`rebuild`).  The host front-end (`laser`) is its parity reference.  There is no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device."""
 import ctypes as C
 
 import numpy as np
@@ -13,7 +14,7 @@ LFE_EXPORTS = [
     "liw_lfe_store_layout", "liw_lfe_create", "liw_lfe_destroy", "liw_lfe_last_error", "liw_lfe_set_geometry", "liw_lfe_store_reset",
     "liw_lfe_ranges_to_points", "liw_lfe_deskew", "liw_lfe_spawn", "liw_lfe_match", "liw_lfe_add_scan", "liw_lfe_pack_track",
     "liw_lfe_status", "liw_lfe_num_lines", "liw_lfe_get_lines", "liw_lfe_cell_lines", "liw_lfe_submap_pose",
-    "liw_lfe_spawn_corners", "liw_lfe_corners_to_world",
+    "liw_lfe_spawn_corners", "liw_lfe_corners_to_world", "liw_lfe_match_front", "liw_lfe_pack_init", "liw_lfe_rebuild",
 ]
 
 ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID, ST_CORNERS = 1, 2, 4, 8, 16, 32
@@ -55,6 +56,10 @@ def _lib():
         L.liw_lfe_match.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_add_scan.argtypes = [vp, vp, C.c_int, vp, vp, vp]
         L.liw_lfe_pack_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        ll = C.c_longlong
+        L.liw_lfe_match_front.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, ll, ll, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_pack_init.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_rebuild.argtypes = [vp, vp, C.c_int, C.c_int, vp, ll, ll, vp, vp]
         L.liw_lfe_status.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_num_lines.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_get_lines.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int]
@@ -285,6 +290,74 @@ class BatchFrontEnd:
                                                    L_cap, self._p(off), self._p(lf), self._p(lp), self._p(out["match_pose"]), self._p(out["has_match"]), self._s()))
         res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
         return res, Ltot
+
+    # ------------------------------------------------------------------------------------------------- initialisation
+    def _strided_poses(self, poses, F):
+        """poses of F frames per robot -> (tensor kept alive, robot stride, frame stride) in doubles: a [B, F, k >= 6] float64 device
+        tensor whose last stride is 1 (a view of x [B, n, 15] included) is passed as it is, anything else is packed to [B, F, 6]"""
+        torch = self.torch
+        if (torch.is_tensor(poses) and poses.dim() == 3 and poses.dtype == torch.float64 and poses.device == self.dev and poses.shape[0] == self.B
+                and poses.shape[1] == F and poses.shape[2] >= 6 and poses.stride(2) == 1 and poses.stride(0) >= 0 and poses.stride(1) >= 0):
+            return poses, int(poses.stride(0)), int(poses.stride(1))
+        t = self._t(poses, torch.float64, (self.B, F, 6))
+        return t, 6 * F, 6
+
+    def match_front(self, front_slot, first_slot, F, pose_front, poses, kk=0, cap=256, out=None):
+        """laser_manager::match_with_front of a whole INIT window in one launch: scan slots first_slot .. first_slot + F - 1 against
+        `front_slot`, task (b, k) = match(front_slot, first_slot + k, pose_front, poses[:, k], kk) bit for bit.  pose_front [B, 6];
+        poses [B, F, 6], or a strided view such as x.view(B, n, 15)[:, 1:, :6].  -> dict(count [B, F], recs [B, F, cap, 12],
+        idx1 / idx2 [B, F, cap], match_pose [B, F, 12], cap, F); `out` may supply any of the tensors."""
+        torch = self.torch
+        F = int(F)
+        pf = self._t(pose_front, torch.float64, (self.B, 6))
+        ps, rs, fs = self._strided_poses(poses, F)
+        z = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device=self.dev)
+        o = {} if out is None else dict(out)
+        for k, shape, dt in (("count", (self.B, F), torch.int32), ("recs", (self.B, F, cap, 12), torch.float64), ("idx1", (self.B, F, cap), torch.int32),
+                             ("idx2", (self.B, F, cap), torch.int32), ("match_pose", (self.B, F, 12), torch.float64)):
+            if k not in o:
+                o[k] = z(*[max(int(v), 0) for v in shape], dt=dt)
+            assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() >= int(np.prod(shape)), k
+        o["cap"], o["F"] = int(cap), F
+        self._chk(self.L.liw_lfe_match_front(self.h, self._p(self.store), int(front_slot), int(first_slot), F, self._p(pf), self._p(ps), rs, fs, int(kk),
+                                             int(cap), self._p(o["count"]), self._p(o["recs"]), self._p(o["idx1"]), self._p(o["idx2"]),
+                                             self._p(o["match_pose"]), self._s()))
+        return o
+
+    def pack_init(self, m, n, pose_front, out=None, L_cap=None, bufs=None):
+        """the laser arrays of B n-frame INIT windows from a match_front() result with F = n - 1 (frame 0: the empty match at
+        pose_front [B, 6]).  out: dict with `match_pose` [B * n * 12], `has_match` [B * n], `init_ok` [B] to write into; bufs:
+        laser_off [B + 1], laser_frame [L_cap], laser_pts [12 * L_cap] to reuse.  -> (dict of laser_off, laser_frame, laser_pts,
+        match_pose, has_match for BatchSolver.rebind, Ltot, init_ok [B] uint8: 1 iff every frame 1 .. n-1 has at least 2 pairs)."""
+        torch = self.torch
+        n, cap = int(n), int(m["cap"])
+        assert int(m["F"]) == n - 1, "pack_init needs a match_front result with F = n - 1"
+        L_cap = self.B * (n - 1) * cap if L_cap is None else int(L_cap)
+        pf = self._t(pose_front, torch.float64, (self.B, 6))
+        out = dict(out or {})
+        for k, size, dt in (("match_pose", self.B * n * 12, torch.float64), ("has_match", self.B * n, torch.uint8), ("init_ok", self.B, torch.uint8)):
+            if k not in out:
+                out[k] = torch.zeros(max(size, 1), dtype=dt, device=self.dev)
+            assert out[k].dtype == dt and out[k].is_contiguous() and out[k].numel() >= size, k
+        if bufs is None:
+            bufs = dict(laser_off=torch.empty(self.B + 1, dtype=torch.int32, device=self.dev),
+                        laser_frame=torch.empty(max(L_cap, 1), dtype=torch.int32, device=self.dev),
+                        laser_pts=torch.empty(12 * max(L_cap, 1), dtype=torch.float64, device=self.dev))
+        off, lf, lp = bufs["laser_off"], bufs["laser_frame"], bufs["laser_pts"]
+        assert off.numel() >= self.B + 1 and lf.numel() >= max(L_cap, 1) and lp.numel() >= 12 * max(L_cap, 1)
+        Ltot = self._chk(self.L.liw_lfe_pack_init(self.h, n, cap, self._p(m["count"]), self._p(m["recs"]), self._p(m["match_pose"]), self._p(pf), L_cap,
+                                                  self._p(off), self._p(lf), self._p(lp), self._p(out["match_pose"]), self._p(out["has_match"]),
+                                                  self._p(out["init_ok"]), self._s()))
+        res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
+        return res, Ltot, out["init_ok"]
+
+    def rebuild(self, first_slot, F, poses, mask=None):
+        """the sub-map rebuild after the INIT solve: clear_all_scan on the masked robots' managers (their scan slots are kept), then
+        add_scan of slot first_slot + k at poses[:, k], k = 0 .. F - 1.  poses as in match_front (x.view(B, n, 15) is one)."""
+        F = int(F)
+        ps, rs, fs = self._strided_poses(poses, F)
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_rebuild(self.h, self._p(self.store), int(first_slot), F, self._p(ps), rs, fs, self._p(m), self._s()))
 
     # -------------------------------------------------------------------------------------------------------- getters
     def status(self, robot, slot=ROBOT):

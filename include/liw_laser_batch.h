@@ -1,7 +1,8 @@
 /* liw_laser_batch.h — C ABI of the batched laser front-end on the device: the tracking-time work of liw_laser.h for B robots
  * at once (ranges -> points -> de-skew -> lines -> matches against the reference sub-map -> sub-map update -> the laser arrays
- * of a liw_batch), so that a fleet's frame never leaves device memory.  The single-scan host front-end (liw_laser.h) is the
- * parity reference of every entry point here.
+ * of a liw_batch), so that a fleet's frame never leaves device memory, and the initialisation that comes before it (the matches
+ * of a window against its front key frame, the INIT-topology laser arrays, the sub-map rebuild at the solved poses).  The
+ * single-scan host front-end (liw_laser.h) is the parity reference of every entry point here.
  *
  * Conventions as the batch API of liw_window.h:
  *   - the caller owns all device memory: the store (sized by liw_lfe_store_layout) and every input / output array;
@@ -140,6 +141,47 @@ int liw_lfe_add_scan(liw_lfe_ctx* ctx, void* store, int src_slot, const double* 
 int liw_lfe_pack_track(liw_lfe_ctx* ctx, int n, int frame, int cap, const int* count, const double* recs, const double* match_pose,
                        int L_cap, int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match,
                        void* stream);
+
+/* Initialisation (lvio_2d::trajectory while status == INITIALIZING).  The caller keeps the window's scans in scan slots; the
+ * reference's per-frame add_scan calls while INITIALIZING only feed the key-frame deque (here: the caller's slots) and sub-maps
+ * that clear_all_scan discards before anything reads them, so the device path does not make them: a window is
+ * spawn (per frame) -> liw_lfe_match_front -> liw_lfe_pack_init -> the INIT solve -> liw_lfe_rebuild at the solved poses.
+ *
+ * liw_lfe_match_front: laser_manager::match_with_front of a whole window in one launch.  Task (robot b, frame k), k = 0 .. F-1, is
+ * exactly liw_lfe_match(front_slot, first_slot + k, pose_front, pose_k, kk): the same count, recs[0 .. count), idx1 / idx2[0 .. count)
+ * and match_pose, count 0 and LIW_LFE_ST_INVALID for an invalid slot, count 0 and LIW_LFE_ST_MATCH for more than cap pairs (bytes of
+ * recs past count are unspecified).  pose_front [B][6]; the pose of frame k of robot b is read at
+ * poses + b * robot_stride + k * frame_stride (strides in doubles: a packed [B][F][6] array has 6 F and 6; the states array
+ * x [B][n][15] of a liw_batch, offset to its first matched frame, has 15 n and 15).  Outputs by task: count [B][F],
+ * recs [B][F][cap][12], idx1 / idx2 [B][F][cap] (either may be NULL), match_pose [B][F][12].  One wavefront works on one task (lanes
+ * over the lines of the frame's scan, 12 bytes of LDS per line of max_lines); the mean distance is summed and the pairs are written in
+ * line order, so the result is bit-identical to liw_lfe_match's.  Tasks of one robot set its status word with an atomic OR.
+ * LIW_EINVAL: F < 1, first_slot < 0, first_slot + F > slots, front_slot outside 0 .. slots-1, cap < 1, kk < 0, a null array. */
+int liw_lfe_match_front(liw_lfe_ctx* ctx, void* store, int front_slot, int first_slot, int F, const double* pose_front, const double* poses,
+                        long long robot_stride, long long frame_stride, int kk, int cap, int* count, double* recs, int* idx1, int* idx2,
+                        double* match_pose, void* stream);
+
+/* The laser arrays of a liw_batch of B n-frame INIT windows from a liw_lfe_match_front output with F = n - 1 (task k is frame k + 1;
+ * count, recs with row stride cap, match_pose) and the front poses:
+ *   laser_off [B+1]; laser_frame [Ltot]: the owning frame of every block, ascending inside each window; laser_pts [12][Ltot]
+ *   component-major; match_pose_out [B][n][12]; has_match [B][n]; init_ok [B] (may be NULL).
+ * Frame 0 of every window gets the empty match of the reference's first frame: no blocks, match_pose (p0 q0 p0 q0) from pose_front,
+ * has_match 1.  Frame f = 1 .. n-1 gets its match's pose row, has_match 1 and its count blocks (counts clamped to 0 .. cap).
+ * init_ok[b] = 1 iff every frame 1 .. n-1 of robot b has count >= 2 (check_and_processing_initialize's lines2.size() < 2 test).  A
+ * failing robot is packed like any other; the caller masks it out of liw_lfe_rebuild and gives it to liw_lfe_store_reset, as the
+ * reference does with pop_frame + clear_all_scan + init_current_status.  No atomics decide a position: the output is deterministic.
+ * laser_frame / laser_pts must hold L_cap blocks; Ltot > L_cap is LIW_ENOMEM (nothing but laser_off written).  Returns Ltot: the one
+ * host read-back (a 4-byte copy and a synchronisation of `stream`).  LIW_EINVAL: n < 2, cap < 1, L_cap < 0, a null array. */
+int liw_lfe_pack_init(liw_lfe_ctx* ctx, int n, int cap, const int* count, const double* recs, const double* match_pose, const double* pose_front,
+                      int L_cap, int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match,
+                      unsigned char* init_ok, void* stream);
+
+/* The sub-map rebuild after init_solve: for the robots with mask[b] != 0 (all when NULL) laser_manager::clear_all_scan on the manager
+ * alone (state, status word, both sub-maps; every scan slot is kept), then liw_lfe_add_scan of scan slot first_slot + k at pose k for
+ * k = 0 .. F-1 in order (motion filter, first-scan sub-map, the ref_n_accumulation swap, invalid-source propagation).  Poses strided
+ * as in liw_lfe_match_front, with k = 0 the window's first frame.  LIW_EINVAL: F < 1, first_slot < 0, first_slot + F > slots. */
+int liw_lfe_rebuild(liw_lfe_ctx* ctx, void* store, int first_slot, int F, const double* poses, long long robot_stride, long long frame_stride,
+                    const unsigned char* mask, void* stream);
 
 /* getters (synchronous device -> host copies; tests and tools).  slot: 0 .. slots-1, LIW_LFE_REF or LIW_LFE_SPAWNING. */
 /* status word of robot / slot (slot = LIW_LFE_ROBOT: the robot word); a missing sub-map reads LIW_LFE_NONE */

@@ -7,7 +7,12 @@ match against the reference sub-map, add_scan (the accumulating call: the refere
 HIP events on the current stream (median of --reps after one warm-up); scans/s = B / ms.  For comparison the same line carries
 the host front-end (liw.laser through ctypes) per scan over 256 robots: laser_to_points, Scan.spawn, match_with_ref, add_scan.
 
-  python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5]
+--init N adds the initialisation of a fleet (key "init", per B of --init-B): N scans per robot in N scan slots, then
+match_front_ms (F = N - 1 frames against slot 0 in one launch of the wave-per-(robot, frame) kernel), lane_match_ms (the same
+work as N - 1 calls of the lane-per-robot match, outputs reused), pack_init_ms (incl. the Ltot read-back) and rebuild_ms, each
+with min / max, the ratio lane / wave, and whether the two paths' counts agree.  --B "" runs that leg alone.
+
+  python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5] [--init 30 [--init-B 4096]]
 """
 import argparse
 import importlib
@@ -147,6 +152,72 @@ def device_run(liw, torch, lp, B, sc, reps, cap=256, max_corners=64):
     return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
 
 
+def init_scenes(liw, lp, nd, N, seed=4343):
+    """nd distinct windows of N scans: (ranges [nd, N, n_rays], poses [nd, N, 6]), frame 0 the front key frame"""
+    rng = np.random.default_rng(seed)
+    Til = np.asarray(lp["T_imu_to_laser"], dtype=np.float64).reshape(4, 4)
+    R, Pq = np.zeros((nd, N, N_RAYS), dtype=np.float32), np.zeros((nd, N, 6))
+    for j in range(nd):
+        segs = liw.laser.room_segments(6000 + j)
+        a = np.concatenate([rng.uniform(-1, 1, 2), [0.0, 0.0, 0.0], rng.uniform(-np.pi, np.pi, 1)])
+        for k in range(N):
+            if k:   # a walk away from the front pose, a few centimetres and degrees per frame
+                a = a.copy()
+                a[:2] += rng.uniform(-0.03, 0.03, 2)
+                a[5] += rng.uniform(-0.02, 0.02)
+            R[j, k] = liw.laser.cast_scan(segs, _T(a[:3], a[3:]) @ Til, n_rays=N_RAYS, seed=100 * j + k)[0]
+            Pq[j, k] = a
+    return R, Pq
+
+
+def init_run(liw, torch, lp, B, N, nd, reps, cap=256):
+    R, Pq = init_scenes(liw, lp, nd, N)
+    rob = torch.from_numpy(np.arange(B) % nd).cuda()
+    dims = dict(B=B, slots=N, max_points=N_RAYS, max_lines=256, max_cell_entries=8192)
+    fe = liw.laser_batch.BatchFrontEnd(lp, dims)
+    fe.set_geometry(N_RAYS, ANG_MIN, ANG_INC, T_INC)
+    stamps = torch.zeros(B, dtype=torch.float64, device="cuda")
+    Rd = torch.from_numpy(R).cuda()
+    buf = None
+    for k in range(N):
+        buf = fe.ranges_to_points(Rd[:, k][rob].contiguous(), stamps, out=buf)
+        fe.spawn(k, buf[0], buf[2])
+    poses = torch.from_numpy(Pq).cuda()[rob].contiguous()           # [B, N, 6]
+    pf, pk = poses[:, 0].contiguous(), [poses[:, k].contiguous() for k in range(N)]
+    F = N - 1
+    out = dict(dims=dims, N=N, cap=cap, store_GB=round(fe.store.numel() / 1e9, 3))
+    sp = []
+    m = fe.match_front(0, 1, F, pf, poses[:, 1:], cap=cap)
+    mb = {k: m[k] for k in ("count", "recs", "idx1", "idx2", "match_pose")}
+    out["match_front_ms"] = timed(torch, lambda: fe.match_front(0, 1, F, pf, poses[:, 1:], cap=cap, out=mb), reps, sp)
+    out["match_front_min_ms"], out["match_front_max_ms"] = sp
+    l = fe.match(0, 1, pf, pk[1], cap=cap)
+    lb_ = {k: l[k] for k in ("count", "recs", "idx1", "idx2", "match_pose")}
+    counts = []
+    for k in range(1, N):                                           # the lane path's counts, for the agreement flag
+        counts.append(fe.match(0, k, pf, pk[k], cap=cap, out=lb_)["count"].clone())
+
+    def lane_all():
+        for k in range(1, N):
+            fe.match(0, k, pf, pk[k], 0, cap, out=lb_)
+    out["lane_match_ms"] = timed(torch, lane_all, reps, sp)
+    out["lane_match_min_ms"], out["lane_match_max_ms"] = sp
+    out["lane_over_wave"] = out["lane_match_ms"] / out["match_front_ms"]
+    out["counts_agree"] = bool(torch.equal(torch.stack(counts, 1), m["count"].view(B, F)))
+    pack, Ltot, ok = fe.pack_init(m, N, pf)
+    bufs = dict(laser_off=pack["laser_off"], laser_frame=torch.empty(max(Ltot, 1), dtype=torch.int32, device="cuda"),
+                laser_pts=torch.empty(12 * max(Ltot, 1), dtype=torch.float64, device="cuda"))
+    po = dict(match_pose=pack["match_pose"], has_match=pack["has_match"], init_ok=ok)
+    out["pack_init_ms"] = timed(torch, lambda: fe.pack_init(m, N, pf, out=po, L_cap=Ltot, bufs=bufs), reps, sp)
+    out["pack_init_min_ms"], out["pack_init_max_ms"] = sp
+    out["rebuild_ms"] = timed(torch, lambda: fe.rebuild(0, N, poses), reps, sp)
+    out["rebuild_min_ms"], out["rebuild_max_ms"] = sp
+    out["Ltot"], out["pairs_per_frame"], out["init_ok"] = int(Ltot), Ltot / (B * F), int(ok.sum().item())
+    del fe
+    torch.cuda.empty_cache()
+    return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
+
+
 def host_run(liw, lp, sc, n=256):
     ra, rb, pa, pb = sc
     nd = ra.shape[0]
@@ -178,15 +249,22 @@ def main():
     ap.add_argument("--B", default="4096,49152")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--distinct", type=int, default=64)
+    ap.add_argument("--init", type=int, default=0, help="frames per INIT window (0: no initialisation leg)")
+    ap.add_argument("--init-B", default="4096")
     a = ap.parse_args()
     import torch
     liw = importlib.import_module("2dliw-slam_amd")
     lp = liw.laser.office_laser_params()
-    sc = scenes(liw, lp, a.distinct)
     res = dict(tool="bench_laser_batch", n_rays=N_RAYS, distinct=a.distinct, device=torch.cuda.get_device_name(0), batch={})
-    for B in [int(x) for x in a.B.split(",")]:
-        res["batch"][str(B)] = device_run(liw, torch, lp, B, sc, a.reps)
-    res["host_per_scan"] = host_run(liw, lp, sc)
+    Bs = [int(x) for x in a.B.split(",") if x]
+    if Bs:
+        sc = scenes(liw, lp, a.distinct)
+        for B in Bs:
+            res["batch"][str(B)] = device_run(liw, torch, lp, B, sc, a.reps)
+        res["host_per_scan"] = host_run(liw, lp, sc)
+    if a.init:
+        assert a.init >= 2, "--init N: at least two frames"
+        res["init"] = {str(B): init_run(liw, torch, lp, B, a.init, a.distinct, a.reps) for B in [int(x) for x in a.init_B.split(",") if x]}
     print(json.dumps(res))
 
 
