@@ -258,9 +258,27 @@ class BatchSolver:
         b.eval_small = 1
         b.history_records = self.history_records
         self.b = b
-        # views of the laser partial sums (what a factor-sharded run all-reduces)
+        # views of the laser partial sums as the workspace keeps them (what a factor-sharded run all-reduces): 128-slot records, or the
+        # compact records of the large-batch format (lay.laser_partial_stride doubles each: the pair totals the 128 slots expand)
         nd = int(lay.laser_partial_bytes) // 8
-        self.PL = [self.ws[int(lay.laser_partial_off[k]):int(lay.laser_partial_off[k]) + nd * 8].view(torch.float64) for k in range(2)]
+        self.PL_raw = [self.ws[int(lay.laser_partial_off[k]):int(lay.laser_partial_off[k]) + nd * 8].view(torch.float64) for k in range(2)]
+        self._pl_mode = 0          # topology of the last laser linearisation (LIW_MODE_*): which expansion a compact record stands for
+
+    @property
+    def PL(self):
+        """The laser group records of the two partial buffers as 128-slot records [B * n * 128] (Haa | Hbb | Hab | ga | gb | sum r^2).
+        Small batches: views of the workspace.  Large-batch format: the workspace holds the pair totals only, and this returns
+        expanded COPIES (liw_batch_laser_records), read at the topology of the last linearisation."""
+        from . import LASER_PARTIAL
+        if int(self.lay.laser_partial_stride) == LASER_PARTIAL:
+            return self.PL_raw
+        out = []
+        for k in range(2):
+            o = self.torch.empty(self.B * self.n * LASER_PARTIAL, dtype=self.torch.float64, device=self.dev)
+            self._chk(self.L.liw_batch_laser_records(self.h, C.byref(self.b), C.c_int(self._pl_mode), C.c_int(k), self._wsp(),
+                                                     C.c_void_p(o.data_ptr()), self._stream()))
+            out.append(o)
+        return out
 
     INPUT_KEYS = ("x", "laser_off", "laser_frame", "laser_pts", "match_pose", "has_match", "imu_X", "imu_J", "imu_sqrtP", "imu_Dt", "wheel_T", "wheel_sqrtP")
 
@@ -308,6 +326,7 @@ class BatchSolver:
     def solve(self, mode, max_iters=0, use_graph=False):
         """Runs the whole LM loop.  Single rank: one native call (optionally a captured hipGraph).  Factor-sharded:
         the loop is driven here so the all-reduce sits between linearise and step."""
+        self._pl_mode = int(mode)
         if not self.sharded:
             if use_graph:
                 # stream capture is not allowed on the legacy default stream: replay on a dedicated side stream
@@ -530,6 +549,7 @@ class BatchSolver:
         return K
 
     def lm_linearize(self, mode, candidate):
+        self._pl_mode = int(mode)
         self._chk(self.L.liw_batch_lm_linearize(self.h, C.byref(self.b), C.c_int(mode), C.c_int(candidate), self._wsp(), self._stream()))
 
     def lm_step(self, mode):
@@ -546,13 +566,14 @@ class BatchSolver:
         return dict(zip(("k_lin_laser", "k_lin_imu", "k_lin_small", "k_lm_step", "k_marg_schur", "k_lin_laser_marg"), [float(v) for v in out]))
 
     def linearize(self, mode):
+        self._pl_mode = int(mode)
         self._chk(self.L.liw_batch_linearize(self.h, C.byref(self.b), C.c_int(mode), self._wsp(), self._stream()))
         if self.sharded:
             self._exchange_plain(mode)
 
     def _exchange_plain(self, mode):
         # stand-alone linearisations carry no LM state: exchange the full record region (rare path: tests, liw_linearize)
-        self.comm.all_reduce_sum_(self.PL[0])
+        self.comm.all_reduce_sum_(self.PL_raw[0])      # (compact records: sums of pair totals, the zeros behind them stay zeros)
 
     def export_dense(self, mode):
         N = 15 * self.n
@@ -570,6 +591,8 @@ class BatchSolver:
         dH = torch.zeros((self.B, 225), dtype=torch.float64, device=self.dev)
         dg = torch.zeros((self.B, 15), dtype=torch.float64, device=self.dev)
         s = self._stream()
+        from . import LIW_MODE_MARG as _MARG
+        self._pl_mode = _MARG
         self._chk(self.L.liw_batch_marg_linearize(self.h, C.byref(self.b), self._wsp(), s))
         if self.sharded:
             from . import LIW_MODE_MARG

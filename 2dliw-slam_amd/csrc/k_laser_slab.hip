@@ -52,37 +52,14 @@ __device__ __forceinline__ void frame_tf2(const DevParams& P, const double* pose
     }
 }
 
-// slot s of the 128-slot group record (liw_kernels.hpp) as (pair total | 64 if negated), -1 = structural zero; both poses free.
-// The constexpr twin of laser_slot_code<true>: a lane writes its own record, so the expansion is resolved at compile time.
-constexpr int slab_pairidx(int c1, int c2) { return c1 > c2 ? slab_pairidx(c2, c1) : c1 * 9 - c1 * (c1 - 1) / 2 + (c2 - c1); }
-constexpr int slab_col_a(int idx) { return idx < 2 ? idx : (idx == 2 ? -1 : idx - 1); }
-constexpr int slab_col_b(int idx) { return idx < 2 ? idx : (idx == 2 ? -1 : idx + 2); }
-constexpr int slab_slot_code(int s) {
-    if (s < 36) { const int ca = slab_col_a(s / 6), cb = slab_col_a(s % 6); return (ca >= 0 && cb >= 0) ? slab_pairidx(ca, cb) : -1; }
-    if (s < 72) {
-        const int ia = (s - 36) / 6, ib = (s - 36) % 6, ca = slab_col_b(ia), cb = slab_col_b(ib);
-        return (ca >= 0 && cb >= 0) ? (slab_pairidx(ca, cb) | (((ia < 2) != (ib < 2)) ? 64 : 0)) : -1;
-    }
-    if (s < 108) {
-        const int ia = (s - 72) / 6, ib = (s - 72) % 6, ca = slab_col_a(ia), cb = slab_col_b(ib);
-        return (ca >= 0 && cb >= 0) ? (slab_pairidx(ca, cb) | ((ib < 2) ? 64 : 0)) : -1;
-    }
-    if (s < 114) { const int ca = slab_col_a(s - 108); return ca >= 0 ? slab_pairidx(ca, 8) : -1; }
-    if (s < 120) { const int cb = slab_col_b(s - 114); return cb >= 0 ? (slab_pairidx(cb, 8) | ((s - 114 < 2) ? 64 : 0)) : -1; }
-    if (s == 120) return slab_pairidx(8, 8);
-    return -1;
-}
-// the same for the ONE-free-pose record (MARG / TRACK topology: the block's a-pose is the constant laser_match pose, solver.cpp:471-472,
-// :669-698): unique columns px py th0 th1 th2 of the owning frame + the residual = 21 pair totals, H_bb / g_b / cost slots only, no sign
-// (the constexpr twin of laser_slot_code<false>)
-constexpr int slab_pairidx1(int c1, int c2) { return c1 > c2 ? slab_pairidx1(c2, c1) : c1 * 6 - c1 * (c1 - 1) / 2 + (c2 - c1); }
-constexpr int slab_col_b1(int idx) { return idx == 2 ? -1 : (idx < 2 ? idx : idx - 1); }
-constexpr int slab_slot_code1(int s) {
-    if (s >= 36 && s < 72) { const int ca = slab_col_b1((s - 36) / 6), cb = slab_col_b1((s - 36) % 6); return (ca >= 0 && cb >= 0) ? slab_pairidx1(ca, cb) : -1; }
-    if (s >= 114 && s < 120) { const int cb = slab_col_b1(s - 114); return cb >= 0 ? slab_pairidx1(cb, 5) : -1; }
-    if (s == 120) return slab_pairidx1(5, 5);
-    return -1;
-}
+// slot s of the 128-slot group record as (pair total | 64 if negated), -1 = structural zero: laser_slot_code (liw_kernels.hpp), which is
+// constexpr — a lane writes its own record, so the expansion is resolved at compile time.  Both poses free (9 unique columns, 45 pair
+// totals) and the ONE-free-pose record (MARG / TRACK topology: the block's a-pose is the constant laser_match pose, solver.cpp:471-472,
+// :669-698: unique columns px py th0 th1 th2 of the owning frame + the residual = 21 pair totals, H_bb / g_b / cost slots only, no sign).
+constexpr int slab_pairidx(int c1, int c2) { return laser_pairidx<true>(c1, c2); }
+constexpr int slab_pairidx1(int c1, int c2) { return laser_pairidx<false>(c1, c2); }
+constexpr int slab_slot_code(int s) { return laser_slot_code<true>(s); }
+constexpr int slab_slot_code1(int s) { return laser_slot_code<false>(s); }
 template <bool BOTH, int S_> __device__ __forceinline__ double slab_slot(const double* acc) {
     constexpr int code = BOTH ? slab_slot_code(S_) : slab_slot_code1(S_);
     if constexpr (code < 0) return 0.0;
@@ -135,6 +112,60 @@ template <bool BOTH, int C_> __device__ __forceinline__ void slab_flush(double* 
 #endif
         }
         slab_flush<BOTH, C_ + 1>(lds, pw, acc, lane);
+    }
+}
+
+// The compact record of the large-batch format (LPC = 48 doubles: the pair totals, zeros behind them) leaves the same way in one and a
+// half chunks: totals 0 .. 31 as 256-byte runs (four windows per store instruction), totals 32 .. 47 as 128-byte runs (eight windows per
+// instruction).  A record is three 128-byte lines at a 128-byte boundary, so every run is whole lines.
+template <int N_, int S_> __device__ __forceinline__ double slab_total(const double* acc) {
+    if constexpr (S_ < N_) return acc[S_]; else return 0.0;
+}
+template <int N_, int S0_, int CNT_, int I_ = 0> __device__ __forceinline__ void slab_stage_totals(double* st, const double* acc) {
+    if constexpr (I_ < CNT_) {
+        typedef double __attribute__((ext_vector_type(2))) dbl2;
+        dbl2 v;
+        v.x = slab_total<N_, S0_ + 2 * I_>(acc); v.y = slab_total<N_, S0_ + 2 * I_ + 1>(acc);
+        *reinterpret_cast<dbl2*>(st + 2 * I_) = v;
+        slab_stage_totals<N_, S0_, CNT_, I_ + 1>(st, acc);
+    }
+}
+template <int N_> __device__ __forceinline__ void slab_flush_compact(double* lds, const unsigned long long* pw, const double* acc, int lane) {
+    typedef double __attribute__((ext_vector_type(2))) dbl2;
+    static_assert(LPC == 48 && N_ <= LPC, "one and a half chunks");
+    lds_sync();
+    slab_stage_totals<N_, 0, 16>(lds + lane * STG, acc);
+    lds_sync();
+    {
+        const int wq = lane >> 4, pc = lane & 15;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int w = 4 * t + wq;
+            const unsigned long long p = pw[w];
+            const dbl2 v = *reinterpret_cast<const dbl2*>(lds + w * STG + 2 * pc);
+#if LIW_SLAB_NT & 2
+            if (p) __builtin_nontemporal_store(v, reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 2 * pc));
+#else
+            if (p) *reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 2 * pc) = v;
+#endif
+        }
+    }
+    lds_sync();
+    slab_stage_totals<N_, 32, 8>(lds + lane * STG, acc);
+    lds_sync();
+    {
+        const int wq = lane >> 3, pc = lane & 7;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int w = 8 * t + wq;
+            const unsigned long long p = pw[w];
+            const dbl2 v = *reinterpret_cast<const dbl2*>(lds + w * STG + 2 * pc);
+#if LIW_SLAB_NT & 2
+            if (p) __builtin_nontemporal_store(v, reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 32 + 2 * pc));
+#else
+            if (p) *reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 32 + 2 * pc) = v;
+#endif
+        }
     }
 }
 
@@ -529,16 +560,20 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
 #undef LIW_SLAB_BLOCK
 #if defined(LIW_SLAB_DIRECT_STORE)
     if (in) {
-        double* out = (psel ? A.PL[1] : A.PL[0]) + ((size_t)bb * n + f) * LP;
-        slab_store<BOTH, 0>(out, acc);
+        double* out = (psel ? A.PL[1] : A.PL[0]) + ((size_t)bb * n + f) * laser_stride(A.pl_compact);
+        if (A.pl_compact) {
+#pragma unroll
+            for (int e = 0; e < LPC; ++e) out[e] = e < NACC ? acc[e < NACC ? e : 0] : 0.0;
+        } else slab_store<BOTH, 0>(out, acc);
     }
 #else
     {
         static_assert(SLAB * STG + SLAB <= 2 * (TF2 - TFR) * SLAB && LP == 128, "staging area of the record epilogue");
         unsigned long long* pw = reinterpret_cast<unsigned long long*>(lds + SLAB * STG);
         lds_sync();                                  // every lane is past its last transform read
-        pw[lane] = in ? (unsigned long long)((psel ? A.PL[1] : A.PL[0]) + ((size_t)bb * n + f) * LP) : 0ull;
-        slab_flush<BOTH, 0>(lds, pw, acc, lane);
+        pw[lane] = in ? (unsigned long long)((psel ? A.PL[1] : A.PL[0]) + ((size_t)bb * n + f) * laser_stride(A.pl_compact)) : 0ull;
+        if (A.pl_compact) slab_flush_compact<NACC>(lds, pw, acc, lane);   // (uniform: the large-batch format stores the pair totals themselves)
+        else slab_flush<BOTH, 0>(lds, pw, acc, lane);
     }
 #endif
     if (in && A.CS[0]) (psel ? A.CS[1] : A.CS[0])[cs_index(n, bb, CS_LASER, f)] = acc[BOTH ? slab_pairidx(8, 8) : slab_pairidx1(5, 5)];

@@ -31,42 +31,9 @@
             frame_tf_record(P, pose6, dir, tf + g * 64 + which * FTF);
         }
     }
-    // slot -> (pair index | 64 if negated), -1 = structural zero, of the 128-slot group record.  Unique-column index of a
-    // pose entry (0..5 = px py pz th0 th1 th2) and its sign:
-    {
-        auto pairidx = [](int c1, int c2) { if (c1 > c2) { const int t = c1; c1 = c2; c2 = t; } return c1 * NC - c1 * (c1 - 1) / 2 + (c2 - c1); };
-        auto col_a = [](int idx) { return idx < 2 ? idx : (idx == 2 ? -1 : idx - 1); };                       // a: x y - th0..2 -> 0 1 - 2 3 4
-        auto col_b = [](int idx) { return BOTH ? (idx < 2 ? idx : (idx == 2 ? -1 : idx + 2)) : (idx == 2 ? -1 : (idx < 2 ? idx : idx - 1)); };
-        auto sgn_b = [](int idx) { return (BOTH && idx < 2) ? -1.0 : 1.0; };
-        constexpr int RC = NC - 1;
+    // slot -> (pair index | 64 if negated), -1 = structural zero, of the 128-slot group record (laser_slot_code, liw_kernels.hpp)
 #pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-            const int s = lane + 64 * qq;
-            int src = -1;
-            double sg = 1.0;
-            if (s < 36) {
-                const int ca = col_a(s / 6), cb = col_a(s % 6);
-                if (BOTH && ca >= 0 && cb >= 0) src = pairidx(ca, cb);
-            } else if (s < 72) {
-                const int ia = (s - 36) / 6, ib = (s - 36) % 6;
-                const int ca = col_b(ia), cb = col_b(ib);
-                if (ca >= 0 && cb >= 0) { src = pairidx(ca, cb); sg = sgn_b(ia) * sgn_b(ib); }
-            } else if (s < 108) {
-                const int ia = (s - 72) / 6, ib = (s - 72) % 6;
-                const int ca = col_a(ia), cb = col_b(ib);
-                if (BOTH && ca >= 0 && cb >= 0) { src = pairidx(ca, cb); sg = sgn_b(ib); }
-            } else if (s < 114) {
-                const int ca = col_a(s - 108);
-                if (BOTH && ca >= 0) src = pairidx(ca, RC);
-            } else if (s < 120) {
-                const int cb = col_b(s - 114);
-                if (cb >= 0) { src = pairidx(cb, RC); sg = sgn_b(s - 114); }
-            } else if (s == 120) {
-                src = pairidx(RC, RC);
-            }
-            slot_src[s] = src < 0 ? -1 : (src | (sg < 0.0 ? 64 : 0));
-        }
-    }
+    for (int qq = 0; qq < 2; ++qq) slot_src[lane + 64 * qq] = laser_slot_code<BOTH>(lane + 64 * qq);
     LSTAMP(0);
     if (lane < i1 - i0) fon_lds[lane] = (A.has_match[b * n + i0 + lane] && (A.mode != LIW_MODE_TRACK || i0 + lane == n - 1 || A.marg_older)) ? 1 : 0;
     if (lane <= i1 - i0) goff[lane] = A.group_off[b * (n + 1) + i0 + lane];
@@ -292,7 +259,7 @@
             LSTAMP(8 + pass_dbg * 8 + 3 + 2 * fl_dbg);
             fl_dbg = fl_dbg < 2 ? fl_dbg + 1 : 2;
             if (more) {
-                double* out = (psel ? A.PL[1] : A.PL[0]) + ((size_t)b * n + cf) * LP;
+                double* out = (psel ? A.PL[1] : A.PL[0]) + ((size_t)b * n + cf) * laser_stride(A.pl_compact);
                 // totals of the NP pair accumulators over the 64 lanes.  Stage 1, in registers: v_permlane32_swap folds the upper
                 // half-wave onto the lower one for TWO accumulators at a time (A' = [A_lo | B_lo], B' = [A_hi | B_hi], A' + B' =
                 // [A's 32 half-sums | B's 32 half-sums]) -> NPK = ceil(NP / 2) packed registers.  Stage 2: ONE transpose through LDS
@@ -325,12 +292,17 @@
                 }
                 lds_sync();
                 (void)NP;
-                // compose the 128-slot record from the pair totals (source pair and sign per slot: table built once per wave)
+                if (A.pl_compact) {
+                    // large-batch format: the pair totals themselves, zeros behind them
+                    if (lane < LPC) out[lane] = lane < NP ? tl[lane] : 0.0;
+                } else {
+                    // compose the 128-slot record from the pair totals (source pair and sign per slot: table built once per wave)
 #pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    const int s = lane + 64 * qq;
-                    const int src = slot_src[s];
-                    out[s] = src < 0 ? 0.0 : (src & 64 ? -tl[src & 63] : tl[src & 63]);
+                    for (int qq = 0; qq < 2; ++qq) {
+                        const int s = lane + 64 * qq;
+                        const int src = slot_src[s];
+                        out[s] = src < 0 ? 0.0 : (src & 64 ? -tl[src & 63] : tl[src & 63]);
+                    }
                 }
 #pragma unroll
                 for (int e = 0; e < NACC; ++e) acc[e] = 0.0;

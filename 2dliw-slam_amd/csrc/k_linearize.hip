@@ -1429,25 +1429,30 @@ void launch_linearize_join(hipStream_t s, const LinFork* fk) {
 
 // ------------------------------------------------------------------------------------------- factor-sharded exchange
 // A laser group record (LP = 128 slots) is a signed expansion of NP pair totals (45 with both poses free, 21 with one): the
-// exchange between ranks moves the NP totals only.  pack: record -> totals (representative slot and sign per total, table built on
-// the host with the same slot map the laser kernel uses); unpack: sum over `world` gathered copies in rank order -> record.
-__global__ void k_exchange_pack(int groups, int n, int np, LaserPackTable tb, const double* PL0, const double* PL1, int candidate, const LmState* lm, double* buf) {
+// exchange between ranks moves the NP totals only.  pack: record -> totals (128-slot records: representative slot and sign per total,
+// table built on the host from laser_slot_code; compact records of the large-batch format hold the totals themselves: a plain copy);
+// unpack: sum over `world` gathered copies in rank order -> record.
+__global__ void k_exchange_pack(int groups, int n, int np, int compact, LaserPackTable tb, const double* PL0, const double* PL1, int candidate, const LmState* lm, double* buf) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= groups * np) return;
     const int grp = t / np, p = t % np;
     const bool dead = lm && lm[grp / n].done;   // finished windows are not re-linearised: their stale sums must not accumulate
     const int sel = lm ? (candidate ? 1 - lm[grp / n].cur : lm[grp / n].cur) : 0;
-    const double v = (sel ? PL1 : PL0)[(size_t)grp * LP + tb.slot[p]];
-    buf[t] = dead ? 0.0 : (tb.neg[p] ? -v : v);
+    const double* PL = sel ? PL1 : PL0;
+    double v;
+    if (compact) v = PL[(size_t)grp * LPC + p];
+    else { v = PL[(size_t)grp * LP + tb.slot[p]]; v = tb.neg[p] ? -v : v; }
+    buf[t] = dead ? 0.0 : v;
 }
 template <bool BOTH>
-__global__ void k_exchange_unpack(int groups, int n, int np, int world, size_t stride, const double* buf, double* PL0, double* PL1, double* CS0, double* CS1, int candidate, const LmState* lm, int sysload) {
+__global__ void k_exchange_unpack(int groups, int n, int np, int compact, int world, size_t stride, const double* buf, double* PL0, double* PL1, double* CS0, double* CS1, int candidate, const LmState* lm, int sysload) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= groups * LP) return;
-    const int grp = t / LP, s = t % LP;
+    const int lps = laser_stride(compact);
+    if (t >= groups * lps) return;
+    const int grp = t / lps, s = t % lps;
     const int sel = lm ? (candidate ? 1 - lm[grp / n].cur : lm[grp / n].cur) : 0;
     double* PL = sel ? PL1 : PL0;
-    const int code = laser_slot_code<BOTH>(s);
+    const int code = compact ? (s < np ? s : -1) : laser_slot_code<BOTH>(s);   // compact: slot s IS pair total s, zeros behind the totals
     double v = 0.0;
     if (code >= 0) {
         const double* src = buf + (size_t)grp * np + (code & 63);
@@ -1461,7 +1466,20 @@ __global__ void k_exchange_unpack(int groups, int n, int np, int world, size_t s
     // the compact cost array of the large-batch format (liw_kernels.hpp, cs_index) holds the record's sum r^2 a second time: the prologue of
     // k_lm_step_quad reads ONLY that copy, so it has to carry the cross-rank total like the record does (else every rank would accept or
     // reject on its own shard's laser cost and the ranks would part ways)
-    if (s == 120 && CS0) (sel ? CS1 : CS0)[cs_index(n, grp / n, CS_LASER, grp % n)] = v;
+    if (s == (compact ? np - 1 : 120) && CS0) (sel ? CS1 : CS0)[cs_index(n, grp / n, CS_LASER, grp % n)] = v;   // (the last pair total is sum r^2)
+}
+// records of either format -> 128-slot records (what a caller that inspects the records reads: 2dliw-slam_amd/batch.py)
+template <bool BOTH>
+__global__ void k_laser_expand(int groups, int compact, const double* PL, double* out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)groups * LP) return;
+    out[t] = laser_slot<BOTH>(PL + (t / LP) * laser_stride(compact), (int)(t % LP), compact);
+}
+void launch_laser_expand(int B, int n, bool both, int compact, const double* PL, double* out, hipStream_t s) {
+    const int groups = B * n;
+    const unsigned blocks = (unsigned)(((size_t)groups * LP + 255) / 256);
+    if (both) hipLaunchKernelGGL(k_laser_expand<true>, dim3(blocks), dim3(256), 0, s, groups, compact, PL, out);
+    else hipLaunchKernelGGL(k_laser_expand<false>, dim3(blocks), dim3(256), 0, s, groups, compact, PL, out);
 }
 __global__ void k_count_active(int B, const LmState* lm, double* out) {
     __shared__ int cnt;
@@ -1473,7 +1491,7 @@ __global__ void k_count_active(int B, const LmState* lm, double* out) {
     __syncthreads();
     if (threadIdx.x == 0) out[0] = (double)cnt;
 }
-void launch_exchange_pack(int B, int n, bool both, const double* PL0, const double* PL1, int candidate, const LmState* lm, double* buf, hipStream_t s) {
+void launch_exchange_pack(int B, int n, bool both, int compact, const double* PL0, const double* PL1, int candidate, const LmState* lm, double* buf, hipStream_t s) {
     const int np = both ? 45 : 21, groups = B * n;
     LaserPackTable tb{};
     for (int p = 0; p < np; ++p) tb.slot[p] = -1;
@@ -1481,13 +1499,13 @@ void launch_exchange_pack(int B, int n, bool both, const double* PL0, const doub
         const int code = both ? laser_slot_code<true>(sl) : laser_slot_code<false>(sl);
         if (code >= 0 && tb.slot[code & 63] < 0) { tb.slot[code & 63] = sl; tb.neg[code & 63] = (code & 64) ? 1 : 0; }
     }
-    hipLaunchKernelGGL(k_exchange_pack, dim3((groups * np + 255) / 256), dim3(256), 0, s, groups, n, np, tb, PL0, PL1, candidate, lm, buf);
+    hipLaunchKernelGGL(k_exchange_pack, dim3((groups * np + 255) / 256), dim3(256), 0, s, groups, n, np, compact, tb, PL0, PL1, candidate, lm, buf);
     if (lm) hipLaunchKernelGGL(k_count_active, dim3(1), dim3(256), 0, s, B, lm, buf + (size_t)groups * np);
 }
-void launch_exchange_unpack(int B, int n, bool both, int world, size_t stride, const double* buf, double* PL0, double* PL1, double* CS0, double* CS1, int candidate, const LmState* lm, hipStream_t s, bool sysload) {
-    const int np = both ? 45 : 21, groups = B * n;
-    if (both) hipLaunchKernelGGL(k_exchange_unpack<true>, dim3((groups * LP + 255) / 256), dim3(256), 0, s, groups, n, np, world, stride, buf, PL0, PL1, CS0, CS1, candidate, lm, sysload ? 1 : 0);
-    else hipLaunchKernelGGL(k_exchange_unpack<false>, dim3((groups * LP + 255) / 256), dim3(256), 0, s, groups, n, np, world, stride, buf, PL0, PL1, CS0, CS1, candidate, lm, sysload ? 1 : 0);
+void launch_exchange_unpack(int B, int n, bool both, int compact, int world, size_t stride, const double* buf, double* PL0, double* PL1, double* CS0, double* CS1, int candidate, const LmState* lm, hipStream_t s, bool sysload) {
+    const int np = both ? 45 : 21, groups = B * n, lps = laser_stride(compact);
+    if (both) hipLaunchKernelGGL(k_exchange_unpack<true>, dim3((groups * lps + 255) / 256), dim3(256), 0, s, groups, n, np, compact, world, stride, buf, PL0, PL1, CS0, CS1, candidate, lm, sysload ? 1 : 0);
+    else hipLaunchKernelGGL(k_exchange_unpack<false>, dim3((groups * lps + 255) / 256), dim3(256), 0, s, groups, n, np, compact, world, stride, buf, PL0, PL1, CS0, CS1, candidate, lm, sysload ? 1 : 0);
 }
 
 // ---- native one-shot exchange: instead of an all-gather collective every rank WRITES its packed record

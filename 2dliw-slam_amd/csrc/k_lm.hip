@@ -48,6 +48,7 @@ __device__ long long g_span[3 * 16384];   // per window: start, end (s_memtime),
 struct AsmCtx {
     int n, mode, fast, b, buf;
     int pif;                  // 1: PI holds per-frame IMU records (PIF_*, liw_kernels.hpp), 0: per-block records (PI_*)
+    int plc;                  // 1: PL holds compact laser group records (LPC pair totals, WsView::pl_compact), 0: 128-slot records
     const double* PL; const double* PI; const double* PW; const double* PG;   // of window b already offset? no: batch base
     const double* x;          // states the partials were evaluated at, window base [n][15]
     const double* pJ; const double* pX; bool prior_on;
@@ -60,6 +61,10 @@ __device__ __forceinline__ double prior_r(const AsmCtx& c, int k) {
     for (int j = 0; j < 15; ++j) s += c.pJ[k * 15 + j] * (xs[j] - c.pX[j]);
     return s;
 }
+
+// slot s of the 128-slot laser group record at `rec`, whichever format the workspace holds (compact: the pair total behind the slot, its
+// sign bit flipped where the expansion negates, +0 for a structural zero: laser_slot_code)
+__device__ __forceinline__ double pl_slot(const AsmCtx& c, const double* rec, int s) { return laser_slot(rec, s, c.plc, c.mode == LIW_MODE_INIT); }
 
 // Assemble frame i's blocks (ambient -> tangent, constants masked), UNSCALED, into 16x16 LDS tiles (ld 16):
 //   Dm = H[i,i], Om = H[i-1,i] (rows: frame i-1), Rm rows 0..5 = H[0(pose), i] (init arrow, i >= 2), gv = g_i.
@@ -110,7 +115,8 @@ constexpr int ASM_TMP = 16;                 // asm_commit scratch: r_prior
 __device__ __forceinline__ AsmRegs asm_issue(const AsmCtx& c, int i, const double* scl, const double* dgl, int lane = threadIdx.x & 63, int dir = -1) {
     const int n = c.n;
     const bool up = dir > 0;
-    const double* PLb = c.PL + (size_t)c.b * n * LP;
+    const int LPS = laser_stride(c.plc);
+    const double* PLb = c.PL + (size_t)c.b * n * LPS;
     const bool pif = c.pif != 0;
     const bool hasm = i >= 1, hasp = i <= n - 2;
     // per-block records: PIm = block (i-1, i), PIp = block (i, i+1).  Per-frame records: PIm = frame i's record (diagonal tile complete,
@@ -125,8 +131,8 @@ __device__ __forceinline__ AsmRegs asm_issue(const AsmCtx& c, int i, const doubl
     const double* PWp = PWb + (size_t)(hasp ? i : 0) * PWS;
     // frame-level bases are wave-uniform (SGPR pairs), the lane-dependent part of every address is an unsigned 32-bit element offset:
     // global_load with scalar base + vector offset instead of a 64-bit vector address per load (148 of the kernel's 236 loads)
-    const double* PLi = PLb + (size_t)i * LP;
-    const double* PL1 = PLb + (size_t)(n > 1 ? 1 : 0) * LP;
+    const double* PLi = PLb + (size_t)i * LPS;
+    const double* PL1 = PLb + (size_t)(n > 1 ? 1 : 0) * LPS;
     const double* PGi = PGb + (size_t)i * PGS;
     AsmRegs R;
 #pragma unroll
@@ -142,18 +148,18 @@ __device__ __forceinline__ AsmRegs asm_issue(const AsmCtx& c, int i, const doubl
     {   // the 6x6 pose block terms: one element per lane (lanes 0..35)
         const bool pl = lane < 36;
         const int r = pl ? lane / 6 : 0, cc = pl ? lane % 6 : 0;
-        R.t1 = PLi[(unsigned)(36 + r * 6 + cc)];
+        R.t1 = pl_slot(c, PLi, 36 + r * 6 + cc);
         R.t2 = PWm[(unsigned)PW_JJ(r, cc)];
         R.t3 = PWp[(unsigned)PW_II(r, cc)];
         R.t4 = PGi[(unsigned)PG_H(r, cc)];
         R.t8 = up ? PWp[(unsigned)PW_IJ(cc, r)] : PWm[(unsigned)PW_IJ(r, cc)];
         R.e2 = up ? PWm[(unsigned)PW_IJ(r, cc)] : 0.0;
-        R.t9 = PL1[(unsigned)(72 + r * 6 + cc)];
-        R.t10 = PLi[(unsigned)(72 + r * 6 + cc)];
+        R.t9 = pl_slot(c, PL1, 72 + r * 6 + cc);
+        R.t10 = pl_slot(c, PLi, 72 + r * 6 + cc);
     }
     {
         const int r = lane < 15 ? lane : 0, r6 = r < 6 ? r : 0;
-        R.g1 = PLi[(unsigned)(114 + r6)];
+        R.g1 = pl_slot(c, PLi, 114 + r6);
         R.g2 = PWm[(unsigned)PW_G(6 + r6)];
         R.g3 = PWp[(unsigned)PW_G(r6)];
         R.g4 = PGi[(unsigned)PG_G(r6)];
@@ -185,7 +191,8 @@ template <int LAYOUT>
 __device__ void asm_commit(const AsmCtx& c, int i, const AsmRegs& R, const Tiles<LAYOUT>& T_, double* tmp, FrameExtra* ex = nullptr,
                            int lane = threadIdx.x & 63, int dir = -1, const PriorRegs* pr = nullptr) {
     const int n = c.n;
-    const double* PLb = c.PL + (size_t)c.b * n * LP;
+    const int LPS = laser_stride(c.plc);
+    const double* PLb = c.PL + (size_t)c.b * n * LPS;
     const bool hasm = i >= 1, hasp = i <= n - 2;
     const bool up = dir > 0, hasnb = up ? hasp : hasm;
     const int nbf = up ? (hasp ? i + 1 : i) : (hasm ? i - 1 : i);
@@ -237,10 +244,10 @@ __device__ void asm_commit(const AsmCtx& c, int i, const AsmRegs& R, const Tiles
             double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
             int j = 0;
             for (; j + 4 <= n; j += 4) {
-                s0 += PLb[(size_t)j * LP + r * 6 + cc]; s1 += PLb[(size_t)(j + 1) * LP + r * 6 + cc];
-                s2 += PLb[(size_t)(j + 2) * LP + r * 6 + cc]; s3 += PLb[(size_t)(j + 3) * LP + r * 6 + cc];
+                s0 += pl_slot(c, PLb + (size_t)j * LPS, r * 6 + cc); s1 += pl_slot(c, PLb + (size_t)(j + 1) * LPS, r * 6 + cc);
+                s2 += pl_slot(c, PLb + (size_t)(j + 2) * LPS, r * 6 + cc); s3 += pl_slot(c, PLb + (size_t)(j + 3) * LPS, r * 6 + cc);
             }
-            for (; j < n; ++j) s0 += PLb[(size_t)j * LP + r * 6 + cc];
+            for (; j < n; ++j) s0 += pl_slot(c, PLb + (size_t)j * LPS, r * 6 + cc);
             dP += (s0 + s1) + (s2 + s3);
         }
         oP = hasnb ? R.t8 + ((!up && i == 1) ? R.t9 : 0.0) : 0.0;
@@ -256,10 +263,10 @@ __device__ void asm_commit(const AsmCtx& c, int i, const AsmRegs& R, const Tiles
                 double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
                 int j = 0;
                 for (; j + 4 <= n; j += 4) {
-                    s0 += PLb[(size_t)j * LP + 108 + r]; s1 += PLb[(size_t)(j + 1) * LP + 108 + r];
-                    s2 += PLb[(size_t)(j + 2) * LP + 108 + r]; s3 += PLb[(size_t)(j + 3) * LP + 108 + r];
+                    s0 += pl_slot(c, PLb + (size_t)j * LPS, 108 + r); s1 += pl_slot(c, PLb + (size_t)(j + 1) * LPS, 108 + r);
+                    s2 += pl_slot(c, PLb + (size_t)(j + 2) * LPS, 108 + r); s3 += pl_slot(c, PLb + (size_t)(j + 3) * LPS, 108 + r);
                 }
-                for (; j < n; ++j) s0 += PLb[(size_t)j * LP + 108 + r];
+                for (; j < n; ++j) s0 += pl_slot(c, PLb + (size_t)j * LPS, 108 + r);
                 gg += (s0 + s1) + (s2 + s3);
             }
         }
@@ -370,7 +377,8 @@ __device__ void assemble_frame(const AsmCtx& c, int i, const Tiles<LAYOUT>& T_, 
 __device__ double window_cost(const AsmCtx& c, double* gchk = nullptr) {
     const int lane = threadIdx.x & 63;
     const int n = c.n;
-    const double* PLb = c.PL + (size_t)c.b * n * LP;
+    const int LPS = laser_stride(c.plc);
+    const double* PLb = c.PL + (size_t)c.b * n * LPS;
     const bool pif = c.pif != 0;
     const double* PIb = c.PI + (size_t)c.b * (pif ? (size_t)n * PIFS : (size_t)(n - 1) * PIS);
     const double* PWb = c.PW + (size_t)c.b * (n - 1) * PWS;
@@ -381,12 +389,12 @@ __device__ double window_cost(const AsmCtx& c, double* gchk = nullptr) {
         // (tracking: only the newest frame has laser / ground blocks with a free parameter.  The older frames' laser records are zero —
         //  or, LinArgs::marg_older, hold their marginalisation-topology sums, which are no part of the tracking problem)
         const bool gon = !(track && i < n - 1);
-        if (gon) s += PLb[(size_t)i * LP + 120];
+        if (gon) s += pl_slot(c, PLb + (size_t)i * LPS, 120);
         if (gon) s += PGb[(size_t)i * PGS + PG_C];
         if (gchk) {
             if (gon) {
 #pragma unroll
-                for (int k = 0; k < 12; ++k) gs += PLb[(size_t)i * LP + 108 + k];
+                for (int k = 0; k < 12; ++k) gs += pl_slot(c, PLb + (size_t)i * LPS, 108 + k);
             }
             if (gon) {
 #pragma unroll
@@ -521,14 +529,15 @@ __device__ double frame_diag(const AsmCtx& c, int i, LdsStep& T) {
     }
     if (lane >= 15) return 0.0;
     const int r = lane;
-    const double* PLb = c.PL + (size_t)c.b * n * LP;
+    const int LPS = laser_stride(c.plc);
+    const double* PLb = c.PL + (size_t)c.b * n * LPS;
     const double* PIb = c.PI + (size_t)c.b * (c.pif ? (size_t)n * PIFS : (size_t)(n - 1) * PIS);
     const double* PWb = c.PW + (size_t)c.b * (n - 1) * PWS;
     const double* PGb = c.PG + (size_t)c.b * n * PGS;
     double d = 0.0;
     if (r < 6) {
-        d += PLb[(size_t)i * LP + 36 + r * 7];
-        if (i == 0) for (int j = 0; j < n; ++j) d += PLb[(size_t)j * LP + r * 7];
+        d += pl_slot(c, PLb + (size_t)i * LPS, 36 + r * 7);
+        if (i == 0) for (int j = 0; j < n; ++j) d += pl_slot(c, PLb + (size_t)j * LPS, r * 7);
         if (i >= 1) d += PWb[(size_t)(i - 1) * PWS + PW_JJ(r, r)];
         if (i <= n - 2) d += PWb[(size_t)i * PWS + PW_II(r, r)];
         d += PGb[(size_t)i * PGS + PG_H(r, r)];
@@ -565,7 +574,7 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
         double v[14];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            v[4 * k + 0] = touch_lines(a.w.PL[k] + (size_t)b * n2 * LP, sizeof(double) * n2 * LP);
+            v[4 * k + 0] = touch_lines(a.w.PL[k] + (size_t)b * n2 * laser_stride(a.w.pl_compact), sizeof(double) * n2 * laser_stride(a.w.pl_compact));
             v[4 * k + 1] = touch_lines(a.w.PI[k] + (size_t)b * (n2 - 1) * PIS, sizeof(double) * (n2 - 1) * PIS);
             v[4 * k + 2] = touch_lines(a.w.PW[k] + (size_t)b * (n2 - 1) * PWS, sizeof(double) * (n2 - 1) * PWS);
             v[4 * k + 3] = touch_lines(a.w.PG[k] + (size_t)b * n2 * PGS, sizeof(double) * n2 * PGS);
@@ -600,6 +609,7 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
 
     AsmCtx c;
     c.pif = a.w.pi_frame;
+    c.plc = a.w.pl_compact;
     c.n = n; c.mode = a.mode; c.fast = a.fast_mode; c.b = b;
     c.pJ = a.prior_J + (size_t)b * 225; c.pX = a.prior_X + (size_t)b * 15;
     c.prior_on = a.mode == LIW_MODE_TRACK && a.has_prior[b] && !a.fast_mode;
@@ -1182,6 +1192,7 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
 
     AsmCtx c;
     c.pif = a.w.pi_frame;
+    c.plc = a.w.pl_compact;
     c.n = n; c.mode = a.mode; c.fast = a.fast_mode; c.b = b;
     c.pJ = a.prior_J + (size_t)b * 225; c.pX = a.prior_X + (size_t)b * 15;
     c.prior_on = a.mode == LIW_MODE_TRACK && a.has_prior[b] && !a.fast_mode;
@@ -1681,6 +1692,7 @@ __global__ __launch_bounds__(64) void k_export_dense(ExportArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x & 63, n = a.n, N = 15 * n;
     AsmCtx c;
     c.pif = a.w.pi_frame;
+    c.plc = a.w.pl_compact;
     c.n = n; c.mode = a.mode; c.fast = a.fast_mode; c.b = b; c.buf = a.buf;
     c.PL = a.w.PL[0]; c.PI = a.w.PI[0]; c.PW = a.w.PW[0]; c.PG = a.w.PG[0];   // standalone linearise writes buffer 0
     c.x = a.x + (size_t)b * n * 15;
@@ -1717,6 +1729,7 @@ __device__ __forceinline__ bool marg_chain(const MargArgs& a, const int b, TILES
     const int lane = threadIdx.x & 63, n = a.n;
     AsmCtx c;
     c.pif = a.w.pi_frame;
+    c.plc = a.w.pl_compact;
     const int sel = a.use_cur ? __builtin_amdgcn_readfirstlane(a.w.lm[b].cur) : 0;
     c.n = n; c.mode = LIW_MODE_MARG; c.fast = 0; c.b = b; c.buf = sel;
     c.PL = sel ? a.w.PL[1] : a.w.PL[0]; c.PI = sel ? a.w.PI[1] : a.w.PI[0]; c.PW = sel ? a.w.PW[1] : a.w.PW[0]; c.PG = sel ? a.w.PG[1] : a.w.PG[0];

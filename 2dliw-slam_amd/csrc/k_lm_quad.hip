@@ -76,11 +76,50 @@ constexpr int QNT1 = (LIW_NT_MASK & 16) ? 2 : 0, QNT2 = (LIW_NT_MASK & 64) ? 2 :
 constexpr int QTR = 4 * 15 * 6;                           // transposition tile of the carried arrow block (below)
 #endif
 // Gather table of the assembly phase: one 16-bit LDS byte offset per (read, lane) — see the kernel.  Reads: K_A laser Hbb | gb, K_B wheel
-// jj | g_j, K_C ground H | g, K_HA laser Haa | ga, K_D IMU diagonal tile, K_CW wheel ii | g_i, K_GSH wheel g_i lane per entry.
-constexpr int K_A = 0, K_B = 6, K_C = 12, K_HA = 18, K_D = 24, K_CW = 39, K_GSH = 45, NRD = 46;
+// jj | g_j, K_C ground H | g, K_HA laser Haa | ga, K_D IMU diagonal tile, K_CW wheel ii | g_i, K_GSH wheel g_i lane per entry, K_RL laser Hab.
+constexpr int K_A = 0, K_B = 6, K_C = 12, K_HA = 18, K_D = 24, K_CW = 39, K_GSH = 45, K_RL = 46, NRD = 52;
 constexpr int QTAB = NRD * 16;                            // doubles: NRD x 64 unsigned shorts
 constexpr int QZB = 86;                                  // a block of zeros: lanes that take no part in a strided read
-constexpr int QTOT_1 = 4 * (PIFS + LP + PWS + PGS) + 32 + QTR + QZB + QTAB;   // first sweep
+constexpr int QPAD = 96;                                 // behind the staged records: the over-read of the last piece of a frame's laser | wheel | ground stream
+constexpr int QTOT_1 = 4 * (PIFS + LPC + PWS + PGS) + QPAD + QTR + QZB + QTAB;   // first sweep
+// The laser group records this kernel reads are COMPACT (LPC pair totals, liw_kernels.hpp): the slot of the 128-slot record a laser read
+// (kind 0: K_A Hbb | gb, 1: K_HA Haa | ga, 2: K_RL Hab; row r; lane role j < 6 = block column / row, 15 = gradient) stands for, which
+// laser_slot_code turns into (pair total, negate) or "structural zero".
+constexpr int quad_laser_slot(int kind, int r, int j) {
+    return kind == 0 ? (j == 15 ? 114 + r : 36 + r * 6 + j) : kind == 1 ? (j == 15 ? 108 + r : r * 6 + j) : 72 + j * 6 + r;
+}
+// Where the expansion negates, the lane flips the sign bit of what it read.  The (read, lane) sign pattern has THREE distinct rows — the
+// kernel keeps one mask register for each: rows 0, 1 of K_A, rows 3 .. 5 of K_A, rows 0, 1 of K_RL; every other laser read is unsigned.
+template <bool BOTH> constexpr bool quad_sign_rows_ok() {
+    for (int jj = 0; jj < 7; ++jj) {
+        const int j = jj < 6 ? jj : 15;
+        auto sg = [&](int kind, int r) { const int c = laser_slot_code<BOTH>(quad_laser_slot(kind, r, j)); return c >= 0 && (c & 64) != 0; };
+        for (int r = 0; r < 6; ++r) {
+            if (sg(1, r)) return false;
+            if (sg(0, r) != (r < 2 ? sg(0, 0) : (r > 2 && sg(0, 3)))) return false;
+            if (j < 6 && sg(2, r) != (r < 2 && sg(2, 0))) return false;
+        }
+        if (sg(0, 0) != sg(0, 1) || (j < 6 && sg(2, 0) != sg(2, 1))) return false;
+    }
+    return true;
+}
+static_assert(quad_sign_rows_ok<true>() && quad_sign_rows_ok<false>(), "sign rows of the laser reads");
+// laser_slot_code of read (kind, r) for the seven lane roles (j = 0 .. 5, then 15), one byte each (0xff: structural zero, or no part in the
+// read), packed into a compile-time 64-bit constant: the per-launch table build costs a shift and a mask per read, not the slot arithmetic
+template <bool BOTH> constexpr unsigned long long quad_code_pack(int kind, int r) {
+    unsigned long long v = 0;
+    for (int jj = 0; jj < 7; ++jj) {
+        const int c = (kind == 2 && jj == 6) ? -1 : laser_slot_code<BOTH>(quad_laser_slot(kind, r, jj < 6 ? jj : 15));
+        v |= (unsigned long long)(c < 0 ? 0xff : c) << (8 * jj);
+    }
+    return v;
+}
+template <int KIND, int R> __device__ __forceinline__ int quad_code(bool track, int role) {   // role: 0 .. 5 = j, 6 = lane 15; -1 = structural zero
+    constexpr unsigned long long both = quad_code_pack<true>(KIND, R), one = quad_code_pack<false>(KIND, R);
+    const int c = (int)(((track ? one : both) >> (8 * role)) & 0xffull);
+    return c == 0xff ? -1 : c;
+}
+__device__ __forceinline__ double flip_sign(double x, unsigned m) { return __hiloint2double(__double2hiint(x) ^ (int)m, __double2loint(x)); }   // m: 0x80000000 or 0
 #ifndef LIW_QUAD_BSD
 #define LIW_QUAD_BSD 3   // frames of second-sweep records in flight (2: 30 kB of LDS per wave instead of 38 — co-residency experiments)
 #endif
@@ -258,7 +297,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     const double* const PW0 = a.w.PW[0];
     const double* const PG0 = a.w.PG[0];
     const unsigned bp = (g_qprobe & 1) ? 0u : (unsigned)b;
-    const unsigned oPL = bp * (unsigned)(n * LP) + (cur ? (unsigned)(a.w.PL[1] - a.w.PL[0]) : 0u);
+    const unsigned oPL = bp * (unsigned)(n * LPC) + (cur ? (unsigned)(a.w.PL[1] - a.w.PL[0]) : 0u);
     const unsigned oPI = bp * (unsigned)(n * PIFS) + (cur ? (unsigned)(a.w.PI[1] - a.w.PI[0]) : 0u);
     const unsigned oPW = bp * (unsigned)((n - 1) * PWS) + (cur ? (unsigned)(a.w.PW[1] - a.w.PW[0]) : 0u);
     const unsigned oPG = bp * (unsigned)(n * PGS) + (cur ? (unsigned)(a.w.PG[1] - a.w.PG[0]) : 0u);
@@ -277,13 +316,17 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
         // terms that do not apply are dropped by selects; every sum keeps its terms and their order.
         double sp = 0.0;
         if (prior_row) for (int k = 0; k < 15; ++k) { const double v = a.prior_J[(size_t)b * 225 + k * 15 + jc]; sp += v * v; }
+        // (compact laser records: the pair totals behind the diagonal slots of Hbb / Haa — never negated — or a structural zero)
+        const int cbb = track ? laser_slot_code<false>(36 + (l6 ? jc : 0) * 7) : laser_slot_code<true>(36 + (l6 ? jc : 0) * 7);
+        const int caa = track ? laser_slot_code<false>((l6 ? jc : 0) * 7) : laser_slot_code<true>((l6 ? jc : 0) * 7);
         for (int i0 = 0; i0 < n; i0 += 4) {
             double vbb[4], vjj[4], vii[4], vg[4], vi[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = min(i0 + u, n - 1);
                 const int j6 = l6 ? jc : 0;          // pose entry of the 6 x 6 / 7 x 7 records (the loads of the other lanes are dropped below: any valid offset)
-                vbb[u] = PL0[oPL + (unsigned)(i * LP + 36 + j6 * 7)];
+                vbb[u] = PL0[oPL + (unsigned)(i * LPC + (cbb >= 0 ? cbb & 63 : 0))];
+                vbb[u] = cbb >= 0 ? vbb[u] : 0.0;
                 vjj[u] = n > 1 ? PW0[oPW + (unsigned)(max(i - 1, 0) * PWS + PW_JJ(j6, j6))] : 0.0;         // (n == 1: no wheel block at all)
                 vii[u] = n > 1 ? PW0[oPW + (unsigned)(min(i, n - 2) * PWS + PW_II(j6, j6))] : 0.0;
                 vg[u] = PG0[oPG + (unsigned)(i * PGS + PG_H(j6, j6))];
@@ -296,7 +339,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
                 double dd = 0.0;
                 if (l6) {
                     dd += vbb[u];
-                    if (i == 0) for (int f = 0; f < n; ++f) dd += PL0[oPL + (unsigned)(f * LP + jc * 7)];   // frame 0's pose: the H_aa diagonals of every laser group, in group order
+                    if (i == 0) for (int f = 0; f < n; ++f) { const double va = PL0[oPL + (unsigned)(f * LPC + (caa >= 0 ? caa & 63 : 0))]; dd += caa >= 0 ? va : 0.0; }   // frame 0's pose: the H_aa diagonals of every laser group, in group order
                     if (i >= 1) dd += vjj[u];
                     if (i <= n - 2) dd += vii[u];
                     dd += vg[u];
@@ -313,9 +356,9 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     // (global_load_lds: no VGPRs, no waits; LDS destination = uniform base + lane * 16 bytes, so every instruction fills a lane-linear
     // piece of one row's area), the Jacobi scale / LM diagonal / state entry of this lane in three registers.
     //   S_IMU[w][376]  per-frame IMU record of frame f           3 pieces per row
-    //   S_PL[w][128]   laser group record of frame f             1 piece per row (the whole record: Haa / ga feed the hub accumulators)
-    //   S_PW[w][92]    wheel partial of block (f-1, f)           1 piece per row (46 lanes)
-    //   S_PG[w][28]    ground partial of frame f                 1 piece for the four rows (14 lanes each)
+    //   S_PL[w][48]    compact laser group record of frame f     }
+    //   S_PW[w][92]    wheel partial of block (f-1, f)           } back to back: ONE lane-linear stream of 672 doubles, cut every 128: 6 pieces
+    //   S_PG[w][28]    ground partial of frame f                 }   (18 pieces per frame; 20 with the 128-slot laser record, one piece per row)
     // Round 4 measured what the staging costs and what does NOT change it (tools/quad_occ_probe2.sh, tools/quad_probe.py,
     // tools/clk_probe_quad.py): issuing a frame's 26 pieces (21 since the packed wheel / ground records) stalls the wave for ~4 k of its ~18.6 k cycles; with two waves per SIMD (a
     // <= 256-register build, six waves per CU) the SAME phase takes 5 - 11 k per wave and the kernel is no faster — the other phases keep
@@ -325,13 +368,14 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     // (4.9 TB/s chip-wide during the sweep) — and whoever issues next waits for a slot.  Probes with the records aliased to one window
     // (cache-resident) bound the memory share of the kernel at 21 %; the rest is the instruction stream.  The DMA form stays: it needs
     // no registers.
-    constexpr int S_IMU = 0, S_PL = 4 * PIFS, S_PW = S_PL + 4 * LP, S_PG = S_PW + 4 * PWS, S_TR = S_PG + 4 * PGS + 32;   // (32 doubles of pad: the over-read of the last piece)
+    constexpr int S_IMU = 0, S_PL = 4 * PIFS, S_PW = S_PL + 4 * LPC, S_PG = S_PW + 4 * PWS, S_TR = S_PG + 4 * PGS + QPAD;   // (QPAD doubles of pad: the over-read of the last piece)
     constexpr int S_ZERO = S_TR + QTR, S_TAB = S_ZERO + QZB;
     static_assert(S_TAB + QTAB <= QTOT && 8 * QTOT < 65536, "LDS layout");
-    const unsigned rPL[4] = {(unsigned)__builtin_amdgcn_readlane(oPL, 0), (unsigned)__builtin_amdgcn_readlane(oPL, 16), (unsigned)__builtin_amdgcn_readlane(oPL, 32), (unsigned)__builtin_amdgcn_readlane(oPL, 48)};
     const unsigned rPI[4] = {(unsigned)__builtin_amdgcn_readlane(oPI, 0), (unsigned)__builtin_amdgcn_readlane(oPI, 16), (unsigned)__builtin_amdgcn_readlane(oPI, 32), (unsigned)__builtin_amdgcn_readlane(oPI, 48)};
     const unsigned rPW[4] = {(unsigned)__builtin_amdgcn_readlane(oPW, 0), (unsigned)__builtin_amdgcn_readlane(oPW, 16), (unsigned)__builtin_amdgcn_readlane(oPW, 32), (unsigned)__builtin_amdgcn_readlane(oPW, 48)};
     const unsigned oPGw = oPG + (unsigned)(PG0 - PW0);   // ground records relative to the wheel buffer (launch_lm_step_quad checks the span): one base pointer per piece
+    const unsigned oPLw = oPL + (unsigned)(PL0 - PW0);   // laser records relative to the wheel buffer as well (the workspace keeps them between the wheel and the ground buffers)
+    const unsigned rPLw[4] = {(unsigned)__builtin_amdgcn_readlane(oPLw, 0), (unsigned)__builtin_amdgcn_readlane(oPLw, 16), (unsigned)__builtin_amdgcn_readlane(oPLw, 32), (unsigned)__builtin_amdgcn_readlane(oPLw, 48)};
     const unsigned rPGw[4] = {(unsigned)__builtin_amdgcn_readlane(oPGw, 0), (unsigned)__builtin_amdgcn_readlane(oPGw, 16), (unsigned)__builtin_amdgcn_readlane(oPGw, 32), (unsigned)__builtin_amdgcn_readlane(oPGw, 48)};
     typedef __attribute__((address_space(3))) void* lds_t;
     const int j_ = j;
@@ -362,29 +406,28 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
                 sfor<0, 3>([&](auto Q) { __builtin_amdgcn_global_load_lds(g, (lds_t)(S + S_IMU + ws * PIFS), 16, KI(Q) * 1024, QNT1); });
             });
         }
-        sfor<0, 4>([&](auto W) {                    // laser group record: exactly one piece
-            constexpr int ws = KI(W);
-            static_assert(LP == 128, "one piece");
-            __builtin_amdgcn_global_load_lds(PL0 + rPL[ws] + (unsigned)(f * LP) + lane2, (lds_t)(S + S_PL + ws * LP), 16, 0, QNT1);
-        });
-        // wheel partials (block f-1; frame 0 re-reads block 0, unused) and ground partials of the four rows: the 4 x 92 + 4 x 28 doubles that lie
-        // back to back in LDS are cut into 128-double pieces wherever the cuts fall (4 pieces; a piece per wheel record + one for the ground
-        // records was 5): a lane's global address = the base of the record its 16 bytes belong to + its offset inside it; the lanes behind
-        // the last record read on (over-read into the pad)
+        // compact laser group records of the four rows, wheel partials (block f-1; frame 0 re-reads block 0, unused) and ground partials: the
+        // 4 x 48 + 4 x 92 + 4 x 28 doubles that lie back to back in LDS are cut into 128-double pieces wherever the cuts fall (6 pieces; a piece
+        // per 128-slot laser record + 4 for the wheel / ground stream was 8): a lane's global address = the base of the record its 16 bytes belong
+        // to + its offset inside it; the lanes behind the last record read on (over-read into the pad: inside the workspace, the ground buffers are
+        // not its last region)
         {
-            const unsigned fw = (unsigned)((k >= 0 ? k : 0) * PWS), fg = (unsigned)(f * PGS);
-            sfor<0, 4>([&](auto P) {
-                constexpr int q0 = KI(P) * 128;                     // first stream double of this piece (stream = the S_PW .. S_PG areas)
+            const unsigned fl = (unsigned)(f * LPC), fw = (unsigned)((k >= 0 ? k : 0) * PWS), fg = (unsigned)(f * PGS);
+            constexpr int NPC = (4 * (LPC + PWS + PGS) + 127) / 128;
+            static_assert(NPC * 128 - 4 * (LPC + PWS + PGS) <= QPAD && LPC % 2 == 0 && PWS % 2 == 0 && PGS % 2 == 0, "stream pieces: pad, 16-byte slots");
+            sfor<0, NPC>([&](auto P) {
+                constexpr int q0 = KI(P) * 128;                     // first stream double of this piece (stream = the S_PL .. S_PG areas)
                 unsigned off = 0;
-                sfor<0, 8>([&](auto G) {
+                sfor<0, 12>([&](auto G) {
                     constexpr int g = KI(G);
-                    constexpr int st = g < 4 ? g * PWS : 4 * PWS + (g - 4) * PGS, en = g == 7 ? (1 << 20) : st + (g < 4 ? PWS : PGS);
+                    constexpr int st = g < 4 ? g * LPC : g < 8 ? 4 * LPC + (g - 4) * PWS : 4 * (LPC + PWS) + (g - 8) * PGS;
+                    constexpr int en = g == 11 ? (1 << 20) : st + (g < 4 ? LPC : g < 8 ? PWS : PGS);
                     if constexpr (st < q0 + 128 && en > q0) {
-                        const unsigned v = (g < 4 ? rPW[g & 3] + fw : rPGw[g & 3] + fg) + (unsigned)(lane2 - (st - q0));
+                        const unsigned v = (g < 4 ? rPLw[g & 3] + fl : g < 8 ? rPW[g & 3] + fw : rPGw[g & 3] + fg) + (unsigned)(lane2 - (st - q0));
                         if constexpr (st <= q0) off = v; else off = lane2 >= st - q0 ? v : off;
                     }
                 });
-                __builtin_amdgcn_global_load_lds(PW0 + off, (lds_t)(S + S_PW + q0), 16, 0, QNT1);
+                __builtin_amdgcn_global_load_lds(PW0 + off, (lds_t)(S + S_PL + q0), 16, 0, QNT1);
             });
         }
         asm volatile("" ::: "memory");
@@ -402,22 +445,37 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     {
         const int jt = j < 15 ? j : 0, cjt = 14 * jt - (jt * (jt - 1)) / 2, j6t = j < 6 ? j : 0;
         const bool t6 = j < 6, t15 = j == 15, tm = j < 15;
-        const int oL = S_PL + w * LP, oW_ = S_PW + w * PWS, oG = S_PG + w * PGS, oI = S_IMU + w * PIFS;
+        const int oL = S_PL + w * LPC, oW_ = S_PW + w * PWS, oG = S_PG + w * PGS, oI = S_IMU + w * PIFS;
         auto put = [&](int k, bool on, int idx) { TAB[k * 64 + lane] = (unsigned short)(8 * (on ? idx : S_ZERO)); };
+        // a laser read: the pair total behind the slot it stands for, or the zero block for a structural zero (the sign: sgA0 / sgA3 / sgR0 below)
+        const int role = t15 ? 6 : j6t;
+        auto put_laser = [&](int k, bool on, int code) { put(k, on && code >= 0, oL + (code & 63)); };
         for (int e = lane; e < QZB; e += 64) S[S_ZERO + e] = 0.0;
         sfor<0, 6>([&](auto R) {
             constexpr int r = KI(R);
-            put(K_A + r, t6 || t15, oL + (t15 ? 114 + r : 36 + r * 6 + j6t));
+            put_laser(K_A + r, t6 || t15, quad_code<0, r>(track, role));
             put(K_B + r, t6 || t15, oW_ + (t15 ? PW_G(6 + r) : PW_JJ(r, j6t)));
             put(K_C + r, t6 || t15, oG + (t15 ? PG_G(r) : PG_H(r, j6t)));
-            put(K_HA + r, t6 || t15, oL + (t15 ? 108 + r : r * 6 + j6t));
+            put_laser(K_HA + r, t6 || t15, quad_code<1, r>(track, role));
             put(K_CW + r, t6 || t15, oW_ + (t15 ? PW_G(r) : PW_II(r, j6t)));
+            put_laser(K_RL + r, t6, quad_code<2, r>(track, role));
         });
         put(K_GSH, t6, oW_ + PW_G(j6t));
         sfor<0, 15>([&](auto R) {
             constexpr int r = KI(R);
             put(K_D + r, tm, oI + PIF_D + tri_rc<r>(jt, cjt));
         });
+    }
+    // sign masks of the laser reads (quad_sign_rows_ok): sign bit set where the 128-slot record holds the NEGATED pair total — rows 0, 1 of
+    // K_A (Hbb | gb), rows 3 .. 5 of K_A, rows 0, 1 of K_RL (Hab).  Built once per launch; applied with all 64 lanes, in straight-line code.
+    unsigned sgA0, sgA3, sgR0;
+    {
+        const bool t6 = j < 6, t15 = j == 15;
+        const int role = t15 ? 6 : (t6 ? j : 0);
+        const int cA0 = quad_code<0, 0>(track, role), cA3 = quad_code<0, 3>(track, role), cR0 = quad_code<2, 0>(track, role);
+        sgA0 = ((t6 || t15) && cA0 >= 0 && (cA0 & 64)) ? 0x80000000u : 0u;
+        sgA3 = ((t6 || t15) && cA3 >= 0 && (cA3 & 64)) ? 0x80000000u : 0u;
+        sgR0 = (t6 && cR0 >= 0 && (cR0 & 64)) ? 0x80000000u : 0u;
     }
     const int lane_tab = lane * 2;                  // byte offset of the lane's entry inside a table row
     auto RD = [&](auto K) -> double {               // read K of the gather table
@@ -469,15 +527,15 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
         double tS[6], oW[6], rL[6];
         {
             constexpr int NT = K_D - K_A;                // K_A, K_B, K_C, K_HA; K_D behind them
-            unsigned of[NT + 15];
+            unsigned of[NT + 15], ofR[6];
             auto tab_at = [&](int k) { return (unsigned)*reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(TAB) + k * 128 + lane_tab); };
             sfor<0, NT>([&](auto Q) { constexpr int q = KI(Q); of[q] = tab_at(K_A + q); });
+            sfor<0, 6>([&](auto Q) { constexpr int q = KI(Q); ofR[q] = tab_at(K_RL + q); });
             if (n > 1) sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); of[NT + q] = tab_at(K_D + q); });
             const char* const Sb = reinterpret_cast<const char*>(S);
             const int w8 = (lane >> 4) * 8;
             const char* const bOV = Sb + (l15 ? 8 * (S_IMU + PIF_GJ) : 8 * (S_IMU + PIF_IJ) + jc * 120) + w8 * PIFS;
             const char* const bGI = Sb + (l15 ? 8 * (S_IMU + PIF_GI) + w8 * PIFS : 8 * S_ZERO);
-            const char* const bRL = Sb + (l6 ? 8 * (S_PL + 72) + w8 * LP + j6 * 48 : 8 * S_ZERO);
             const char* const bOW = Sb + (l6 ? 8 * (S_PW + PW_IJ(0, 0)) + w8 * PWS + j6 * 48 : 8 * S_ZERO);
             double gi[15];
             if (n > 1) {
@@ -485,12 +543,17 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
             } else {
                 sfor<0, 15>([&](auto R) { constexpr int r = KI(R); d[r] = 0.0; o[r] = 0.0; gi[r] = 0.0; });
             }
-            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); rL[r] = *reinterpret_cast<const double*>(bRL + 8 * r); oW[r] = *reinterpret_cast<const double*>(bOW + 8 * r); });
+            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); oW[r] = *reinterpret_cast<const double*>(bOW + 8 * r); });
             asm volatile("" ::: "memory");
             double pb[NT];
             sfor<0, NT>([&](auto Q) { constexpr int q = KI(Q); pb[q] = *reinterpret_cast<const double*>(Sb + of[q]); });
+            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); rL[r] = *reinterpret_cast<const double*>(Sb + ofR[r]); });
             if (n > 1) sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); d[q] = *reinterpret_cast<const double*>(Sb + of[NT + q]); });
             asm volatile("" ::: "memory");
+            // the 128-slot record's negated entries: the pair total with its sign bit flipped (rows 2 are structural zeros: +0, no flip)
+            pb[K_A + 0] = flip_sign(pb[K_A + 0], sgA0); pb[K_A + 1] = flip_sign(pb[K_A + 1], sgA0);
+            pb[K_A + 3] = flip_sign(pb[K_A + 3], sgA3); pb[K_A + 4] = flip_sign(pb[K_A + 4], sgA3); pb[K_A + 5] = flip_sign(pb[K_A + 5], sgA3);
+            rL[0] = flip_sign(rL[0], sgR0); rL[1] = flip_sign(rL[1], sgR0);
             sfor<0, 6>([&](auto R) { constexpr int r = KI(R); tS[r] = pb[K_A + r] + bits_and(pb[K_B + r], mh) + pb[K_C + r]; });
             if (!track) {   // every laser frame's Haa / ga lands on frame 0's pose (init topology): summed as the frames stream by (until round 4
                             // frame 0 re-read the n records from HBM)
@@ -870,7 +933,9 @@ bool lm_step_quad_fits(const StepArgs& a) {
         return d <= lim && d + (unsigned long long)a.B * per <= lim;
     };
     const int nm = a.n > 1 ? a.n - 1 : 1;
-    return a.n >= 1 && (a.mode == LIW_MODE_INIT || (a.mode == LIW_MODE_TRACK && a.n >= 2)) && span(a.w.PL[0], a.w.PL[1], (unsigned long long)a.n * LP) && a.w.pi_frame && a.w.CS[0] && a.w.CS[1] && span(a.w.PI[0], a.w.PI[1], (unsigned long long)a.n * PIFS) &&
+    return a.n >= 1 && (a.mode == LIW_MODE_INIT || (a.mode == LIW_MODE_TRACK && a.n >= 2)) && span(a.w.PL[0], a.w.PL[1], (unsigned long long)a.n * LPC) && a.w.pi_frame && a.w.pl_compact &&
+           a.w.PL[0] >= a.w.PW[0] && span(a.w.PW[0], a.w.PL[1], (unsigned long long)a.n * LPC) &&   // (the laser records' pieces are addressed from the wheel buffer)
+           a.w.CS[0] && a.w.CS[1] && span(a.w.PI[0], a.w.PI[1], (unsigned long long)a.n * PIFS) &&
            span(a.w.PW[0], a.w.PW[1], (unsigned long long)nm * PWS) && span(a.w.PG[0], a.w.PG[1], (unsigned long long)a.n * PGS) &&
            a.w.PG[0] >= a.w.PW[0] && span(a.w.PW[0], a.w.PG[1], (unsigned long long)a.n * PGS) &&   // (ground records are addressed from the wheel buffer)
            (unsigned long long)a.B * (sizeof(LmState) / 8) <= lim && (unsigned long long)a.B * a.n * SOLVE_WS <= lim;

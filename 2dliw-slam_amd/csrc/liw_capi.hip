@@ -238,9 +238,12 @@ static FullLayout full_layout(int B, int n, int hist) {
     FullLayout f{};
     size_t o = 0;
     const int nm = n > 1 ? n - 1 : 1;
-    for (int k = 0; k < 2; ++k) { f.PL[k] = o; o = al256(o + sizeof(double) * (size_t)B * n * LP); }
+    const int lps = laser_stride(pi_frame_format(B) ? 1 : 0);   // the large-batch format keeps compact laser group records (LPC pair totals)
     for (int k = 0; k < 2; ++k) { f.PI[k] = o; o = al256(o + sizeof(double) * (size_t)B * pi_doubles_per_window(n)); }
     for (int k = 0; k < 2; ++k) { f.PW[k] = o; o = al256(o + sizeof(double) * (size_t)B * nm * PWS); }
+    // (between the wheel and the ground buffers: k_lm_step_quad stages a frame's laser | wheel | ground records as one stream addressed
+    //  from the wheel buffer, with unsigned 32-bit element offsets — lm_step_quad_fits)
+    for (int k = 0; k < 2; ++k) { f.PL[k] = o; o = al256(o + sizeof(double) * (size_t)B * n * lps); }
     for (int k = 0; k < 2; ++k) { f.PG[k] = o; o = al256(o + sizeof(double) * (size_t)B * n * PGS); }
     f.x_cand = o; o = al256(o + sizeof(double) * (size_t)B * n * 15);
     f.group_off = o; o = al256(o + sizeof(int) * (size_t)B * (n + 1));
@@ -273,6 +276,7 @@ static WsView make_view(void* ws, int B, int n, int hist) {
     v.history_records = hist;
     v.active = (int*)(base + f.active);
     v.pi_frame = pi_frame_format(B) ? 1 : 0;
+    v.pl_compact = v.pi_frame;
     for (int k = 0; k < 2; ++k) v.CS[k] = (double*)(base + f.CS[k]);
     v.imu_pk = (double*)(base + f.imu_pk);
     v.imu_pk_bad = (int*)(base + f.imu_pk_bad);
@@ -285,7 +289,8 @@ int liw_batch_ws_layout(int B, int n, int history_records, liw_ws_layout* out) {
     out->bytes = f.bytes;
     out->laser_partial_off[0] = f.PL[0];
     out->laser_partial_off[1] = f.PL[1];
-    out->laser_partial_bytes = sizeof(double) * (size_t)B * n * LP;
+    out->laser_partial_stride = laser_stride(pi_frame_format(B) ? 1 : 0);
+    out->laser_partial_bytes = sizeof(double) * (size_t)B * n * out->laser_partial_stride;
     out->info_off = f.info;
     out->history_off = f.history;
     return LIW_OK;
@@ -347,6 +352,7 @@ static LinArgs lin_args(const liw_batch* b, int mode, const double* x, const WsV
     A.active = use_lm ? v.active : nullptr;
     A.candidate = candidate;
     A.pi_frame = v.pi_frame;
+    A.pl_compact = v.pl_compact;
     for (int k = 0; k < 2; ++k) A.CS[k] = v.pi_frame ? v.CS[k] : nullptr;
     if (packed && b->n > 1 && b->eval_small) { A.imu_pk = v.imu_pk; A.imu_pk_bad = v.imu_pk_bad; }
     if (packed) A.laser_hz = v.imu_pk_bad + 1;
@@ -448,7 +454,7 @@ int liw_batch_exchange_pack(liw_ctx* c, const liw_batch* b, int mode, int candid
     if (int r = check_batch(c, b, min_frames(mode))) return r;
     if (!buf) return fail(c, LIW_EINVAL, "liw_batch_exchange_pack: null buffer");
     WsView v = make_view(ws, b->B, b->n, b->history_records);
-    launch_exchange_pack(b->B, b->n, mode == LIW_MODE_INIT, v.PL[0], v.PL[1], candidate, mode == LIW_MODE_MARG ? nullptr : v.lm, buf, (hipStream_t)stream);
+    launch_exchange_pack(b->B, b->n, mode == LIW_MODE_INIT, v.pl_compact, v.PL[0], v.PL[1], candidate, mode == LIW_MODE_MARG ? nullptr : v.lm, buf, (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
     return LIW_OK;
 }
@@ -458,7 +464,16 @@ int liw_batch_exchange_unpack(liw_ctx* c, const liw_batch* b, int mode, int cand
     if (!buf || copies < 1) return fail(c, LIW_EINVAL, "liw_batch_exchange_unpack: null buffer / copies < 1");
     WsView v = make_view(ws, b->B, b->n, b->history_records);
     const size_t stride = (size_t)liw_batch_exchange_doubles(b->B, b->n, mode);
-    launch_exchange_unpack(b->B, b->n, mode == LIW_MODE_INIT, copies, stride, buf, v.PL[0], v.PL[1], v.pi_frame ? v.CS[0] : nullptr, v.pi_frame ? v.CS[1] : nullptr, candidate, mode == LIW_MODE_MARG ? nullptr : v.lm, (hipStream_t)stream);
+    launch_exchange_unpack(b->B, b->n, mode == LIW_MODE_INIT, v.pl_compact, copies, stride, buf, v.PL[0], v.PL[1], v.pi_frame ? v.CS[0] : nullptr, v.pi_frame ? v.CS[1] : nullptr, candidate, mode == LIW_MODE_MARG ? nullptr : v.lm, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return LIW_OK;
+}
+int liw_batch_laser_records(liw_ctx* c, const liw_batch* b, int mode, int buffer, void* ws, double* out, void* stream) {
+    NEEDDEV(c);
+    if (int r = check_batch(c, b, min_frames(mode))) return r;
+    if (!out || buffer < 0 || buffer > 1) return fail(c, LIW_EINVAL, "liw_batch_laser_records: null output / buffer not 0 or 1");
+    WsView v = make_view(ws, b->B, b->n, b->history_records);
+    launch_laser_expand(b->B, b->n, mode == LIW_MODE_INIT, v.pl_compact, v.PL[buffer], out, (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
     return LIW_OK;
 }
@@ -487,7 +502,7 @@ int liw_batch_solve_sharded(liw_ctx* c, const liw_batch* b, int mode, int max_it
             c->last_x = c->p2p.area[c->p2p_rank] + (size_t)(e & 1ull) * world * nd;
             c->last_x_copies = world;
             WsView v = make_view(ws, b->B, b->n, b->history_records);
-            launch_exchange_unpack(b->B, b->n, mode == LIW_MODE_INIT, world, nd, c->last_x, v.PL[0], v.PL[1], v.pi_frame ? v.CS[0] : nullptr, v.pi_frame ? v.CS[1] : nullptr, cand, v.lm, s, true);
+            launch_exchange_unpack(b->B, b->n, mode == LIW_MODE_INIT, v.pl_compact, world, nd, c->last_x, v.PL[0], v.PL[1], v.pi_frame ? v.CS[0] : nullptr, v.pi_frame ? v.CS[1] : nullptr, cand, v.lm, s, true);
             HIPCHK(c, hipGetLastError());
             if (c->time_exchange) (void)hipEventRecord(next_event(c->ev_x, c->xev_used), s);
             return liw_batch_lm_join(c, stream);

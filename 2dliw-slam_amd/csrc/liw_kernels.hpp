@@ -22,6 +22,7 @@ struct DevParams {
 
 // Partial-sum slots written by k_linearize, per buffer (doubles):
 //   PL[B][n][LP]   laser group (window, owning frame): Haa(36) Hbb(36) Hab(36) ga(6) gb(6) sum r^2 (1), pad -> 128
+//                  (large-batch format: PL[B][n][LPC], the 45 / 21 pair totals the 128 slots are a signed expansion of — laser_slot_code below)
 //   PI[B][n-1][PIS] IMU block k (frames k,k+1): G = Y^T Y, Y = [J(15x30) | r]: blocks ii, jj (packed upper triangles), ij (15x15), g(30), sum r^2 -> 496
 //   PW[B][n-1][PWS] wheel block k: G = Y^T Y, Y = [J(3x12) | r]: blocks ii, jj as packed upper triangles (21 each), ij (6x6 row-major; the ji
 //                   block is ij^T and not stored), gradient (12), sum r^2 -> 91, pad -> 92   (a full 13x13 = 172 until round 3, square ii / jj = 122 until round 4)
@@ -113,6 +114,7 @@ struct WsView {
     int* active;          // [1 + B] compacted list of the windows still iterating (IMU / wheel / ground roles index their blocks over it);
                           //    behind it the ticket word and the per-group publication words of k_compact_active (zeroed by lm_begin)
     int pi_frame;         // 1: PI holds per-frame records (PIF_*, pi_frame_format(B)), 0: per-block records (PI_*)
+    int pl_compact;       // 1: PL holds compact laser group records (LPC pair totals per (window, frame), the large-batch format), 0: 128-slot records
     double* CS[2];        // [B][4][n] per buffer: the cost slot (sum r^2) of every record once more, compact (cs_index; written in the per-frame format only)
     double* imu_pk;       // [B][n-1][IMU_PK] packed IMU block records of the solve in progress (launch_imu_pack, from liw_batch_lm_begin)
     int* imu_pk_bad;      // [0] != 0: some sqrt_inverse_P is not upper triangular -> the IMU role reads the caller's arrays;
@@ -151,6 +153,7 @@ struct LinArgs {
     int small_nd;               // derivative directions per lane of the IMU / wheel roles: 3 (batches) or 1 (k_lin_all on a few windows)
     int* active;                // [1 + B]: number of windows still iterating, then their ids (built per linearisation when lm != null)
     int pi_frame;               // 1: write per-frame IMU records (WsView::pi_frame)
+    int pl_compact;             // 1: write compact laser group records (WsView::pl_compact)
     double* CS[2];              // non-null (per-frame format): every role also stores its record's cost into the compact cost array (cs_index)
     const double* imu_pk;       // packed IMU block records (WsView::imu_pk) or null
     const int* imu_pk_bad;      //   ... usable iff *imu_pk_bad == 0
@@ -167,36 +170,61 @@ struct LinArgs {
 // Slot map of a laser group record (LP slots): which pair total (bits 0..5) of the group's NP unique pair products a slot holds,
 // bit 6 = negated, -1 = structural zero.  Unique columns of a block's two Jacobian rows: BOTH poses free
 // [a_x a_y a_th0..2 b_th0..2 r] (9 -> 45 pairs; b_x = -a_x, b_y = -a_y), one free pose [b_x b_y b_th0..2 r] (6 -> 21 pairs).
-// Record: Haa (0..35) Hbb (36..71) Hab (72..107) ga (108..113) gb (114..119) sum r^2 (120).  The laser kernel builds the same
-// table in LDS (k_lin_laser_body.inc); the factor-sharded exchange packs / unpacks records with it.
+// Record: Haa (0..35) Hbb (36..71) Hab (72..107) ga (108..113) gb (114..119) sum r^2 (120).  THE one statement of the expansion
+// (constexpr: the lane-per-group kernel resolves it at compile time, the lane-per-block kernel builds its LDS table from it, the
+// step kernels their gather tables, the factor-sharded exchange and every reader of a compact record go through it).
+template <bool BOTH> constexpr int laser_pairidx(int c1, int c2) {   // pair total of unique columns c1, c2 (either order)
+    constexpr int NC = BOTH ? 9 : 6;
+    return c1 > c2 ? laser_pairidx<BOTH>(c2, c1) : c1 * NC - c1 * (c1 - 1) / 2 + (c2 - c1);
+}
+constexpr int laser_col_a(int idx) { return idx < 2 ? idx : (idx == 2 ? -1 : idx - 1); }   // pose entry (px py pz th0..2) of pose a -> unique column
+template <bool BOTH> constexpr int laser_col_b(int idx) { return BOTH ? (idx < 2 ? idx : (idx == 2 ? -1 : idx + 2)) : (idx == 2 ? -1 : (idx < 2 ? idx : idx - 1)); }
+template <bool BOTH> constexpr bool laser_neg_b(int idx) { return BOTH && idx < 2; }
 template <bool BOTH>
-__host__ __device__ inline int laser_slot_code(int s) {
-    constexpr int NC = BOTH ? 9 : 6, RC = NC - 1;
-    auto pairidx = [](int c1, int c2) { if (c1 > c2) { const int t = c1; c1 = c2; c2 = t; } return c1 * NC - c1 * (c1 - 1) / 2 + (c2 - c1); };
-    auto col_a = [](int idx) { return idx < 2 ? idx : (idx == 2 ? -1 : idx - 1); };
-    auto col_b = [](int idx) { return BOTH ? (idx < 2 ? idx : (idx == 2 ? -1 : idx + 2)) : (idx == 2 ? -1 : (idx < 2 ? idx : idx - 1)); };
-    auto neg_b = [](int idx) { return BOTH && idx < 2; };
+__host__ __device__ constexpr int laser_slot_code(int s) {
+    constexpr int RC = (BOTH ? 9 : 6) - 1;
     int src = -1;
     bool neg = false;
-    if (s < 36) {
-        const int ca = col_a(s / 6), cb = col_a(s % 6);
-        if (BOTH && ca >= 0 && cb >= 0) src = pairidx(ca, cb);
+    if (s < 0) {
+    } else if (s < 36) {
+        const int ca = laser_col_a(s / 6), cb = laser_col_a(s % 6);
+        if (BOTH && ca >= 0 && cb >= 0) src = laser_pairidx<BOTH>(ca, cb);
     } else if (s < 72) {
-        const int ia = (s - 36) / 6, ib = (s - 36) % 6, ca = col_b(ia), cb = col_b(ib);
-        if (ca >= 0 && cb >= 0) { src = pairidx(ca, cb); neg = neg_b(ia) != neg_b(ib); }
+        const int ia = (s - 36) / 6, ib = (s - 36) % 6, ca = laser_col_b<BOTH>(ia), cb = laser_col_b<BOTH>(ib);
+        if (ca >= 0 && cb >= 0) { src = laser_pairidx<BOTH>(ca, cb); neg = laser_neg_b<BOTH>(ia) != laser_neg_b<BOTH>(ib); }
     } else if (s < 108) {
-        const int ia = (s - 72) / 6, ib = (s - 72) % 6, ca = col_a(ia), cb = col_b(ib);
-        if (BOTH && ca >= 0 && cb >= 0) { src = pairidx(ca, cb); neg = neg_b(ib); }
+        const int ia = (s - 72) / 6, ib = (s - 72) % 6, ca = laser_col_a(ia), cb = laser_col_b<BOTH>(ib);
+        if (BOTH && ca >= 0 && cb >= 0) { src = laser_pairidx<BOTH>(ca, cb); neg = laser_neg_b<BOTH>(ib); }
     } else if (s < 114) {
-        const int ca = col_a(s - 108);
-        if (BOTH && ca >= 0) src = pairidx(ca, RC);
+        const int ca = laser_col_a(s - 108);
+        if (BOTH && ca >= 0) src = laser_pairidx<BOTH>(ca, RC);
     } else if (s < 120) {
-        const int cb = col_b(s - 114);
-        if (cb >= 0) { src = pairidx(cb, RC); neg = neg_b(s - 114); }
+        const int cb = laser_col_b<BOTH>(s - 114);
+        if (cb >= 0) { src = laser_pairidx<BOTH>(cb, RC); neg = laser_neg_b<BOTH>(s - 114); }
     } else if (s == 120) {
-        src = pairidx(RC, RC);
+        src = laser_pairidx<BOTH>(RC, RC);
     }
     return src < 0 ? -1 : (src | (neg ? 64 : 0));
+}
+template <bool BOTH> __host__ __device__ constexpr bool laser_slot_zero(int s) { return laser_slot_code<BOTH>(s) < 0; }   // structural zero
+// Compact laser group record of the large-batch format (WsView::pl_compact): the pair totals themselves, slot p = total p (p < 45 with
+// both poses free, p < 21 with one; the cost total keeps its pair index (8, 8) / (5, 5)), zeros behind them up to LPC = 48 doubles =
+// three full 128-byte lines instead of eight.  The 128-slot record is a signed expansion of exactly these numbers, so a reader that
+// takes total (code & 63) and flips its sign bit where (code & 64) sees the value the expanded slot held, bit for bit.
+constexpr int LPC = LIW_LASER_PARTIAL_COMPACT;
+__host__ __device__ constexpr int laser_stride(int compact) { return compact ? LPC : LP; }
+constexpr int LPC_COST_BOTH = laser_pairidx<true>(8, 8), LPC_COST_ONE = laser_pairidx<false>(5, 5);
+static_assert(laser_slot_code<true>(120) == LPC_COST_BOTH && laser_slot_code<false>(120) == LPC_COST_ONE && LPC_COST_BOTH == 44 && LPC_COST_ONE == 20, "cost total");
+// slot s of the 128-slot record out of a record in either format (the consumers that are not hot)
+template <bool BOTH> __host__ __device__ inline double laser_slot(const double* rec, int s, int compact) {
+    if (!compact) return rec[s];
+    const int code = laser_slot_code<BOTH>(s);
+    if (code < 0) return 0.0;
+    const double v = rec[code & 63];
+    return (code & 64) ? -v : v;
+}
+__host__ __device__ inline double laser_slot(const double* rec, int s, int compact, bool both) {
+    return both ? laser_slot<true>(rec, s, compact) : laser_slot<false>(rec, s, compact);
 }
 struct LaserPackTable { short slot[45]; unsigned char neg[45]; };   // representative record slot (and sign) of every pair total
 
@@ -312,8 +340,8 @@ struct PackArgs {
 };
 void launch_linearize(const LinArgs& A, const DevParams& P, hipStream_t s, const LinFork* fk, bool defer_join = false);
 void launch_linearize_join(hipStream_t s, const LinFork* fk);
-void launch_exchange_pack(int B, int n, bool both, const double* PL0, const double* PL1, int candidate, const LmState* lm, double* buf, hipStream_t s);
-void launch_exchange_unpack(int B, int n, bool both, int world, size_t stride, const double* buf, double* PL0, double* PL1, double* CS0, double* CS1, int candidate, const LmState* lm, hipStream_t s, bool sysload = false);   // CS0 / CS1: the compact cost arrays of the large-batch format (or null)
+void launch_exchange_pack(int B, int n, bool both, int compact, const double* PL0, const double* PL1, int candidate, const LmState* lm, double* buf, hipStream_t s);
+void launch_exchange_unpack(int B, int n, bool both, int compact, int world, size_t stride, const double* buf, double* PL0, double* PL1, double* CS0, double* CS1, int candidate, const LmState* lm, hipStream_t s, bool sysload = false);   // CS0 / CS1: the compact cost arrays of the large-batch format (or null)
 constexpr int P2P_MAX = 16;
 struct P2pPeers { double* area[P2P_MAX]; unsigned long long* flags[P2P_MAX]; };   // device pointers to every rank's receive area / flags, as mapped here
 void launch_p2p_exchange(size_t nd, const double* buf, const P2pPeers& peers, int rank, int world, unsigned long long epoch, int* err, hipStream_t s);
@@ -340,6 +368,7 @@ size_t compact_list_bytes_host(int B);                // bytes of WsView::active
 bool lin_builds_active_list(int B, int eval_small);   // k_linearize.hip: does launch_linearize (with LM state) compact the active windows?
 void launch_lm_finish(const StepArgs& a, hipStream_t s);
 void launch_export_dense(const ExportArgs& a, hipStream_t s);
+void launch_laser_expand(int B, int n, bool both, int compact, const double* PL, double* out, hipStream_t s);   // records of either format -> 128-slot records
 void launch_marg_schur(const MargArgs& a, hipStream_t s);
 
 // batched pre-integration (k_preint.hip)

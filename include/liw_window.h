@@ -173,11 +173,19 @@ typedef struct liw_ws_layout {
     size_t bytes;                /* total */
     size_t laser_partial_off[2]; /* byte offsets of the two laser partial-sum buffers (a window's current linearisation lives in the
                                   * buffer its LM state selects, the candidate in the other: exchange them with liw_batch_exchange_*) */
-    size_t laser_partial_bytes;  /* B*n*LIW_LASER_PARTIAL doubles */
+    size_t laser_partial_bytes;  /* B*n*laser_partial_stride doubles */
     size_t info_off;             /* liw_summary[B] (device) */
     size_t history_off;          /* optional x history, 0 if not requested */
+    int laser_partial_stride;    /* doubles per (window, frame) laser group record in this workspace: LIW_LASER_PARTIAL, or
+                                  * LIW_LASER_PARTIAL_COMPACT in the large-batch format (batches of 1 024 windows and more) */
 } liw_ws_layout;
+/* A laser group record as a caller reads it is LIW_LASER_PARTIAL slots: Haa (0..35) Hbb (36..71) Hab (72..107) ga (108..113)
+ * gb (114..119) sum r^2 (120), zeros behind.  Those slots are a signed expansion of the group's 45 unique pair totals (INIT: both poses
+ * free) or 21 (TRACK / MARG).  Small batches and the single-window path keep the expanded record in the workspace; the large-batch format
+ * keeps the pair totals themselves, LIW_LASER_PARTIAL_COMPACT doubles per record (the totals, zeros behind them), and every kernel that
+ * reads a record applies the expansion as it reads.  liw_batch_laser_records writes the expanded records of either format. */
 #define LIW_LASER_PARTIAL 128
+#define LIW_LASER_PARTIAL_COMPACT 48
 int liw_batch_ws_layout(int B, int n, int history_records, liw_ws_layout* out);
 
 /* LM driver pieces (what ceres::Solve iterates, solver.cpp:168,802).  All launches go to `stream`
@@ -218,6 +226,10 @@ int liw_batch_launch_paths(liw_ctx* ctx, const liw_batch* b, const void* ws, int
  * batches stay near 1 (they packed 4x the data in batch order). */
 int liw_batch_packed_rows(liw_ctx* ctx, const liw_batch* b, const void* ws, long long* rows, long long* blocks);
 int liw_batch_lm_linearize(liw_ctx* ctx, const liw_batch* b, int mode, int candidate, void* ws, void* stream);
+/* The laser group records of partial buffer `buffer` (0 / 1) as B*n*LIW_LASER_PARTIAL doubles in `out` (device), whichever format the
+ * workspace keeps them in; `mode` names the topology they were linearised in (INIT: 45 pair totals, TRACK / MARG: 21).  Inspection aid
+ * (tests); no reference counterpart. */
+int liw_batch_laser_records(liw_ctx* ctx, const liw_batch* b, int mode, int buffer, void* ws, double* out, void* stream);
 int liw_batch_lm_step(liw_ctx* ctx, const liw_batch* b, int mode, void* ws, void* stream);
 int liw_batch_lm_finish(liw_ctx* ctx, const liw_batch* b, int mode, void* ws, void* stream);
 /* Factor-sharded (multi-GPU) exchange of the laser partial sums, SURVEY.md 8(e).  A laser group record (LIW_LASER_PARTIAL slots)
