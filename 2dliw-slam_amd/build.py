@@ -9,20 +9,8 @@ LIB = os.path.join(HERE, "libliw_window.so")
 SOURCES = ["k_linearize.hip", "k_laser_slab.hip", "k_lm.hip", "k_lm_quad.hip", "k_preint.hip", "k_posegraph.hip", "k_laser_frontend.hip", "k_loop.hip", "k_map.hip", "liw_capi.hip", "liw_preint.cpp", "liw_laser.cpp", "liw_io.cpp", "liw_lie.cpp", "liw_loop.cpp", "liw_map.cpp"]
 HEADERS = ["liw_dual.hpp", "liw_kernels.hpp", "k_lm_common.hpp", "k_lin_laser_body.inc", "k_loop.hpp", "k_map.hpp", os.path.join("..", "..", "include", "liw_window.h"), os.path.join("..", "..", "include", "liw_laser.h"), os.path.join("..", "..", "include", "liw_laser_batch.h"), os.path.join("..", "..", "include", "liw_io.h"), os.path.join("..", "..", "include", "liw_posegraph.h"), os.path.join("..", "..", "include", "liw_loop.h"), os.path.join("..", "..", "include", "liw_map.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
-if os.environ.get("LIW_QUAD_OCC"):   # A/B aid: waves per SIMD the quad step kernel is compiled for
-    FLAGS.append("-DLIW_QUAD_OCC=" + os.environ["LIW_QUAD_OCC"])
-if os.environ.get("LIW_SMALL_OCC"):   # A/B aid: waves per SIMD k_lin_small is compiled for (3: <= 168 registers, co-resident with the lane-per-group laser kernel)
-    FLAGS.append("-DLIW_SMALL_OCC=" + os.environ["LIW_SMALL_OCC"])
-if os.environ.get("LIW_QUAD_BSD"):   # second-sweep staging depth of the quad step kernel (2 / 3)
-    FLAGS.append("-DLIW_QUAD_BSD=" + os.environ["LIW_QUAD_BSD"])
-if os.environ.get("LIW_SLAB_ROWS"):   # A/B aid: rows of end points in flight per wave of k_lin_laser_slab (2 / 3 / 4)
-    FLAGS.append("-DLIW_SLAB_ROWS=" + os.environ["LIW_SLAB_ROWS"])
-if os.environ.get("LIW_MARG_OCC"):   # A/B aid: waves per SIMD k_marg_schur (one wave per window) is compiled for
-    FLAGS.append("-DLIW_MARG_OCC=" + os.environ["LIW_MARG_OCC"])
 if os.environ.get("LIW_EXTRA_FLAGS"):   # A/B aid: any further -D... for a probe build (part of the source hash like every flag)
     FLAGS += os.environ["LIW_EXTRA_FLAGS"].split()
-if os.environ.get("LIW_QUAD_TILE_ALIAS"):
-    FLAGS.append("-DLIW_QUAD_TILE_ALIAS")
 if os.environ.get("LIW_CLK"):   # phase-timing build for tools/clk_probe_*.py
     FLAGS.append("-DLIW_CLK")
     if os.environ.get("LIW_CLK_IT"):

@@ -66,23 +66,13 @@ template <bool BOTH, int S_> __device__ __forceinline__ double slab_slot(const d
     else if constexpr ((code & 64) != 0) return -acc[code & 63];
     else return acc[code & 63];
 }
-template <bool BOTH, int S_> __device__ __forceinline__ void slab_store(double* out, const double* acc) {
-    if constexpr (S_ < LP) {
-        typedef double __attribute__((ext_vector_type(2))) dbl2;
-        dbl2 v;
-        v.x = slab_slot<BOTH, S_>(acc); v.y = slab_slot<BOTH, S_ + 1>(acc);
-        *reinterpret_cast<dbl2*>(out + S_) = v;
-        slab_store<BOTH, S_ + 2>(out, acc);
-    }
-}
 
 // Epilogue (round 5, late): the 64 records of a wave lie 1 KiB x n apart, so a lane that stores its own record writes 16 bytes into 64
 // different cache lines per instruction -- 0.47 of the kernel's 1.79 ms per 49 152 C2 windows went into those partial-line writes
 // (probe build without the stores).  The records are staged through LDS instead, 32 slots of every lane at a time ([lane][32 + 2 pad]),
 // and leave as 256-byte runs: a store instruction covers four windows x 16 lanes x 16 bytes = eight full lines.
-#ifndef LIW_SLAB_NT
-#define LIW_SLAB_NT 3                 // bit 0: the packed rows are loaded, bit 1: the records stored with the nontemporal hint (both are touched once per
-#endif                                // launch; 1.67 -> 1.53 ms per 49 152 C2 windows on one box, 1.64 / 1.58 with one of the two)
+// The packed rows are loaded and the records stored with the nontemporal hint (both are touched once per launch; 1.67 -> 1.53 ms per
+// 49 152 C2 windows on one box, 1.64 / 1.58 with one of the two).
 constexpr int STG = 34;               // doubles per lane of a staged chunk (32 slots + 2 of padding: conflict-free 16-byte accesses)
 template <bool BOTH, int C_, int I_ = 0> __device__ __forceinline__ void slab_stage(double* st, const double* acc) {
     if constexpr (I_ < 16) {
@@ -105,11 +95,7 @@ template <bool BOTH, int C_> __device__ __forceinline__ void slab_flush(double* 
             const int w = 4 * t + wq;
             const unsigned long long p = pw[w];
             const dbl2 v = *reinterpret_cast<const dbl2*>(lds + w * STG + 2 * pc);
-#if LIW_SLAB_NT & 2
             if (p) __builtin_nontemporal_store(v, reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 32 * C_ + 2 * pc));
-#else
-            if (p) *reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 32 * C_ + 2 * pc) = v;
-#endif
         }
         slab_flush<BOTH, C_ + 1>(lds, pw, acc, lane);
     }
@@ -143,11 +129,7 @@ template <int N_> __device__ __forceinline__ void slab_flush_compact(double* lds
             const int w = 4 * t + wq;
             const unsigned long long p = pw[w];
             const dbl2 v = *reinterpret_cast<const dbl2*>(lds + w * STG + 2 * pc);
-#if LIW_SLAB_NT & 2
             if (p) __builtin_nontemporal_store(v, reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 2 * pc));
-#else
-            if (p) *reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 2 * pc) = v;
-#endif
         }
     }
     lds_sync();
@@ -160,11 +142,7 @@ template <int N_> __device__ __forceinline__ void slab_flush_compact(double* lds
             const int w = 8 * t + wq;
             const unsigned long long p = pw[w];
             const dbl2 v = *reinterpret_cast<const dbl2*>(lds + w * STG + 2 * pc);
-#if LIW_SLAB_NT & 2
             if (p) __builtin_nontemporal_store(v, reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 32 + 2 * pc));
-#else
-            if (p) *reinterpret_cast<dbl2*>(reinterpret_cast<double*>(p) + 32 + 2 * pc) = v;
-#endif
         }
     }
 }
@@ -178,7 +156,7 @@ __device__ __forceinline__ double slab_weight(double d1x, double d1y, double d2x
 
 constexpr int SLAB = 64;
 constexpr int ROWD = LASER_SLAB_ROWD;  // doubles per packed row
-constexpr int NPL = ROWD / SLAB;       // planes per row: 8 end-point components (+ the block weight)
+constexpr int NPL = ROWD / SLAB;       // planes per row: the 8 end-point components
 
 }  // namespace
 
@@ -259,28 +237,14 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
     for (int e = 0; e < NACC; ++e) acc[e] = 0.0;
     const double* row0 = A.laser_pk + (size_t)A.laser_slab_off[(size_t)s * n + f] * ROWD + lane;
     auto load_row = [&](double* q, int j) {
-#if defined(LIW_SLAB_PROBE) && LIW_SLAB_PROBE == 1
-        const double* r = row0 + (size_t)(j & 1) * ROWD;       // probe: every load hits the slab's first two rows (cache-resident): compute-only time
-#else
         const double* r = row0 + (size_t)j * ROWD;
-#endif
 #pragma unroll
-#if LIW_SLAB_NT & 1
         for (int c = 0; c < NPL; ++c) q[c] = __builtin_nontemporal_load(r + c * SLAB);
-#else
-        for (int c = 0; c < NPL; ++c) q[c] = r[c * SLAB];
-#endif
     };
     const double w0 = P.laser_sqrt_info;
 #define TA(k) ((k) < TFR ? ra[(k) < TFR ? (k) : 0] : lta[((k) < TFR ? 0 : (k) - TFR) * SLAB + lane])
 #define TB(k) ((k) < TFR ? rb[(k) < TFR ? (k) : 0] : ltb[((k) < TFR ? 0 : (k) - TFR) * SLAB + lane])
     auto block = [&](const double* p) {     // one laser_factor block (k_lin_laser_body.inc, 2-D, both poses free): rows + pair products
-#if defined(LIW_SLAB_PROBE) && LIW_SLAB_PROBE == 2
-        // probe: no arithmetic, the loads only (memory-only time)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) acc[c] += p[c];
-        return;
-#endif
         const double d1x = p[0] - p[2], d1y = p[1] - p[3];
         const double d2x = p[4] - p[6], d2y = p[5] - p[7];
         const double l2 = fmin(d1x * d1x + d1y * d1y, d2x * d2x + d2y * d2y);
@@ -372,10 +336,6 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
             }
         }
     };
-#ifndef LIW_SLAB_ALG
-#define LIW_SLAB_ALG 1      // 0: every block through the general form (A/B aid)
-#endif
-#if LIW_SLAB_ALG == 1
     // The same block with the algebra folded (round 5, late): only DIFFERENCES of mapped points enter the rows, so the reference segment's
     // direction is M_a (B - A) (no translation, no mapped A), the whole row is scaled by the block's weight ONCE through the line
     // direction (l_w = w l: the sign of the distance then needs no select — the pair products of a row are even in it, and the products
@@ -385,12 +345,8 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
     bool irregular = false;
     auto block_fast = [&](const double* p) {
         const double d1x = p[0] - p[2], d1y = p[1] - p[3];
-#if LIW_SLAB_WPLANE
-        const double w = p[8] * w0;                 // the block's weight from the ninth plane of the row (slab_weight, computed once per solve by the re-pack)
-#else
         const double d2x = p[4] - p[6], d2y = p[5] - p[7];
         const double w = slab_weight(d1x, d1y, d2x, d2y) * w0;
-#endif
         const double ux = -(ra[0] * d1x + ra[1] * d1y), uy = -(ra[2] * d1x + ra[3] * d1y);
         const double zz = ux * ux + uy * uy;
         if (__builtin_expect(!(zz > 0.0), 0)) { irregular = true; return; }      // zero-length reference segment (or NaN input): the general form, in a pass of its own behind the loop
@@ -479,69 +435,22 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
             }
         }
     };
-#define LIW_SLAB_BLOCK block_fast
-#else
-#define LIW_SLAB_BLOCK block
-#endif
-    // rows in flight: LIW_SLAB_ROWS register sets in rotation.  The loads are UNCONDITIONAL (row index clamped to the slab's last row):
+    // rows in flight: two register sets in rotation.  The loads are UNCONDITIONAL (row index clamped to the slab's last row):
     // behind a branch the compiler can no longer count them and waits for every outstanding load before each block
-#ifndef LIW_SLAB_ROWS
-#define LIW_SLAB_ROWS 2
-#endif
     const int last = maxc - 1;
-#if LIW_SLAB_ROWS == 2
     double q0[NPL], q1[NPL];
     if (maxc > 0) {
         load_row(q0, 0);
         for (int j = 0; j < maxc; j += 2) {
             asm volatile("" ::: "memory");
             load_row(q1, min(j + 1, last));
-            if (j < cnt) LIW_SLAB_BLOCK(q0);
+            if (j < cnt) block_fast(q0);
             __builtin_amdgcn_sched_barrier(0);
             load_row(q0, min(j + 2, last));
-            if (j + 1 < cnt) LIW_SLAB_BLOCK(q1);
+            if (j + 1 < cnt) block_fast(q1);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-#elif LIW_SLAB_ROWS == 3
-    double q0[NPL], q1[NPL], q2[NPL];
-    if (maxc > 0) {
-        load_row(q0, 0); load_row(q1, min(1, last));
-        for (int j = 0; j < maxc; j += 3) {
-            asm volatile("" ::: "memory");
-            load_row(q2, min(j + 2, last));
-            if (j < cnt) LIW_SLAB_BLOCK(q0);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(q0, min(j + 3, last));
-            if (j + 1 < cnt) LIW_SLAB_BLOCK(q1);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(q1, min(j + 4, last));
-            if (j + 2 < cnt) LIW_SLAB_BLOCK(q2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#else
-    double q0[NPL], q1[NPL], q2[NPL], q3[NPL];
-    if (maxc > 0) {
-        load_row(q0, 0); load_row(q1, min(1, last)); load_row(q2, min(2, last));
-        for (int j = 0; j < maxc; j += 4) {
-            asm volatile("" ::: "memory");
-            load_row(q3, min(j + 3, last));
-            if (j < cnt) LIW_SLAB_BLOCK(q0);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(q0, min(j + 4, last));
-            if (j + 1 < cnt) LIW_SLAB_BLOCK(q1);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(q1, min(j + 5, last));
-            if (j + 2 < cnt) LIW_SLAB_BLOCK(q2);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(q2, min(j + 6, last));
-            if (j + 3 < cnt) LIW_SLAB_BLOCK(q3);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#endif
-#if LIW_SLAB_ALG == 1
     if (__builtin_expect(__any(irregular), 0)) {
         // the blocks block_fast left out (their pair products join the lane's sums behind the regular ones): same test, general form.
         // Kept out of the main loop so that its live ranges do not count against the rows in flight there.
@@ -553,20 +462,9 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
             if (irregular && j < cnt && !(ux * ux + uy * uy > 0.0)) block(q);
         }
     }
-#endif
     SSTAMP(3);
 #undef TA
 #undef TB
-#undef LIW_SLAB_BLOCK
-#if defined(LIW_SLAB_DIRECT_STORE)
-    if (in) {
-        double* out = (psel ? A.PL[1] : A.PL[0]) + ((size_t)bb * n + f) * laser_stride(A.pl_compact);
-        if (A.pl_compact) {
-#pragma unroll
-            for (int e = 0; e < LPC; ++e) out[e] = e < NACC ? acc[e < NACC ? e : 0] : 0.0;
-        } else slab_store<BOTH, 0>(out, acc);
-    }
-#else
     {
         static_assert(SLAB * STG + SLAB <= 2 * (TF2 - TFR) * SLAB && LP == 128, "staging area of the record epilogue");
         unsigned long long* pw = reinterpret_cast<unsigned long long*>(lds + SLAB * STG);
@@ -575,7 +473,6 @@ __device__ __forceinline__ void slab_item(const LinArgs& A, const DevParams& P, 
         if (A.pl_compact) slab_flush_compact<NACC>(lds, pw, acc, lane);   // (uniform: the large-batch format stores the pair totals themselves)
         else slab_flush<BOTH, 0>(lds, pw, acc, lane);
     }
-#endif
     if (in && A.CS[0]) (psel ? A.CS[1] : A.CS[0])[cs_index(n, bb, CS_LASER, f)] = acc[BOTH ? slab_pairidx(8, 8) : slab_pairidx1(5, 5)];
     SSTAMP(4);
 }
@@ -684,17 +581,6 @@ __global__ __launch_bounds__(256) void k_laser_slab_pack(int B, int n, long Ltot
             for (int r = t >> 6; r < rows; r += 4) base[(size_t)(jb + r) * ROWD + c * SLAB + (t & 63)] = tile[r * 65 + (t & 63)];
             __syncthreads();
         }
-#if LIW_SLAB_WPLANE
-        {   // ninth plane: the weights of the rows just written (read back lane-linear: the lines are still in the cache)
-            __threadfence_block();
-            __syncthreads();
-            const int rows = min(64, maxc - jb);
-            for (int r = t >> 6; r < rows; r += 4) {
-                const double* q = base + (size_t)(jb + r) * ROWD + (t & 63);
-                base[(size_t)(jb + r) * ROWD + 8 * SLAB + (t & 63)] = slab_weight(q[0] - q[2 * SLAB], q[SLAB] - q[3 * SLAB], q[4 * SLAB] - q[6 * SLAB], q[5 * SLAB] - q[7 * SLAB]);
-            }
-        }
-#endif
     }
 }
 

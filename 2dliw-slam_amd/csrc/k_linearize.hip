@@ -21,12 +21,6 @@
 #include <cstring>
 #include "liw_kernels.hpp"
 
-#ifndef LIW_IMU_PROBE_NOSTORE
-#define LIW_IMU_PROBE_NOSTORE 0     // probe build (wrong results): k_lin_imu_chain without its frame-record stores
-#endif
-#ifndef LIW_IMU_PROBE_PHASE
-#define LIW_IMU_PROBE_PHASE 0       // probe builds (wrong results, round 6): 1 = the dual-number part only (the block records stay in LDS, nothing is stored),
-#endif                              // 2 = the matrix-core part only (on whatever the LDS holds): the two halves of the split VERDICT r5 proposed, each alone
 namespace liw {
 
 // ------------------------------------------------------------------------------------------- laser
@@ -109,10 +103,7 @@ typedef LJN<3> J3;
 // (31.6 kB, five waves per CU) the kernel took 563 us per 12 288 C2 windows, with the packed inputs alone 3 % less.
 constexpr int IMU_PER_WAVE = 16;    // (18 until the chain kernel's output staging area took the room of two blocks)
 constexpr int IMU_STAGE = 244;      // k_lin_imu_chain: one frame record's larger part (ij | g_j: 240 doubles) on its way out
-#ifndef LIW_IMU_COAL
-#define LIW_IMU_COAL 1                // A/B aid: 0 = the sqrt-information operands as four 8-byte gathers per block (until round 6)
-#endif
-constexpr int IMU_SBUF = LIW_IMU_COAL ? 128 : 0;   // LDS copy of one block's packed sqrt-information triangle (COAL in imu_blocks): 19 232 -> 20 256 B, still eight waves per CU
+constexpr int IMU_SBUF = 128;       // LDS copy of one block's packed sqrt-information triangle (COAL in imu_blocks): 19 232 -> 20 256 B, still eight waves per CU
 // compact block record in LDS (doubles): Xc[9][10] = rows alpha, beta, gamma: the 9 derivative columns (theta_i 0-2, theta_j 3-5,
 // bw_i 6-8) + r_raw (9); Rb[6] = r_raw of the bias rows (their derivative columns are constants); Rt[9] = R_i^T; RtDt[9];
 // Jb[18] = alpha_J_ba (9), beta_J_ba (9)
@@ -252,10 +243,6 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
     // memory round trips per wave: 0.6 of the role's 2.15 ms (probe build with constant operands: 1.56 ms).  One batch = one round trip.
     constexpr int GRP = ND == 3 ? 8 : 1;
     auto load_sop = [&](int gq, double* o) {
-#if defined(LIW_IMU_PROBE_NOSOP)      // probe build (wrong results): the sqrt-information operands are constants — no global loads in front of / inside the matrix-core loop
-        for (int c = 0; c < 4; ++c) o[c] = 1.0 + 0.001 * (gq + c);
-        return;
-#endif
         const int fq = __shfl(fk_lane, gq < nblk ? LPB * gq : 0, 64);
         const double* S = PK ? A.imu_pk + (size_t)fq * IMU_PK + IPK_S : A.imu_sqrtP + (size_t)fq * 225;
 #pragma unroll
@@ -278,7 +265,7 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
     // COAL (round 6, the chain kernels on packed records): a block's sqrt-information triangle is fetched as ONE coalesced 16-byte-per-lane load (61 lanes:
     // 120 entries + the zero word) instead of four gathers of 8 bytes per lane, parked in registers (4 per block) and spread into the MFMA operand
     // layout through a 1-KiB LDS buffer right before the block's products (one ds_write_b128 + four ds_read_b64 at per-lane offsets).
-    constexpr bool COAL = CHAIN && PK && ND == 3 && LIW_IMU_COAL;
+    constexpr bool COAL = CHAIN && PK && ND == 3;
     typedef double __attribute__((ext_vector_type(2))) sraw_t;
     auto load_raw = [&](int gq) -> sraw_t {
         const int fq = __shfl(fk_lane, gq < nblk ? LPB * gq : 0, 64);
@@ -296,20 +283,13 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
         for (int q = 0; q < GRP; ++q) load_sop(q, sop[q]);
     }
     LSTAMP(300);
-    if (on && LIW_IMU_PROBE_PHASE != 2) {
+    if (on) {
         const size_t fk = (size_t)b * nb + k;   // record of this block in the (uncompacted) input / partial arrays
-#if defined(LIW_IMU_PROBE_INCACHE)   // probe build (wrong results): every block's states and packed inputs are those of block 0 (cache-resident)
-        const double* si_ = A.x;
-        const double* sj_ = si_ + 15;
-        constexpr int JLD = PK ? 6 : 15;
-        const double* pkr = PK ? A.imu_pk : nullptr;
-#else
         const double* si_ = A.x + ((size_t)b * n + k) * 15;
         const double* sj_ = si_ + 15;
         // Jp[r * JLD + c], r < 9, 9 <= c < 15: the bias blocks of the pre-integration Jacobian (the only entries the factor reads)
         constexpr int JLD = PK ? 6 : 15;
         const double* pkr = PK ? A.imu_pk + fk * IMU_PK : nullptr;
-#endif
         const double* Jp = PK ? pkr + IPK_J - 9 : A.imu_J + fk * 225;
         const double* X0 = PK ? pkr : A.imu_X + fk * 15;
         const double Dt = PK ? pkr[IPK_DT] : A.imu_Dt[fk];
@@ -432,10 +412,6 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
     }
     lds_sync();
     LSTAMP(304);
-#if LIW_IMU_PROBE_PHASE == 1
-    if (lane < 16 && A.dbg_imu_res) A.dbg_imu_res[lane] = lds[lane * IMU_REC + 9];      // (keeps the dual-number part alive: the pointer is null outside tests)
-    return;
-#endif
     // ---- matrix-core part, one block at a time (the whole wave cooperates).  Operand entry codes of this lane: x0 = column ml of
     // [J_raw wrt x_i | r_raw], x1 = column ml of [J_raw wrt x_j] for the four k-chunks (row kk = mk + 4c)
     if constexpr (ND != 1) ops = c_imu_optab.lane[lane];      // (throughput kernels: 24 registers that must not live across the dual-number part)
@@ -517,10 +493,6 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
             const int sel = __builtin_amdgcn_readfirstlane(__shfl(sel_lane, LPB * gq, 64));
             if constexpr (CHAIN) {
                 chain11 = g11;
-#if defined(LIW_IMU_PROBE_NOOUT)      // probe build (wrong results): operands + the 20 MFMAs of a block only — no staging, no flush, no stores
-                if (g00[0] + g01[1] + g11[2] == 12345.678) lds[lane] = g00[3];
-                continue;
-#endif
                 if (ghost && gq == 0) continue;   // evaluated for its jj tile only
                 // frame kq's record: diagonal tile (upper triangle), gradient part of block (kq, kq+1); frame kq+1's: coupling, gradient
                 // part and cost of the block; behind a window's last block the jj tile is frame n-1's diagonal
@@ -536,7 +508,7 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
                 typedef double __attribute__((ext_vector_type(2))) dbl2;
                 auto flush = [&](double* dst, int nd) {          // nd doubles (even) from img to dst, 16 bytes per lane
                     lds_sync();
-                    for (int e = 2 * lane; e < nd && !LIW_IMU_PROBE_NOSTORE; e += 128) nt_store<4>(reinterpret_cast<dbl2*>(dst + e), *reinterpret_cast<const dbl2*>(img + e));
+                    for (int e = 2 * lane; e < nd; e += 128) nt_store(reinterpret_cast<dbl2*>(dst + e), *reinterpret_cast<const dbl2*>(img + e));
                     lds_sync();
                 };
                 // staging writes are UNCONDITIONAL: every lane's four (tile row group -> staging word) offsets are constants of the wave
@@ -550,7 +522,7 @@ __device__ __forceinline__ void imu_blocks(const LinArgs& A, const DevParams& P,
 #pragma unroll
                     for (int r = 0; r < 4; ++r) img[so_d[r]] = (ml == 15 && !with_gi) ? 0.0 : gd[r];
                     lds_sync();
-                    if (lane < 60 && !LIW_IMU_PROBE_NOSTORE) nt_store<4>(reinterpret_cast<dbl2*>(rec + PIF_D + 2 * lane), *reinterpret_cast<const dbl2*>(img + 2 * lane));
+                    if (lane < 60) nt_store(reinterpret_cast<dbl2*>(rec + PIF_D + 2 * lane), *reinterpret_cast<const dbl2*>(img + 2 * lane));
                     if (lane < 15) rec[PIF_GI + lane] = img[120 + lane];
                     lds_sync();
                 };
@@ -798,7 +770,7 @@ __device__ __forceinline__ void wheel_blocks(const LinArgs& A, const DevParams& 
             };
             auto put = [&](int q, const double2& v) {
                 const int sel = __builtin_amdgcn_readlane(selv, q);
-                nt_store<8>(reinterpret_cast<double2*>(&(sel ? A.PW[1] : A.PW[0])[(size_t)__builtin_amdgcn_readlane(fkv, q) * PWS + 2 * lane]), v);
+                *reinterpret_cast<double2*>(&(sel ? A.PW[1] : A.PW[0])[(size_t)__builtin_amdgcn_readlane(fkv, q) * PWS + 2 * lane]) = v;
             };
             int q = 0;
             if (all_on)
@@ -887,7 +859,7 @@ __device__ __forceinline__ void ground_frames(const LinArgs& A, const DevParams&
                 v.y = mult * __builtin_fma(Yq[7 + r1], Yq[7 + c1], Yq[r1] * Yq[c1]);
                 return v;
             };
-            auto put = [&](int sel, int fq, const double2& v) { nt_store<8>(reinterpret_cast<double2*>(&(sel ? A.PG[1] : A.PG[0])[(size_t)fq * PGS + 2 * pr]), v); };
+            auto put = [&](int sel, int fq, const double2& v) { *reinterpret_cast<double2*>(&(sel ? A.PG[1] : A.PG[0])[(size_t)fq * PGS + 2 * pr]) = v; };
             int q = j;
             if (all_on)
                 for (; q + 4 < nfr; q += 8) {                  // two rounds of four frames in flight
@@ -934,17 +906,10 @@ __device__ __forceinline__ void wheel_ground2_blocks(const LinArgs& A, const Dev
     double* Y = lds + (blk < WG_PER_WAVE ? blk : 0) * WG_REC;
     const size_t fk = on ? (size_t)b * nb + k : 0, fi0 = on ? (size_t)b * n + k : 0;
     if (on) {
-#if defined(LIW_SMALL_PROBE_INCACHE)   // probe build (wrong results): every block reads block 0's states and odometry increment (cache-resident)
-        const double* si_ = A.x;
-        const double* sj_ = si_ + 15;
-        const double* T12 = A.wheel_T;
-        const double* sq9 = A.wheel_sqrtP;
-#else
         const double* si_ = A.x + fi0 * 15;
         const double* sj_ = si_ + 15;
         const double* T12 = A.wheel_T + fk * 12;
         const double* sq9 = A.wheel_sqrtP + fk * 9;
-#endif
         const V3<double> thi = cast_v3<double>(si_ + 3), thj = cast_v3<double>(sj_ + 3);
         V3<J3> arg;   // the rotation this lane differentiates
         arg.x = seed<3>(f ? thj.x : thi.x, 0, true); arg.y = seed<3>(f ? thj.y : thi.y, 1, true); arg.z = seed<3>(f ? thj.z : thi.z, 2, true);
@@ -1096,7 +1061,7 @@ __device__ __forceinline__ void wheel_ground2_blocks(const LinArgs& A, const Dev
         };
         auto put = [&](int q, const double2& v) {
             const int sel = __builtin_amdgcn_readlane(selv, q);
-            nt_store<8>(reinterpret_cast<double2*>(&(sel ? A.PW[1] : A.PW[0])[(size_t)__builtin_amdgcn_readlane(fkv, q) * PWS + 2 * lane]), v);
+            *reinterpret_cast<double2*>(&(sel ? A.PW[1] : A.PW[0])[(size_t)__builtin_amdgcn_readlane(fkv, q) * PWS + 2 * lane]) = v;
         };
         int q = 0;
         if (all_on)
@@ -1128,7 +1093,7 @@ __device__ __forceinline__ void wheel_ground2_blocks(const LinArgs& A, const Dev
                     v.x = mult * __builtin_fma(Yq[7 + r0], Yq[7 + c0], Yq[r0] * Yq[c0]);
                     v.y = mult * __builtin_fma(Yq[7 + r1], Yq[7 + c1], Yq[r1] * Yq[c1]);
                     if (sel >= 0 && (pass == 0 || kq == 0))
-                        nt_store<8>(reinterpret_cast<double2*>(&(sel ? A.PG[1] : A.PG[0])[(size_t)fq * PGS + 2 * pr]), v);
+                        *reinterpret_cast<double2*>(&(sel ? A.PG[1] : A.PG[0])[(size_t)fq * PGS + 2 * pr]) = v;
                 }
             }
         }
@@ -1219,12 +1184,10 @@ void launch_imu_pack(int B, int n, const double* imu_X, const double* imu_J, con
     if (blocks <= 0) return;
     hipLaunchKernelGGL(k_imu_pack, dim3((unsigned)blocks), dim3(256), 0, s, blocks, imu_X, imu_J, imu_sqrtP, imu_Dt, pk, bad);
 }
-#ifndef LIW_SMALL_OCC
-#define LIW_SMALL_OCC 2   // (two waves per SIMD: 17.6 kB of LDS per wave, no scratch; two and three waves tied before the roles were merged)
-#endif
-__global__ __launch_bounds__(64, LIW_SMALL_OCC) void k_lin_small(LinArgs A, DevParams P) {
+constexpr int SMALL_OCC = 2;   // (two waves per SIMD: 17.6 kB of LDS per wave, no scratch; two and three waves tied before the roles were merged)
+__global__ __launch_bounds__(64, SMALL_OCC) void k_lin_small(LinArgs A, DevParams P) {
     __shared__ double lds[WG_LDS > SMALL_LDS ? WG_LDS : SMALL_LDS];
-    static_assert(sizeof(double) * (WG_LDS > SMALL_LDS ? WG_LDS : SMALL_LDS) * 4 * LIW_SMALL_OCC <= 160 * 1024, "LDS of the waves of a CU");
+    static_assert(sizeof(double) * (WG_LDS > SMALL_LDS ? WG_LDS : SMALL_LDS) * 4 * SMALL_OCC <= 160 * 1024, "LDS of the waves of a CU");
     const int* const act = usable_active_list(A.active, A.B);
     if (A.n > 1) wheel_ground2_blocks<true>(A, P, (int)blockIdx.x, lds, act);   // wheel blocks; the ground frames ride along
     else ground_frames<true>(A, P, (int)blockIdx.x, lds, act);                   // a one-frame window has no wheel block

@@ -2066,10 +2066,8 @@ struct LdsMarg {
     double D[256], O[256], R[256], W[256], Wa[256], CD[256];
     double g[16], Cg[16], y0[16], tmp[ASM_TMP];
 };
-#ifndef LIW_MARG_OCC
-#define LIW_MARG_OCC 3
-#endif
-__global__ __launch_bounds__(64, LIW_MARG_OCC) void k_marg_schur(MargArgs a) {
+constexpr int MARG_OCC = 3;   // waves per SIMD both one-wave-per-window kernels are compiled for
+__global__ __launch_bounds__(64, MARG_OCC) void k_marg_schur(MargArgs a) {
     __shared__ LdsMarg T;
     static_assert(sizeof(LdsMarg) * 12 <= 160 * 1024, "twelve waves per CU");
     marg_schur_body(a, (int)blockIdx.x, T, T.R, T.O, T.Cg);
@@ -2186,7 +2184,7 @@ __device__ __forceinline__ void jq_round(double (&A)[16], double (&V)[15], doubl
     lds_sync();
 }
 
-__global__ __launch_bounds__(64, LIW_MARG_OCC) void k_marg_schur_chain(MargArgs a) {
+__global__ __launch_bounds__(64, MARG_OCC) void k_marg_schur_chain(MargArgs a) {
     __shared__ LdsMarg T;
     const int b = blockIdx.x, lane = threadIdx.x & 63;
     double* S = a.w.solve_ws + (size_t)b * a.n * SOLVE_WS;

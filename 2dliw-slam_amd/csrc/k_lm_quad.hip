@@ -65,16 +65,9 @@ __device__ __forceinline__ double row_max(double v) {
 // phase stamps (tools/clk_probe_quad.py): s_memtime of one wave at one frame of one LM iteration; dormant unless switched on
 __device__ long long g_qclk[64];
 __device__ int g_qclk_on[4];   // on, block, frame, iteration
-__device__ int g_qprobe;       // LIW_QUAD_PROBE (diagnosis only, results are wrong): bit 0 = every row reads window 0's partial records (cache-resident),
-                               // bit 1 = every row's back-substitution record is window 0's
 #define QSTAMP(id) do { if (clk_on && i == clk_frame) { if (lane == 0) g_qclk[(id)] = clock64(); } } while (0)
 
-#ifdef LIW_QUAD_TILE_ALIAS   // occupancy experiment only (WRONG results): the tile aliases the IMU record's ii block, LDS = the records alone
-constexpr int QTR = 0;
-#else
-constexpr int QNT1 = (LIW_NT_MASK & 16) ? 2 : 0, QNT2 = (LIW_NT_MASK & 64) ? 2 : 0;   // cache policy of the LDS-DMA pieces (2 = nt)
 constexpr int QTR = 4 * 15 * 6;                           // transposition tile of the carried arrow block (below)
-#endif
 // Gather table of the assembly phase: one 16-bit LDS byte offset per (read, lane) — see the kernel.  Reads: K_A laser Hbb | gb, K_B wheel
 // jj | g_j, K_C ground H | g, K_HA laser Haa | ga, K_D IMU diagonal tile, K_CW wheel ii | g_i, K_GSH wheel g_i lane per entry, K_RL laser Hab.
 constexpr int K_A = 0, K_B = 6, K_C = 12, K_HA = 18, K_D = 24, K_CW = 39, K_GSH = 45, K_RL = 46, NRD = 52;
@@ -120,10 +113,7 @@ template <int KIND, int R> __device__ __forceinline__ int quad_code(bool track, 
     return c == 0xff ? -1 : c;
 }
 __device__ __forceinline__ double flip_sign(double x, unsigned m) { return __hiloint2double(__double2hiint(x) ^ (int)m, __double2loint(x)); }   // m: 0x80000000 or 0
-#ifndef LIW_QUAD_BSD
-#define LIW_QUAD_BSD 3   // frames of second-sweep records in flight (2: 30 kB of LDS per wave instead of 38 — co-residency experiments)
-#endif
-constexpr int BSD2 = LIW_QUAD_BSD;
+constexpr int BSD2 = 3;   // frames of second-sweep records in flight (2: 30 kB of LDS per wave instead of 38, same speed alone — co-residency experiments)
 constexpr int QTOT_2 = BSD2 * (((4 * REC_GS + 127) / 128) * 128 + 6 * 32);             // second sweep: three frames of records + state / scale / diagonal entries
 constexpr int QTOT = QTOT_1 > QTOT_2 ? QTOT_1 : QTOT_2;   // LDS doubles per wave: the prefetched partial records of its four rows, the tile, a zero word, the gather table (35.6 kB: four waves per CU)
 
@@ -133,10 +123,7 @@ template <int R> __device__ __forceinline__ int tri_rc(int j, int cj) {   // cj 
     return R <= j ? cR + j : cj + R;
 }
 
-#ifndef LIW_QUAD_OCC
-#define LIW_QUAD_OCC 1
-#endif
-__global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
+__global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     __shared__ double S[QTOT];
     const int lane = threadIdx.x & 63, j = lane & 15, w = lane >> 4;
     const int n = a.n;
@@ -296,13 +283,11 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     const double* const PI0 = a.w.PI[0];
     const double* const PW0 = a.w.PW[0];
     const double* const PG0 = a.w.PG[0];
-    const unsigned bp = (g_qprobe & 1) ? 0u : (unsigned)b;
-    const unsigned oPL = bp * (unsigned)(n * LPC) + (cur ? (unsigned)(a.w.PL[1] - a.w.PL[0]) : 0u);
-    const unsigned oPI = bp * (unsigned)(n * PIFS) + (cur ? (unsigned)(a.w.PI[1] - a.w.PI[0]) : 0u);
-    const unsigned oPW = bp * (unsigned)((n - 1) * PWS) + (cur ? (unsigned)(a.w.PW[1] - a.w.PW[0]) : 0u);
-    const unsigned oPG = bp * (unsigned)(n * PGS) + (cur ? (unsigned)(a.w.PG[1] - a.w.PG[0]) : 0u);
-    const int qprobe = g_qprobe;
-    const unsigned oWS = (qprobe & 2) ? 0u : (unsigned)b * (unsigned)(n * SOLVE_WS);
+    const unsigned oPL = (unsigned)b * (unsigned)(n * LPC) + (cur ? (unsigned)(a.w.PL[1] - a.w.PL[0]) : 0u);
+    const unsigned oPI = (unsigned)b * (unsigned)(n * PIFS) + (cur ? (unsigned)(a.w.PI[1] - a.w.PI[0]) : 0u);
+    const unsigned oPW = (unsigned)b * (unsigned)((n - 1) * PWS) + (cur ? (unsigned)(a.w.PW[1] - a.w.PW[0]) : 0u);
+    const unsigned oPG = (unsigned)b * (unsigned)(n * PGS) + (cur ? (unsigned)(a.w.PG[1] - a.w.PG[0]) : 0u);
+    const unsigned oWS = (unsigned)b * (unsigned)(n * SOLVE_WS);
     double* const WS = a.w.solve_ws;
     const unsigned oSC = oLM + LM_SCALE, oDG = oLM + LM_DIAG;
     const int jc = j < 15 ? j : 0;            // clamped column for addresses
@@ -359,8 +344,8 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     //   S_PL[w][48]    compact laser group record of frame f     }
     //   S_PW[w][92]    wheel partial of block (f-1, f)           } back to back: ONE lane-linear stream of 672 doubles, cut every 128: 6 pieces
     //   S_PG[w][28]    ground partial of frame f                 }   (18 pieces per frame; 20 with the 128-slot laser record, one piece per row)
-    // Round 4 measured what the staging costs and what does NOT change it (tools/quad_occ_probe2.sh, tools/quad_probe.py,
-    // tools/clk_probe_quad.py): issuing a frame's 26 pieces (21 since the packed wheel / ground records) stalls the wave for ~4 k of its ~18.6 k cycles; with two waves per SIMD (a
+    // Round 4 measured what the staging costs and what does NOT change it (tools/clk_probe_quad.py): issuing a frame's 26 pieces
+    // (21 since the packed wheel / ground records) stalls the wave for ~4 k of its ~18.6 k cycles; with two waves per SIMD (a
     // <= 256-register build, six waves per CU) the SAME phase takes 5 - 11 k per wave and the kernel is no faster — the other phases keep
     // their length, so the ALUs are not what the waves share.  Plain global_load_dwordx4 into registers + ds_write_b128 (25 pieces, in three
     // batches behind the elimination phases, or all at once held in AGPRs) stalls just as long at issue (~100 - 170 cycles per 1-KiB
@@ -389,7 +374,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
     // The 26 pieces of a frame as STRAIGHT-LINE code.  Round 3 issued each piece under its own lane mask (the last piece of a record does
     // not fill 64 lanes) and its own `block exists` test: 26 basic blocks of ~22 instructions each — a branch, the 64-bit scalar address
     // rebuilt from spilled SGPRs (v_readlane / v_writelane), m0 — ~580 instructions and ~4 k of a frame's ~18.6 k cycles with every record
-    // cache-resident (tools/clk_probe_quad.py under LIW_QUAD_PROBE=3: the phase is instruction-bound, not memory-bound).  Now every piece
+    // cache-resident (tools/clk_probe_quad.py on a probe build with every record aliased to window 0: the phase is instruction-bound, not memory-bound).  Now every piece
     // runs with all 64 lanes: lanes past the end of a record read on into whatever follows it in the workspace (always inside it) and their
     // 16 bytes land in the LDS words right behind the record's area — the start of the NEXT area in the layout, whose own piece is issued
     // later and overwrites them (loads of a wave return in order); behind the last area (ground) sits a 24-double pad.  The only test
@@ -403,7 +388,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
             sfor<0, 4>([&](auto W) {                // per-frame IMU record: 3 pieces per row (the immediate offset moves the global AND the LDS address)
                 constexpr int ws = KI(W);
                 const double* g = PI0 + rPI[ws] + (unsigned)(f * PIFS) + lane2;
-                sfor<0, 3>([&](auto Q) { __builtin_amdgcn_global_load_lds(g, (lds_t)(S + S_IMU + ws * PIFS), 16, KI(Q) * 1024, QNT1); });
+                sfor<0, 3>([&](auto Q) { __builtin_amdgcn_global_load_lds(g, (lds_t)(S + S_IMU + ws * PIFS), 16, KI(Q) * 1024, 0); });
             });
         }
         // compact laser group records of the four rows, wheel partials (block f-1; frame 0 re-reads block 0, unused) and ground partials: the
@@ -427,7 +412,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
                         if constexpr (st <= q0) off = v; else off = lane2 >= st - q0 ? v : off;
                     }
                 });
-                __builtin_amdgcn_global_load_lds(PW0 + off, (lds_t)(S + S_PL + q0), 16, 0, QNT1);
+                __builtin_amdgcn_global_load_lds(PW0 + off, (lds_t)(S + S_PL + q0), 16, 0, 0);
             });
         }
         asm volatile("" ::: "memory");
@@ -483,11 +468,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
         const unsigned off = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(TAB) + k * 128 + lane_tab);
         return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(S) + off);
     };
-#ifdef LIW_QUAD_TILE_ALIAS
-    double* ST = S + S_IMU + w * PIFS + PIF_IJ + 100;
-#else
     double* ST = S + S_TR + w * 90;               // ST[c * 6 + q]: carried arrow block of the frame in front, row c (lane c), hub variable q
-#endif
 
     // The arrow block a frame hands to the frame in front of it (R' = -Wo^T Wr: 15 rows x 6 hub variables) is accumulated TRANSPOSED: lane c
     // = its row c, register q = hub variable q — six registers and 90 DPP FMAs per frame instead of fifteen and 225 with the six busy
@@ -747,8 +728,8 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
             const unsigned of = oWS + (unsigned)(i * SOLVE_WS);
             sfor<0, 15>([&](auto K) {
                 constexpr int k = KI(K);
-                nt_store<32>(&WS[of + (unsigned)(k * REC_LD + (l15 ? 21 : j))], o[k]);
-                if (l6) nt_store<32>(&WS[of + (unsigned)(k * REC_LD + 15 + j)], rr[k]);
+                WS[of + (unsigned)(k * REC_LD + (l15 ? 21 : j))] = o[k];
+                if (l6) WS[of + (unsigned)(k * REC_LD + 15 + j)] = rr[k];
             });
         }
         QSTAMP(10);
@@ -817,7 +798,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
                     if constexpr (st <= q0) off = v; else off = lane2 >= st - q0 ? v : off;
                 }
             });
-            __builtin_amdgcn_global_load_lds(WS + off, (lds_t)(dst + q0), 16, 0, QNT2);
+            __builtin_amdgcn_global_load_lds(WS + off, (lds_t)(dst + q0), 16, 0, 0);
         });
         const unsigned* const X32 = reinterpret_cast<const unsigned*>(X);
         const unsigned* const L32 = reinterpret_cast<const unsigned*>(LMD);
@@ -834,7 +815,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
             // (X is the CALLER's array: the lanes behind the last row's 30 dwords re-read its first ones instead of reading on past the
             // end of the allocation; everything else staged here lies inside the workspace, where reading on is harmless)
             if constexpr (q0 + 64 > 120) off = ln >= 120 - q0 ? 2u * (rX[3] + fx) + (unsigned)(ln - (120 - q0)) : off;
-            __builtin_amdgcn_global_load_lds(X32 + off, (lds_t)(dst + RECP * 128 + KI(P) * 32), 4, 0, QNT2);
+            __builtin_amdgcn_global_load_lds(X32 + off, (lds_t)(dst + RECP * 128 + KI(P) * 32), 4, 0, 0);
         });
         sfor<0, LP_>([&](auto P) {                               // Jacobi scale (rows 0 .. 3), then LM diagonal (rows 0 .. 3)
             constexpr int q0 = KI(P) * 64;
@@ -846,7 +827,7 @@ __global__ __launch_bounds__(64, LIW_QUAD_OCC) void k_lm_step_quad(StepArgs a) {
                     if constexpr (st <= q0) off = v; else off = ln >= st - q0 ? v : off;
                 }
             });
-            __builtin_amdgcn_global_load_lds(L32 + off, (lds_t)(dst + RECP * 128 + XP * 32 + KI(P) * 32), 4, 0, QNT2);
+            __builtin_amdgcn_global_load_lds(L32 + off, (lds_t)(dst + RECP * 128 + XP * 32 + KI(P) * 32), 4, 0, 0);
         });
         asm volatile("" ::: "memory");
     };
@@ -946,8 +927,6 @@ extern "C" void liw_debug_quad_clk(int on, int block, int frame, int iteration, 
     if (out) (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_qclk), sizeof(long long) * 64);
 }
 void launch_lm_step_quad(const StepArgs& a, hipStream_t s) {
-    static const int probe = [] { const char* e = getenv("LIW_QUAD_PROBE"); const int v = e ? atoi(e) : 0; if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_qprobe), &v, sizeof(v)); return v; }();
-    (void)probe;
     hipLaunchKernelGGL(k_lm_step_quad, dim3((a.B + 3) / 4), dim3(64), 0, s, a);
 }
 

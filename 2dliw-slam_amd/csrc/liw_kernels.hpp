@@ -243,14 +243,10 @@ __device__ __forceinline__ void wave_mem_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// A/B aid: nontemporal hints on the streams a launch touches once (bits: 4 IMU frame records stored, 8 wheel / ground records stored,
-// 16 first-sweep LDS-DMA pieces of the quad step kernel, 32 its back-substitution record stored, 64 its second-sweep pieces)
-#ifndef LIW_NT_MASK
-#define LIW_NT_MASK 4       // measured per 49 152 C2 windows: 4 -> k_lin_imu_chain 2.19 -> 2.12 ms; 8 / 16 / 32 / 64: no change (left off)
-#endif
-template <int BIT, typename T> __device__ __forceinline__ void nt_store(T* p, T v) {
-    if constexpr ((LIW_NT_MASK & BIT) != 0) __builtin_nontemporal_store(v, p); else *p = v;
-}
+// nontemporal store for a stream a launch touches once.  Measured per 49 152 C2 windows on every such stream: the IMU frame records
+// stored k_lin_imu_chain 2.19 -> 2.12 ms (kept); the wheel / ground records stored, the first- and second-sweep LDS-DMA pieces of the
+// quad step kernel and its back-substitution record stored: no change (plain stores / default cache policy there)
+template <typename T> __device__ __forceinline__ void nt_store(T* p, T v) { __builtin_nontemporal_store(v, p); }
 
 // reciprocal square root / reciprocal from the hardware estimate + two Newton steps (7 / 5 instructions; the library rsqrt() and
 // an IEEE division expand to 3-4 times that, on the dependent chain of single-wave code)
@@ -350,12 +346,10 @@ void launch_laser_z_scan(long Ltot, const double* laser_pts, int* flag, hipStrea
 // k_laser_slab.hip: lane-per-(window, frame) laser role of large 2-D batches
 __host__ __device__ inline int laser_slab_count(int B) { return (B + 63) / 64; }   // slabs of 64 windows
 void launch_laser_slab_prepare(int B, int n, const int* group_off, int* perm, int* mx, long long* off, const int* hz, hipStream_t s);
-#ifndef LIW_SLAB_WPLANE
-#define LIW_SLAB_WPLANE 0     // 1: the re-pack appends the block's weight sqrt(min(len1, len2) / 0.04) (laser_factor.h:38-42, constant over the LM
-                              // iterations) as a ninth plane: -30 of a block's 274 VALU instructions for +12.5 % of row bytes.  Measured twice (round 5): the
-                              // kernel alone 1.51 -> 1.56 ms (it is bandwidth-bound), the linearise bracket 3.907 -> 3.897 ms, 130.2 k -> 130.7 k solves/s: off
-#endif
-constexpr int LASER_SLAB_ROWD = (8 + LIW_SLAB_WPLANE) * 64;      // doubles per packed row of k_laser_slab.hip
+// (a ninth plane with the block's weight sqrt(min(len1, len2) / 0.04) (laser_factor.h:38-42, constant over the LM iterations), appended by
+//  the re-pack: -30 of a block's 274 VALU instructions for +12.5 % of row bytes.  Measured twice (round 5): the kernel alone 1.51 -> 1.56 ms
+//  (it is bandwidth-bound), the linearise bracket 3.907 -> 3.897 ms, 130.2 k -> 130.7 k solves/s: not kept)
+constexpr int LASER_SLAB_ROWD = 8 * 64;      // doubles per packed row of k_laser_slab.hip
 void launch_laser_slab_pack(int B, int n, long Ltot, const int* group_off, const int* perm, const double* pts, const long long* off, const int* mx, double* pk, hipStream_t s);
 void launch_lin_laser_slab(const LinArgs& A, const DevParams& P, hipStream_t s);
 void launch_imu_pack(int B, int n, const double* imu_X, const double* imu_J, const double* imu_sqrtP, const double* imu_Dt, double* pk, int* bad, hipStream_t s);
