@@ -679,7 +679,7 @@ static int enqueue_solve(liw_ctx* c, const liw_batch* b, int mode, int K, void* 
     // launches).  Not under stream capture (the captured launch sequence cannot branch), not without the compacted list (small batches).
     hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &capst);
-    static const bool no_exit = std::getenv("LIW_NO_EARLY_EXIT") != nullptr;
+    const bool no_exit = std::getenv("LIW_NO_EARLY_EXIT") != nullptr;   // A/B / test aid (read per call): the fixed-length loop
     const bool can_exit = capst == hipStreamCaptureStatusNone && !no_exit && lin_builds_active_list(b->B, b->eval_small);
     int next_check = can_exit ? 3 : K + 1;
     for (int k = 0; k < K; ++k) {
@@ -729,6 +729,11 @@ int liw_batch_solve(liw_ctx* c, const liw_batch* b, int mode, int max_iters, voi
             (void)hipGraphDestroy(g);
             c->gkey = key;
         }
+        // A graph solve never packs laser rows (laser_slab_begin does not run under capture), and a replay runs none of the host code that
+        // would drop the rows of an earlier plain solve on these arrays: drop them here, on a cache hit as after a capture.  Otherwise the
+        // marginalisation behind this solve would take rows packed before the caller rewrote laser_pts for it (lpk_matches compares
+        // addresses, not contents).
+        c->lpk_on = false;
         HIPCHK(c, hipGraphLaunch(c->gexec, s));
         return LIW_OK;
     }

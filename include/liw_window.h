@@ -285,7 +285,7 @@ int liw_batch_exchange_unpack(liw_ctx* ctx, const liw_batch* b, int mode, int ca
  * windows are left, the more often), and stop launching once it is 0 — the launches of an iteration in which no window iterates cost ~0.2 ms per
  * 49 152 windows, two thirds of a batched tracking frame.  Results are bit-identical to the full-length loop (a finished window's kernels
  * return at once).  Not under stream capture (use_graph != 0, or `stream` being captured by the caller): the captured sequence runs every
- * iteration.  LIW_NO_EARLY_EXIT=1 restores the fixed-length loop. */
+ * iteration.  LIW_NO_EARLY_EXIT=1 (read at every call) restores the fixed-length loop. */
 int liw_batch_solve(liw_ctx* ctx, const liw_batch* b, int mode, int max_iters, void* ws, void* stream, int use_graph);
 /* marginalisation of every window of the batch (linearise in MARG topology + chain Schur + eigen sqrt);
  * sqrt_H [B][36], Delta_H [B][225], Delta_g [B][15] optional device outputs.  Batches above 256 windows run two kernels on `stream`
@@ -295,7 +295,8 @@ int liw_batch_solve(liw_ctx* ctx, const liw_batch* b, int mode, int max_iters, v
  * ctx-owned memory; liw_batch_marg_linearize on the SAME arrays (same laser_pts / laser_frame allocations, B, n, Ltot, ws) reads those rows
  * instead of the arrays — the reference marginalises the frames it has just solved (trajectory.cpp:446-479, :534-544).  A caller that
  * REWRITES laser_pts / laser_off / laser_frame in place between the solve and the marginalisation must start a new solve first (or hand
- * over other allocations): the rows are keyed by address and size, not by content. */
+ * over other allocations): the rows are keyed by address and size, not by content.  A graph solve (use_graph != 0) packs no rows and
+ * drops those of an earlier solve, on a replay of the cached graph too: the marginalisation behind it reads the arrays. */
 int liw_batch_marg_linearize(liw_ctx* ctx, const liw_batch* b, void* ws, void* stream);
 int liw_batch_marg_schur(liw_ctx* ctx, const liw_batch* b, void* ws, double* sqrt_H, double* Delta_H, double* Delta_g, void* stream);
 /* dense export of the assembled normal equations of buffer `buf` (tests / liw_linearize) */
