@@ -253,9 +253,11 @@ def marg_mpmath(J, R, keep=15, dps=50):
 
 
 # ------------------------------------------------------------------------------------------------ pre-integration (numpy)
-def imu_preint_numpy(prm, samples, t_start, t_end, bias6):
+def imu_preint_numpy(prm, samples, t_start, t_end, bias6, noise_rotation=None):
     """imu_preintegraption driven like trajectory.cpp:176-184: sample 0 seeds last_info, reset at t_start, add every later sample,
-    update_only_t(t_end), result = X, J, LLT(P^-1).matrixL()^T, Dt"""
+    update_only_t(t_end), result = X, J, LLT(P^-1).matrixL()^T, Dt.
+    noise_rotation: None, or a function of Rz whose value takes the place of Rz in the noise matrix G only (imu_preintegraption.h:196) —
+    for tests that ask whether their inputs would expose such a mistake (tests/test_second_config.py); never set by the generators."""
     Q = np.zeros((12, 12))
     Q[0:3, 0:3] = np.diag(np.square(prm["imu_noise_acc_sigma"]))
     Q[3:6, 3:6] = np.diag(np.square(prm["imu_noise_gyro_sigma"]))
@@ -282,7 +284,7 @@ def imu_preint_numpy(prm, samples, t_start, t_end, bias6):
         F[6:9, 6:9] = -hat(gyro - ba)          # the accelerometer bias, as written at imu_preintegraption.h:192
         F[6:9, 12:15] = -np.eye(3)
         G = np.zeros((15, 12))
-        G[3:6, 0:3] = -Rz
+        G[3:6, 0:3] = -(Rz if noise_rotation is None else noise_rotation(Rz))
         G[6:9, 3:6] = -np.eye(3)
         G[9:12, 6:9] = np.eye(3)
         G[12:15, 9:12] = np.eye(3)
@@ -370,14 +372,41 @@ def wheel_preint_numpy(prm, samples, t_start, t_end):
     return np.concatenate([delta[:3, :3].reshape(9), delta[:3, 3]]), sqrt_info, Dt
 
 
+def preint_cases(base, count=3, wheel_count=None):
+    """`count` IMU and `wheel_count` (default: as many) wheel intervals of the synthetic generator's own sample streams at the parameter
+    dict `base`, with the results of the numpy restatements above -> the `preint` record"""
+    synth = importlib.import_module("2dliw-slam_amd.synth")
+    wheel_count = count if wheel_count is None else wheel_count
+    out = {"imu": [], "wheel": []}
+    tr = synth._Truth(base)
+    rng = np.random.default_rng(77)
+    for k in range(count):
+        t0, t1 = 1.0 + 0.1 * k, 1.1 + 0.1 * k + 0.013 * k
+        ts = t0 - 0.004 + np.arange(int((t1 - t0) * 200) + 1) / 200.0
+        smp = np.zeros((len(ts), 7))
+        for i, t in enumerate(ts):
+            a, w = tr.imu(t)
+            smp[i] = np.concatenate([[t], a + rng.normal(0, 0.01, 3), w + rng.normal(0, 0.001, 3)])
+        bias = rng.normal(0.0, 1e-3, 6)
+        X, Jm, S, Dt = imu_preint_numpy(base, smp, t0, t1, bias)
+        out["imu"].append(dict(samples=smp.tolist(), t_start=t0, t_end=t1, bias=bias.tolist(), X=X.tolist(), J=Jm.tolist(), sqrt_inverse_P=S.tolist(), Dt=Dt))
+        tw = np.arange(t0 - 2.5 * 0.0505, t1, 0.0505)
+        ws = np.zeros((len(tw), 13))
+        for i, t in enumerate(tw):
+            T = tr.T_w_o(t)
+            ws[i] = np.concatenate([[t], T[:3, :3].reshape(9), T[:3, 3] + rng.normal(0, 2e-4, 3)])
+        if k < wheel_count:
+            T12, S3, Dtw = wheel_preint_numpy(base, ws, t0, t1)
+            out["wheel"].append(dict(samples=ws.tolist(), t_start=t0, t_end=t1, T=T12.tolist(), sqrt_inverse_P=S3.tolist(), Dt=Dtw))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     synth = importlib.import_module("2dliw-slam_amd.synth")
     from oracle import pyoracle
     base = synth.office_params()
-    prm = dict(base)
-    prm["iw"] = mg.extrinsic(base["T_imu_to_wheel"])
-    prm["il"] = mg.extrinsic(base["T_imu_to_laser"])
+    prm = mg.torch_params(base)
     orc = pyoracle.Oracle(base)   # pre-integration provider of the synthetic generator only
     path = os.path.join(HERE, "solver_golden.json")
     only = set(sys.argv[1:])                       # e.g. `make_golden_solver.py marg preint` recomputes those sections only
@@ -417,26 +446,7 @@ def main():
 
     # ---- preint: intervals of the synthetic generator's own sample streams
     if want("preint"):
-        out["preint"] = {"imu": [], "wheel": []}
-    tr = synth._Truth(base)
-    rng = np.random.default_rng(77)
-    for k in range(3) if want("preint") else ():
-        t0, t1 = 1.0 + 0.1 * k, 1.1 + 0.1 * k + 0.013 * k
-        ts = t0 - 0.004 + np.arange(int((t1 - t0) * 200) + 1) / 200.0
-        smp = np.zeros((len(ts), 7))
-        for i, t in enumerate(ts):
-            a, w = tr.imu(t)
-            smp[i] = np.concatenate([[t], a + rng.normal(0, 0.01, 3), w + rng.normal(0, 0.001, 3)])
-        bias = rng.normal(0.0, 1e-3, 6)
-        X, Jm, S, Dt = imu_preint_numpy(base, smp, t0, t1, bias)
-        out["preint"]["imu"].append(dict(samples=smp.tolist(), t_start=t0, t_end=t1, bias=bias.tolist(), X=X.tolist(), J=Jm.tolist(), sqrt_inverse_P=S.tolist(), Dt=Dt))
-        tw = np.arange(t0 - 2.5 * 0.0505, t1, 0.0505)
-        ws = np.zeros((len(tw), 13))
-        for i, t in enumerate(tw):
-            T = tr.T_w_o(t)
-            ws[i] = np.concatenate([[t], T[:3, :3].reshape(9), T[:3, 3] + rng.normal(0, 2e-4, 3)])
-        T12, S3, Dtw = wheel_preint_numpy(base, ws, t0, t1)
-        out["preint"]["wheel"].append(dict(samples=ws.tolist(), t_start=t0, t_end=t1, T=T12.tolist(), sqrt_inverse_P=S3.tolist(), Dt=Dtw))
+        out["preint"] = preint_cases(base)
     json.dump(out, open(path, "w"))
     print("wrote", path, os.path.getsize(path), "bytes")
 
