@@ -1,7 +1,7 @@
 // k_laser_frontend.hip — the batched laser front-end on the MI355X (C ABI include/liw_laser_batch.h): liw_laser.cpp's
 // tracking-time work for B robots at once, its output landing in the device arrays liw_batch takes.
 //
-// Mapping: one lane per (robot, scan), except spawn and the INIT window's match.  Every step of the host front-end is a serial chain over one scan (the 1 cm
+// Mapping: one lane per (robot, scan), except spawn, the INIT window's match and add_scan / rebuild.  Every step of the host front-end is a serial chain over one scan (the 1 cm
 // filter compares against the previously KEPT point, the segment merge carries `last`, a line's cells are de-duplicated against
 // its earlier cells, the mean match distance is summed in match order), so a lane walks its scan in the host's order and rounds
 // as the host does; the batch is the parallelism.
@@ -25,8 +25,17 @@
 //   k_lfe_match_wave  match_with_front of a whole INIT window, one wavefront per (robot, frame): lanes over the frame's lines, each
 //                  line's search once (best, d in LDS); the mean in line order, the pairs by ballot prefix on a running base:
 //                  bit-identical to k_lfe_match (tests/test_gpu_laser_init.py)
-//   k_lfe_add_scan laser_manager::add_scan: motion filter, fresh sub-maps, add_segment rasterisation, the swap
-//   k_lfe_reset_mgr   clear_all_scan that keeps the scan slots (liw_lfe_rebuild = this + add_scan per frame)
+//   k_lfe_add_scan_wave  laser_manager::add_scan (motion filter, fresh sub-maps, add_segment rasterisation, the swap) and the whole
+//                  liw_lfe_rebuild, one wavefront per robot: the manager's branch wave-uniform, a lane per source line for the fit
+//                  and the 0.05 m walk, ids and entry positions by prefix counts, the call's new entries sorted in LDS and merged
+//                  into the sorted sub-map in place (design and proof of the de-duplication at the kernel).  Same manager record,
+//                  sub-map headers, lines[0 .. n_lines) and ent[0 .. n_entries) as k_lfe_add_scan
+//                  (tests/test_gpu_laser_add_scan_wave.py); a target beyond the LDS buffer or the slot's capacity is built by
+//                  one lane with the lane kernel's code.  236 VGPRs, no scratch, 26 624 B of LDS at 256 lines: two waves per
+//                  SIMD by registers, six work-groups per CU by LDS.
+//   k_lfe_add_scan the lane-per-robot add_scan: the checker behind LIW_LFE_ADD_SCAN=lane, and the path of dimensions whose LDS
+//                  need exceeds a work-group's 64 KiB.  Both kernels write the LIW_LFE_ADD_* flags.
+//   k_lfe_reset_mgr   clear_all_scan that keeps the scan slots (the lane path of liw_lfe_rebuild = this + add_scan per frame)
 //   k_lfe_scan / k_lfe_pack   laser_off exclusive scan (one block), then the component-major laser arrays
 //   k_lfe_scan_init / k_lfe_pack_init   the same for INIT windows: blocks of frames 1 .. n-1, a work-group per window
 // The line_map of a slot is a list of 64-bit entries (cell key << 32 | line index) kept sorted: within a cell the host
@@ -225,15 +234,16 @@ struct Reg {
 
 // scan::add_line(points, index1, index2, add_concers) (laser_manager.cpp:137-212) without corners; from_points selects the
 // point-cell registration (spawn) over the 0.05 m rasterisation (sub-map segments)
-__device__ bool add_line(Slot& s, const Lay& L, const DP& P, const double* pts, int i1, int i2, bool from_points, unsigned& st) {
-    if (i2 - i1 < 2) return false;
+// the fit of add_line (moment sums in index order, eigenvector, max_dis, the projected end points) and its two rejections:
+// one body for the lane kernels and k_lfe_add_scan_wave, so that they round alike
+__device__ __forceinline__ bool line_fit(const DP& P, const double* pts, int i1, int i2, Vec& p1, Vec& p2, Vec& abc, double& len) {
     double M[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     for (int i = i1; i <= i2; ++i) {
         const double x = pts[i * 3], y = pts[i * 3 + 1];
         M[0][0] += x * x; M[0][1] += x * y; M[0][2] += x; M[1][1] += y * y; M[1][2] += y; M[2][2] += 1.0;
     }
     M[1][0] = M[0][1]; M[2][0] = M[0][2]; M[2][1] = M[1][2];
-    const Vec abc = smallest_eigvec3(M);
+    abc = smallest_eigvec3(M);
     Vec a(0, 0, 0), b(0, 0, 0);
     if (fabs(abc.y) < 0.5) {
         a.y = 0; a.x = -abc.z / abc.x; b.y = 1; b.x = (-abc.z - abc.y) / abc.x;
@@ -242,10 +252,18 @@ __device__ bool add_line(Slot& s, const Lay& L, const DP& P, const double* pts, 
     }
     double max_dis = 0;
     for (int i = i1; i <= i2; ++i) { const double d = dis_from_line(ld3(pts + 3 * i), a, b); max_dis = (max_dis < d) ? d : max_dis; }
-    const Vec p1 = project_to_line(ld3(pts + 3 * i1), a, b), p2 = project_to_line(ld3(pts + 3 * i2), a, b);
-    const double len = vnorm(vsub(p1, p2));
+    p1 = project_to_line(ld3(pts + 3 * i1), a, b);
+    p2 = project_to_line(ld3(pts + 3 * i2), a, b);
+    len = vnorm(vsub(p1, p2));
     if (max_dis > P.max_dis) return false;
     if (len < P.min_len) return false;
+    return true;
+}
+__device__ bool add_line(Slot& s, const Lay& L, const DP& P, const double* pts, int i1, int i2, bool from_points, unsigned& st) {
+    if (i2 - i1 < 2) return false;
+    Vec p1, p2, abc;
+    double len;
+    if (!line_fit(P, pts, i1, i2, p1, p2, abc, len)) return false;
     const int id = n_lines(s, L);
     if (id >= L.max_lines) { st |= LIW_LFE_ST_LINES; return false; }
     Reg g{s, L, P, st, id, n_entries(s, L), false, ~0ull};
@@ -1001,11 +1019,12 @@ __device__ inline void set_last(Mgr* m, const Iso<double>& T) {
 }
 
 // laser_manager::add_scan (:424-496) without the key-frame deque
-// pose of robot b at pose + b * pose_stride doubles (6 for a packed [B][6] array)
+// pose of robot b at pose + b * pose_stride doubles (6 for a packed [B][6] array); flags (may be null): LIW_LFE_ADD_* per robot
 __global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP P, int src_slot, const double* pose, long long pose_stride,
-                                                        const unsigned char* mask) {
+                                                        const unsigned char* mask, unsigned char* flags) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= L.B || (mask && !mask[b])) return;
+    if (b >= L.B) return;
+    if (mask && !mask[b]) { if (flags) flags[b] = 0; return; }
     Mgr* m = (Mgr*)robot_ptr(store, L, b);
     const Slot src = slot_at(store, L, b, src_slot);
     // an invalid source scan invalidates every sub-map this call writes (until that sub-map is replaced)
@@ -1017,14 +1036,16 @@ __global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP 
         const Iso<double> last = liw::cast_iso<double>(m->last_R, m->last_t);
         const Iso<double> d = liw::mul(liw::inverse(last), cur);
         const Vec dq = liw::log_SO3(d.R);
-        if (vnorm(d.t) < P.mf_p && vnorm(dq) < P.mf_q) return;
+        if (vnorm(d.t) < P.mf_p && vnorm(dq) < P.mf_q) { if (flags) flags[b] = 0; return; }
     } else {
         fresh_submap(store, L, P, b, m, m->ref_sub & 1, src, src_st, pq);
         m->has_ref = 1;
         set_last(m, cur);
         m->count = 1;
+        if (flags) flags[b] = LIW_LFE_ADD_ADDED | LIW_LFE_ADD_FIRST;
         return;
     }
+    unsigned fl = LIW_LFE_ADD_ADDED;
     const Iso<double> Ti = til(P);
     auto accumulate = [&](int sub) {
         const double sp[6] = {m->sub_p[sub][0], m->sub_p[sub][1], m->sub_p[sub][2], m->sub_q[sub][0], m->sub_q[sub][1], m->sub_q[sub][2]};
@@ -1050,6 +1071,7 @@ __global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP 
     if (!m->has_spawn && m->count == P.n_acc / 2) {
         fresh_submap(store, L, P, b, m, ss, src, src_st, pq);
         m->has_spawn = 1;
+        fl |= LIW_LFE_ADD_SPAWNED;
     }
     if (m->count == P.n_acc) {   // ref = spawning (which may not exist: the /2 quirk of ref_n_accumulation 2); spawning = fresh
         const int nr = 1 - rs;
@@ -1058,9 +1080,264 @@ __global__ void __launch_bounds__(kBlock) k_lfe_add_scan(void* store, Lay L, DP 
         fresh_submap(store, L, P, b, m, 1 - nr, src, src_st, pq);
         m->has_spawn = 1;
         m->count = P.n_acc / 2;
+        fl |= LIW_LFE_ADD_SWAPPED;
     }
     set_last(m, cur);
+    if (flags) flags[b] = (unsigned char)fl;
 }
+
+// ------------------------------------------------------------------------------------------------ wave-per-robot add_scan
+// One work-group of one wave per robot.  The manager's branch (make_tf, the motion filter, count, the n_acc / 2 spawn, the swap) is
+// evaluated by every lane from the same bytes with the device functions of k_lfe_add_scan, so it is wave-uniform and decides as
+// the lane kernel does; lane 0 writes the Mgr record.  The call's targets (reference, spawning sub-map, then the fresh
+// sub-maps) are independent slots and are done one after another by the one wave (add_target_wave).
+//
+// A target, in two passes over the source lines in chunks of 64, a lane per line:
+//   pass 1  apply + line_fit (the body of add_line) and a first walk of the lane's own segment, the lane kernel's
+//           `for (tr = 0; tr <= len; tr += 0.05)` with tr the running sum, which counts the line's cells.  Ids: the running n_lines
+//           plus the ballot prefix over the accepted lines with a valid cell; entry offsets: the running total plus the prefix sum
+//           of the counts.  The line record goes to lines[id] at once (bytes past the header's n_lines are nobody's until the
+//           header moves); id and offset of every source line stay in LDS (lid, loff [max_lines]).
+//   pass 2  the second walk writes (cell << 32 | id) at the line's offset of the new-entry buffer in LDS (nw [ecap]).
+// De-duplication: the lane kernel's backward search only meets cells of the line itself.  x = p1.x + unit.x * tr is monotone
+// in tr (a rounded product and a rounded sum are monotone in one operand), so are x / res + w / 2 and its truncation, and
+// likewise the row: the cell sequence of a walk is monotone in each coordinate and cannot return to a cell it has left, also
+// after the invalid cells are dropped.  Distinct cells = consecutive-distinct cells, which is what seg_cells keeps.
+// Then wave_sort of nw in LDS and the merge into the sorted old entries in place: the final index of new entry j is j + the
+// number of old entries below it (binary search, kept in pos [ecap] before anything moves), of old entry i it is i + the number of
+// new entries below it; the old entries move back to front in chunks of 64 (read, barrier, write: an entry only moves to an
+// index at or above its own, and everything above the chunk has moved), stopping at the first chunk nothing of which moves.
+// (cell, id) pairs are all distinct, so the sorted list, hence every byte below n_lines / n_entries, is the lane kernel's.
+// No atomics; positions are prefix counts.
+//
+// Escape: when pass 1 finds that the lane kernel would flag the target (an accepted line at id >= max_lines, or n_old + new >
+// max_cell_entries), or that the call's new entries exceed ecap (kAddNewCap), lane 0 alone runs the lane kernel's serial code
+// on that target (add_target_serial: add_segment + sort_entries), from the untouched header: the bytes of an overflowed
+// sub-map are then the lane kernel's too, and nothing is truncated.
+struct AddLds { unsigned nw, pos, lid, loff; int ecap; size_t total; };
+constexpr int kAddNewCap = 2048;   // new entries of one target held in LDS (24 KiB with pos); beyond it the serial escape
+inline AddLds add_lds(const Lay& L) {
+    AddLds O;
+    O.ecap = L.max_entries < kAddNewCap ? L.max_entries : kAddNewCap;
+    size_t o = 0;
+    O.nw = (unsigned)o; o += 8 * (size_t)O.ecap;
+    O.pos = (unsigned)o; o += up8(4 * (size_t)O.ecap);
+    O.lid = (unsigned)o; o += up8(4 * (size_t)L.max_lines);
+    O.loff = (unsigned)o; o += up8(4 * (size_t)L.max_lines);
+    O.total = o;
+    return O;
+}
+
+// the rasterisation walk of add_line for a segment: f(k, cell) for the k-th distinct valid cell; returns their number
+template <class F> __device__ __forceinline__ int seg_cells(const DP& P, const Vec& p1, const Vec& p2, double len, F f) {
+    const Vec unit = vunit_div(vsub(p2, p1));
+    unsigned last = ~0u;
+    int n = 0;
+    for (double tr = 0; tr <= len; tr += 0.05) {
+        const Vec t = vadd(p1, vscale(unit, tr));
+        int c, r;
+        xy_to_index(P, t.x, t.y, c, r);
+        if (!valid(P, r, c)) continue;
+        const unsigned cell = (unsigned)(r * P.w + c);
+        if (cell == last) continue;
+        last = cell;
+        f(n, cell);
+        ++n;
+    }
+    return n;
+}
+
+// one target of k_lfe_add_scan as the lane kernel does it (one lane); returns the status bits of the target
+__device__ unsigned add_target_serial(Slot s, const Lay& L, const DP& P, const Slot& src, const Iso<double>* xf, unsigned src_st) {
+    if (!xf) slot_clear(s, 0.0);
+    unsigned st = src_st;
+    for (int i = 0, nl = n_lines(src, L); i < nl; ++i) {
+        const Vec a = ld3(src.lines + 10 * (size_t)i), c = ld3(src.lines + 10 * (size_t)i + 3);
+        if (xf) add_segment(s, L, P, apply(*xf, a), apply(*xf, c), st);
+        else add_segment(s, L, P, a, c, st);
+    }
+    sort_entries(s.ent, n_entries(s, L));
+    if (xf) s.h->status |= (int)st;
+    else s.h->status = (int)st;
+    return st;
+}
+
+// one target by the wave: xf != null accumulates the transformed lines into the existing sub-map, xf == null makes it afresh from
+// the untransformed lines (fresh_submap).  Wave-uniform control flow; returns the target's status bits (uniform).
+__device__ unsigned add_target_wave(Slot s, const Lay& L, const DP& P, const AddLds& O, unsigned char* lds, const Slot& src, const Iso<double>* xf,
+                                    unsigned src_st, int lane) {
+    u64* nw = (u64*)(lds + O.nw);
+    int* pos = (int*)(lds + O.pos);
+    int* lid = (int*)(lds + O.lid);
+    int* loff = (int*)(lds + O.loff);
+    const int nl = n_lines(src, L);
+    const int n0l = xf ? n_lines(s, L) : 0, n0e = xf ? n_entries(s, L) : 0;
+    int run_l = n0l, tot = 0;
+    bool ovf = false;
+    for (int base = 0; base < nl; base += kBlock) {
+        const int i = base + lane;
+        bool acc = false;
+        int cnt = 0;
+        Vec p1, p2, abc;
+        double len = 0;
+        if (i < nl) {
+            Vec a = ld3(src.lines + 10 * (size_t)i), c = ld3(src.lines + 10 * (size_t)i + 3);
+            if (xf) { a = apply(*xf, a); c = apply(*xf, c); }
+            const Vec mid = Vec((c.x + a.x) / 2, (c.y + a.y) / 2, (c.z + a.z) / 2);   // add_segment
+            const double fake[9] = {a.x, a.y, a.z, mid.x, mid.y, mid.z, c.x, c.y, c.z};
+            acc = line_fit(P, fake, 0, 2, p1, p2, abc, len);
+            if (acc) cnt = seg_cells(P, p1, p2, len, [](int, unsigned) {});
+        }
+        const bool reg = acc && cnt > 0;
+        const u64 rm = __ballot(reg);
+        const int id = run_l + __popcll(rm & ((1ull << lane) - 1));
+        if (__ballot(acc && id >= L.max_lines)) ovf = true;
+        int total;
+        const int off = wave_excl(reg ? cnt : 0, lane, total);
+        if (ovf) break;
+        if (i < nl) { lid[i] = reg ? id : -1; loff[i] = tot + off; }
+        if (reg) {
+            double* o = s.lines + 10 * (size_t)id;
+            o[0] = p1.x; o[1] = p1.y; o[2] = p1.z; o[3] = p2.x; o[4] = p2.y; o[5] = p2.z; o[6] = abc.x; o[7] = abc.y; o[8] = abc.z; o[9] = len;
+        }
+        run_l += __popcll(rm);
+        tot += total;
+        if (tot > O.ecap || n0e + tot > L.max_entries) { ovf = true; break; }
+    }
+    __syncthreads();
+    if (ovf) {
+        unsigned st = 0;
+        if (lane == 0) st = add_target_serial(s, L, P, src, xf, src_st);
+        __syncthreads();
+        return (unsigned)__shfl((int)st, 0);
+    }
+    for (int base = 0; base < nl; base += kBlock) {
+        const int i = base + lane;
+        if (i < nl && lid[i] >= 0) {
+            const int id = lid[i], o0 = loff[i];
+            const double* o = s.lines + 10 * (size_t)id;   // this lane's own record of pass 1
+            seg_cells(P, ld3(o), ld3(o + 3), o[9], [&](int k, unsigned cell) { if (o0 + k < O.ecap) nw[o0 + k] = ((u64)cell << 32) | (unsigned)id; });   // o0 + k < tot <= ecap: the walk of pass 1
+        }
+    }
+    __syncthreads();
+    wave_sort(nw, tot, lane);
+    if (n0e == 0) {
+        for (int j = lane; j < tot; j += kBlock) s.ent[j] = nw[j];
+    } else if (tot > 0) {
+        for (int j = lane; j < tot; j += kBlock) pos[j] = j + lower_bound(s.ent, n0e, nw[j]);
+        __syncthreads();
+        for (int top = n0e; top > 0; top -= kBlock) {
+            const int i = top - kBlock + lane;
+            u64 v = 0;
+            int r = 0;
+            if (i >= 0) { v = s.ent[i]; r = lower_bound(nw, tot, v); }
+            __syncthreads();
+            if (r > 0) s.ent[i + r] = v;
+            __syncthreads();
+            if (!__ballot(r > 0)) break;
+        }
+        for (int j = lane; j < tot; j += kBlock) s.ent[pos[j]] = nw[j];
+    }
+    if (lane == 0) {
+        if (xf) s.h->status |= (int)src_st;
+        else { s.h->status = (int)src_st; s.h->time = 0.0; }
+        s.h->n_lines = run_l;
+        s.h->n_entries = n0e + tot;
+    }
+    __syncthreads();
+    return src_st;
+}
+
+// add_scan of one robot's scan slot by its wave; returns the LIW_LFE_ADD_* flags (uniform)
+__device__ unsigned add_scan_wave_one(void* store, const Lay& L, const DP& P, const AddLds& O, unsigned char* lds, int b, int src_slot, const double* pq,
+                                      int lane) {
+    Mgr* m = (Mgr*)robot_ptr(store, L, b);
+    const Slot src = slot_at(store, L, b, src_slot);
+    const unsigned src_st = src.h->status ? ((unsigned)src.h->status | LIW_LFE_ST_INVALID) : 0u;
+    unsigned mst = (unsigned)m->status | src_st;
+    int has_ref = m->has_ref, has_spawn = m->has_spawn, count = m->count;
+    const int rs = m->ref_sub & 1, ss = 1 - rs;
+    int ref_sub = m->ref_sub;
+    auto fresh = [&](int sub) {   // fresh_submap
+        mst |= add_target_wave(slot_at(store, L, b, L.slots + sub), L, P, O, lds, src, nullptr, src_st, lane);
+        if (lane == 0)
+            for (int k = 0; k < 3; ++k) { m->sub_p[sub][k] = pq[k]; m->sub_q[sub][k] = pq[3 + k]; }
+    };
+    if (has_ref) {
+        const Iso<double> last = liw::cast_iso<double>(m->last_R, m->last_t);
+        const Iso<double> d = liw::mul(liw::inverse(last), tf6(pq));
+        const Vec dq = liw::log_SO3(d.R);
+        if (vnorm(d.t) < P.mf_p && vnorm(dq) < P.mf_q) {
+            if (lane == 0) m->status = (int)mst;
+            return 0u;
+        }
+    } else {
+        fresh(rs);
+        if (lane == 0) { m->status = (int)mst; m->has_ref = 1; set_last(m, tf6(pq)); m->count = 1; }
+        return LIW_LFE_ADD_ADDED | LIW_LFE_ADD_FIRST;
+    }
+    unsigned fl = LIW_LFE_ADD_ADDED;
+    const Iso<double> Ti = til(P);
+    auto accumulate = [&](int sub) {
+        const double sp[6] = {m->sub_p[sub][0], m->sub_p[sub][1], m->sub_p[sub][2], m->sub_q[sub][0], m->sub_q[sub][1], m->sub_q[sub][2]};
+        const Iso<double> rel = liw::mul(liw::inverse(tf6(sp)), tf6(pq));   // make_tf of the pose again, not kept live across the targets
+        return liw::mul(liw::mul(liw::inverse(Ti), rel), Ti);
+    };
+    {   // one transform live at a time (registers); both sub-map poses are read before a fresh sub-map below replaces them
+        const Iso<double> l_ref = accumulate(rs);
+        mst |= add_target_wave(slot_at(store, L, b, L.slots + rs), L, P, O, lds, src, &l_ref, src_st, lane);
+    }
+    if (has_spawn) {
+        const Iso<double> l_sp = accumulate(ss);
+        mst |= add_target_wave(slot_at(store, L, b, L.slots + ss), L, P, O, lds, src, &l_sp, src_st, lane);
+    }
+    ++count;
+    if (!has_spawn && count == P.n_acc / 2) {
+        fresh(ss);
+        has_spawn = 1;
+        fl |= LIW_LFE_ADD_SPAWNED;
+    }
+    if (count == P.n_acc) {
+        const int nr = 1 - rs;
+        has_ref = has_spawn;
+        ref_sub = nr;
+        fresh(1 - nr);
+        has_spawn = 1;
+        count = P.n_acc / 2;
+        fl |= LIW_LFE_ADD_SWAPPED;
+    }
+    if (lane == 0) {
+        m->status = (int)mst; m->has_ref = has_ref; m->has_spawn = has_spawn; m->ref_sub = ref_sub; m->count = count;
+        set_last(m, tf6(pq));
+    }
+    return fl;
+}
+
+// liw_lfe_add_scan (F = 1, reset = 0) and liw_lfe_rebuild (reset = 1: k_lfe_reset_mgr, then frames 0 .. F-1 in program order) for
+// robot b = blockIdx.x; pose of frame k at pose + b * robot_stride + k * frame_stride; flags (may be null): of the last frame
+__global__ void __launch_bounds__(kBlock) k_lfe_add_scan_wave(void* store, Lay L, DP P, AddLds O, int first_slot, int F, int reset, const double* pose,
+                                                             long long robot_stride, long long frame_stride, const unsigned char* mask,
+                                                             unsigned char* flags) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= L.B) return;
+    if (mask && !mask[b]) {
+        if (flags && lane == 0) flags[b] = 0;
+        return;
+    }
+    if (reset) {
+        ((int*)robot_ptr(store, L, b))[lane] = 0;   // kMgrBytes = 64 lanes x 4
+        if (lane < 2) { Slot s = slot_at(store, L, b, L.slots + lane); slot_clear(s, 0.0); }
+        __syncthreads();
+    }
+    unsigned fl = 0;
+    for (int k = 0; k < F; ++k) {
+        fl = add_scan_wave_one(store, L, P, O, lds, b, first_slot + k, pose + (long long)b * robot_stride + (long long)k * frame_stride, lane);
+        __syncthreads();
+    }
+    if (flags && lane == 0) flags[b] = (unsigned char)fl;
+}
+static_assert(kMgrBytes == 4 * kBlock, "k_lfe_add_scan_wave clears the manager record a lane per word");
 
 // laser_off = exclusive scan of count (one block of 1024; counts clamped to [0, cap])
 __global__ void __launch_bounds__(1024) k_lfe_scan(int B, int cap, const int* count, int* off) {
@@ -1187,6 +1464,7 @@ struct liw_lfe_ctx {
     float2* d_cs = nullptr;
     int n_rays = 0;
     float tinc = 0.0f;
+    int add_path = -1;   // the kernel of the last add_scan / rebuild: 0 lane, 1 wave (liw_lfe_add_scan_path)
 };
 
 namespace {
@@ -1240,6 +1518,31 @@ int spawn_launch(liw_lfe_ctx* c, void* store, int slot, const double* pts, const
     else
         hipLaunchKernelGGL(k_lfe_spawn_wave, dim3(c->L.B), dim3(kBlock), O.total, (hipStream_t)stream, store, c->L, c->P, O, slot, pts, n_pts, times,
                            max_corners, corners, n_corners);
+    return launched(c);
+}
+// liw_lfe_add_scan(_flags) (F = 1, reset = false) and liw_lfe_rebuild: the wave-per-robot kernel in one launch unless
+// LIW_LFE_ADD_SCAN=lane (read per call) asks for the lane-per-robot kernel, or the dimensions need more LDS than a work-group has
+int add_scan_launch(liw_lfe_ctx* c, void* store, int first_slot, int F, bool reset, const double* poses, long long robot_stride, long long frame_stride,
+                    const unsigned char* mask, unsigned char* flags, void* stream) {
+    const char* env = std::getenv("LIW_LFE_ADD_SCAN");
+    bool lane = false;
+    if (env && *env) {
+        if (!std::strcmp(env, "lane")) lane = true;
+        else if (std::strcmp(env, "wave")) return fail(c, LIW_EINVAL, "LIW_LFE_ADD_SCAN must be lane or wave");
+    }
+    const AddLds O = add_lds(c->L);
+    hipStream_t s = (hipStream_t)stream;
+    if (lane || O.total > kWaveLdsMax) {
+        c->add_path = 0;
+        if (reset) hipLaunchKernelGGL(k_lfe_reset_mgr, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, s, store, c->L, mask);
+        for (int k = 0; k < F; ++k)
+            hipLaunchKernelGGL(k_lfe_add_scan, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, s, store, c->L, c->P, first_slot + k,
+                               poses + (long long)k * frame_stride, robot_stride, mask, flags);
+    } else {
+        c->add_path = 1;
+        hipLaunchKernelGGL(k_lfe_add_scan_wave, dim3(c->L.B), dim3(kBlock), O.total, s, store, c->L, c->P, O, first_slot, F, reset ? 1 : 0, poses,
+                           robot_stride, frame_stride, mask, flags);
+    }
     return launched(c);
 }
 }  // namespace
@@ -1370,8 +1673,19 @@ int liw_lfe_match(liw_lfe_ctx* c, void* store, int slot1, int slot2, const doubl
 int liw_lfe_add_scan(liw_lfe_ctx* c, void* store, int src_slot, const double* pose, const unsigned char* mask, void* stream) {
     LFE_DEV(c);
     if (!store || !pose || src_slot < 0 || src_slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_add_scan: bad argument");
-    hipLaunchKernelGGL(k_lfe_add_scan, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, src_slot, pose, 6LL, mask);
-    return launched(c);
+    return add_scan_launch(c, store, src_slot, 1, false, pose, 6LL, 0LL, mask, nullptr, stream);
+}
+
+int liw_lfe_add_scan_flags(liw_lfe_ctx* c, void* store, int src_slot, const double* pose, const unsigned char* mask, unsigned char* flags, void* stream) {
+    LFE_DEV(c);
+    if (!store || !pose || !flags || src_slot < 0 || src_slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_add_scan_flags: bad argument");
+    return add_scan_launch(c, store, src_slot, 1, false, pose, 6LL, 0LL, mask, flags, stream);
+}
+
+int liw_lfe_add_scan_path(liw_lfe_ctx* c) {
+    if (!c) return LIW_EINVAL;
+    if (!c->have_device) return fail(c, LIW_ENODEV, "no usable gfx950 device (no CPU fallback)");
+    return c->add_path < 0 ? fail(c, LIW_EINVAL, "liw_lfe_add_scan_path: no add_scan or rebuild yet") : c->add_path;
 }
 
 int liw_lfe_pack_track(liw_lfe_ctx* c, int n, int frame, int cap, const int* count, const double* recs, const double* match_pose, int L_cap,
@@ -1436,12 +1750,7 @@ int liw_lfe_rebuild(liw_lfe_ctx* c, void* store, int first_slot, int F, const do
                     const unsigned char* mask, void* stream) {
     LFE_DEV(c);
     if (!store || !poses || F < 1 || first_slot < 0 || (long long)first_slot + F > c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_rebuild: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_lfe_reset_mgr, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, s, store, c->L, mask);
-    for (int k = 0; k < F; ++k)
-        hipLaunchKernelGGL(k_lfe_add_scan, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, s, store, c->L, c->P, first_slot + k,
-                           poses + (long long)k * frame_stride, robot_stride, mask);
-    return launched(c);
+    return add_scan_launch(c, store, first_slot, F, true, poses, robot_stride, frame_stride, mask, nullptr, stream);
 }
 
 int liw_lfe_status(liw_lfe_ctx* c, const void* store, int robot, int slot) {

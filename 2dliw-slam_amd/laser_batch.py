@@ -15,9 +15,11 @@ LFE_EXPORTS = [
     "liw_lfe_ranges_to_points", "liw_lfe_deskew", "liw_lfe_spawn", "liw_lfe_match", "liw_lfe_add_scan", "liw_lfe_pack_track",
     "liw_lfe_status", "liw_lfe_num_lines", "liw_lfe_get_lines", "liw_lfe_cell_lines", "liw_lfe_submap_pose",
     "liw_lfe_spawn_corners", "liw_lfe_corners_to_world", "liw_lfe_match_front", "liw_lfe_pack_init", "liw_lfe_rebuild",
+    "liw_lfe_add_scan_flags", "liw_lfe_add_scan_path",
 ]
 
 ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID, ST_CORNERS = 1, 2, 4, 8, 16, 32
+ADD_ADDED, ADD_FIRST, ADD_SPAWNED, ADD_SWAPPED = 1, 2, 4, 8   # LIW_LFE_ADD_*: what an add_scan did for a robot
 REF, SPAWNING, ROBOT = -1, -2, -3
 NONE = -61   # LIW_LFE_NONE: a getter's "no such sub-map / outside the grid" (the Python getters turn it into -1 / None)
 
@@ -55,6 +57,8 @@ def _lib():
         L.liw_lfe_corners_to_world.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
         L.liw_lfe_match.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_add_scan.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+        L.liw_lfe_add_scan_flags.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+        L.liw_lfe_add_scan_path.argtypes = [vp]
         L.liw_lfe_pack_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         ll = C.c_longlong
         L.liw_lfe_match_front.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, ll, ll, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -261,11 +265,26 @@ class BatchFrontEnd:
         """laser_manager::match_with_ref of scan `slot` at pose [B, 6]"""
         return self.match(REF, slot, None, pose, 0, cap)
 
-    def add_scan(self, slot, pose, mask=None):
-        """laser_manager::add_scan of scan `slot` at pose [B, 6] (the key-frame deque stays with the caller)"""
-        p = self._t(pose, self.torch.float64, (self.B, 6))
+    def add_scan(self, slot, pose, mask=None, flags=False):
+        """laser_manager::add_scan of scan `slot` at pose [B, 6] (the key-frame deque stays with the caller).  flags=True returns
+        what the call did per robot, a [B] uint8 tensor of ADD_* bits (0: masked out or dropped by the motion filter); flags may
+        also be such a tensor to write into.  The environment's LIW_LFE_ADD_SCAN=lane selects the lane-per-robot kernel for the
+        call (add_scan_path() tells which one ran)."""
+        torch = self.torch
+        p = self._t(pose, torch.float64, (self.B, 6))
         m = self._mask(mask)
-        self._chk(self.L.liw_lfe_add_scan(self.h, self._p(self.store), int(slot), self._p(p), self._p(m), self._s()))
+        if flags is False or flags is None:
+            self._chk(self.L.liw_lfe_add_scan(self.h, self._p(self.store), int(slot), self._p(p), self._p(m), self._s()))
+            return None
+        if flags is True:
+            flags = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+        assert torch.is_tensor(flags) and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.device == self.dev and flags.numel() >= self.B
+        self._chk(self.L.liw_lfe_add_scan_flags(self.h, self._p(self.store), int(slot), self._p(p), self._p(m), self._p(flags), self._s()))
+        return flags
+
+    def add_scan_path(self):
+        """the kernel the last add_scan / rebuild launched: 0 lane-per-robot, 1 wave-per-robot (LiwError before any)"""
+        return self._chk(self.L.liw_lfe_add_scan_path(self.h))
 
     def pack_track(self, m, n=2, frame=1, out=None, L_cap=None, bufs=None):
         """the laser arrays of B n-frame windows whose laser frame is `frame`, from a match() result.  out: dict with `match_pose`

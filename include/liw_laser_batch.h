@@ -129,8 +129,37 @@ int liw_lfe_match(liw_lfe_ctx* ctx, void* store, int slot1, int slot2, const dou
 /* laser_manager::add_scan of scan slot `src_slot` at pose [B][6] for the robots with mask[b] != 0 (all when NULL): motion filter,
  * first-scan sub-map, rasterisation into the reference and spawning sub-maps, the ref_n_accumulation swap.  The key-frame deque
  * stays with the caller.  An invalid source slot makes every sub-map the call writes invalid (its status and
- * LIW_LFE_ST_INVALID), so matches against it have count 0 until that sub-map is replaced. */
+ * LIW_LFE_ST_INVALID), so matches against it have count 0 until that sub-map is replaced.
+ * Mapping: one wavefront per robot (k_lfe_add_scan_wave).  The manager's decisions are wave-uniform and made with the device
+ * functions of the lane-per-robot kernel; a lane fits and rasterises one source line (chunks of 64), line ids and entry positions
+ * are prefix counts, the call's new entries are sorted in LDS and merged into the sorted old ones in place.  LDS: 12 bytes per
+ * new entry of a call (at most 2 048 held) and 8 per line of max_lines.  The lane-per-robot kernel (k_lfe_add_scan) is the checker:
+ * the environment's LIW_LFE_ADD_SCAN=lane, read per call, selects it (=wave: the default), and it takes every call whose
+ * dimensions need more than 64 KiB of LDS.
+ * Equal between the two kernels, bit for bit: the robot's manager record and status word, and of every sub-map slot its
+ * header, lines[0 .. n_lines) and entries[0 .. n_entries) (tests/test_gpu_laser_add_scan_wave.py).  A target whose new entries
+ * exceed what the wave holds in LDS, or that overflows max_lines / max_cell_entries, is built by one lane with the lane kernel's
+ * code, so the same holds for it; of an overflowed sub-map (LIW_LFE_ST_LINES / _CELLS) callers may rely only on its status
+ * words, the manager record, count 0 of every match against it, and that nothing outside the robot's region is written: which
+ * lines and entries it keeps is unspecified. */
 int liw_lfe_add_scan(liw_lfe_ctx* ctx, void* store, int src_slot, const double* pose, const unsigned char* mask, void* stream);
+
+/* what liw_lfe_add_scan_flags did for robot b */
+#define LIW_LFE_ADD_ADDED 1    /* passed the motion filter, or was the first scan: the sub-maps changed */
+#define LIW_LFE_ADD_FIRST 2    /* created the first reference sub-map */
+#define LIW_LFE_ADD_SPAWNED 4  /* created the spawning sub-map at count == ref_n_accumulation / 2 */
+#define LIW_LFE_ADD_SWAPPED 8  /* count reached ref_n_accumulation: reference := spawning (which may not exist), fresh spawning */
+
+/* liw_lfe_add_scan that also reports what it did: flags [B] bytes, 0 for a robot that is masked out or whose scan the motion
+ * filter dropped, otherwise the OR of LIW_LFE_ADD_*.  After LIW_LFE_ADD_SWAPPED every later match against LIW_LFE_REF uses the new
+ * reference, and with ref_n_accumulation = 2 the robot may have no reference at all until its next added scan
+ * (LIW_LFE_ADD_FIRST again).  LIW_EINVAL for a null flags; in every other respect the same call. */
+int liw_lfe_add_scan_flags(liw_lfe_ctx* ctx, void* store, int src_slot, const double* pose, const unsigned char* mask, unsigned char* flags,
+                           void* stream);
+
+/* the kernel the last liw_lfe_add_scan / _flags / liw_lfe_rebuild of this ctx launched: 0 lane-per-robot, 1 wave-per-robot;
+ * LIW_EINVAL before any such call.  Host-only state, but LIW_ENODEV without a device like every call that needs one. */
+int liw_lfe_add_scan_path(liw_lfe_ctx* ctx);
 
 /* The laser arrays of a liw_batch of B n-frame windows whose laser blocks all belong to frame `frame` (n = 2 tracking: 1), from a
  * liw_lfe_match output (count, recs with row stride cap, match_pose):
@@ -179,7 +208,9 @@ int liw_lfe_pack_init(liw_lfe_ctx* ctx, int n, int cap, const int* count, const 
 /* The sub-map rebuild after init_solve: for the robots with mask[b] != 0 (all when NULL) laser_manager::clear_all_scan on the manager
  * alone (state, status word, both sub-maps; every scan slot is kept), then liw_lfe_add_scan of scan slot first_slot + k at pose k for
  * k = 0 .. F-1 in order (motion filter, first-scan sub-map, the ref_n_accumulation swap, invalid-source propagation).  Poses strided
- * as in liw_lfe_match_front, with k = 0 the window's first frame.  LIW_EINVAL: F < 1, first_slot < 0, first_slot + F > slots. */
+ * as in liw_lfe_match_front, with k = 0 the window's first frame.  LIW_EINVAL: F < 1, first_slot < 0, first_slot + F > slots.
+ * One launch: the robot's wavefront resets its manager and walks the F frames itself, program order standing in for the launch
+ * boundaries; the store's bytes are those of the F + 1 launches of the lane path (LIW_LFE_ADD_SCAN=lane), as for liw_lfe_add_scan. */
 int liw_lfe_rebuild(liw_lfe_ctx* ctx, void* store, int first_slot, int F, const double* poses, long long robot_stride, long long frame_stride,
                     const unsigned char* mask, void* stream);
 

@@ -3,14 +3,17 @@
 B robots (default 4 096 and 49 152) with 1 080-ray scans tiled from 64 distinct rooms / poses.  Per B: ranges -> points, spawn
 (spawn_ms: the default wave-per-scan kernel, with min / max of the repetitions; spawn_lane_ms: the lane-per-scan kernel selected
 by LIW_LFE_SPAWN=lane; spawn_corners_ms: the default kernel also writing the corners, corners_per_robot of them),
-match against the reference sub-map, add_scan (the accumulating call: the reference exists) and pack_track, each timed with
+match against the reference sub-map, add_scan (the accumulating call: the reference exists; add_scan_ms: the default
+wave-per-robot kernel, add_scan_lane_ms: the lane-per-robot kernel selected by LIW_LFE_ADD_SCAN=lane, both with min / max, and
+add_scan_path: what the default dispatch ran, 1 = wave) and pack_track, each timed with
 HIP events on the current stream (median of --reps after one warm-up); scans/s = B / ms.  For comparison the same line carries
 the host front-end (liw.laser through ctypes) per scan over 256 robots: laser_to_points, Scan.spawn, match_with_ref, add_scan.
 
 --init N adds the initialisation of a fleet (key "init", per B of --init-B): N scans per robot in N scan slots, then
 match_front_ms (F = N - 1 frames against slot 0 in one launch of the wave-per-(robot, frame) kernel), lane_match_ms (the same
-work as N - 1 calls of the lane-per-robot match, outputs reused), pack_init_ms (incl. the Ltot read-back) and rebuild_ms, each
-with min / max, the ratio lane / wave, and whether the two paths' counts agree.  --B "" runs that leg alone.
+work as N - 1 calls of the lane-per-robot match, outputs reused), pack_init_ms (incl. the Ltot read-back), rebuild_ms (the default:
+one launch of the wave-per-robot add_scan kernel) and rebuild_lane_ms (LIW_LFE_ADD_SCAN=lane: the reset and N launches), each
+with min / max, the ratios lane / wave, and whether the two paths' counts and rebuilt stores' headers agree.  --B "" runs that leg alone.
 
   python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5] [--init 30 [--init-B 4096]]
 """
@@ -131,8 +134,14 @@ def device_run(liw, torch, lp, B, sc, reps, cap=256, max_corners=64):
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1)
-    add_b()
-    out["add_scan_ms"] = float(np.median([add_b() for _ in range(reps)]))
+    def add_timed(key):
+        add_b()
+        ts = [add_b() for _ in range(reps)]
+        out[key + "_ms"], out[key + "_min_ms"], out[key + "_max_ms"] = float(np.median(ts)), float(min(ts)), float(max(ts))
+    add_timed("add_scan")
+    out["add_scan_path"] = fe.add_scan_path()
+    with_env("LIW_LFE_ADD_SCAN", "lane", lambda: add_timed("add_scan_lane"))
+    out["add_scan_lane_over_default"] = out["add_scan_lane_ms"] / out["add_scan_ms"]
     fresh()
     m = fe.match_with_ref(1, PB, cap=cap)
     mbufs = {k: m[k] for k in ("count", "recs", "idx1", "idx2", "match_pose")}   # outputs allocated outside the timed region
@@ -212,6 +221,14 @@ def init_run(liw, torch, lp, B, N, nd, reps, cap=256):
     out["pack_init_min_ms"], out["pack_init_max_ms"] = sp
     out["rebuild_ms"] = timed(torch, lambda: fe.rebuild(0, N, poses), reps, sp)
     out["rebuild_min_ms"], out["rebuild_max_ms"] = sp
+    out["rebuild_path"] = fe.add_scan_path()
+    torch.cuda.synchronize()
+    mgr_default = fe.store.view(B, -1)[:, :256].clone()
+    out["rebuild_lane_ms"] = with_env("LIW_LFE_ADD_SCAN", "lane", lambda: timed(torch, lambda: fe.rebuild(0, N, poses), reps, sp))
+    out["rebuild_lane_min_ms"], out["rebuild_lane_max_ms"] = sp
+    out["rebuild_lane_over_default"] = out["rebuild_lane_ms"] / out["rebuild_ms"]
+    torch.cuda.synchronize()
+    out["rebuild_managers_agree"] = bool(torch.equal(mgr_default, fe.store.view(B, -1)[:, :256]))
     out["Ltot"], out["pairs_per_frame"], out["init_ok"] = int(Ltot), Ltot / (B * F), int(ok.sum().item())
     del fe
     torch.cuda.empty_cache()
