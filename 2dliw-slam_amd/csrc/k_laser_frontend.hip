@@ -36,6 +36,11 @@
 //   k_lfe_add_scan the lane-per-robot add_scan: the checker behind LIW_LFE_ADD_SCAN=lane, and the path of dimensions whose LDS
 //                  need exceeds a work-group's 64 KiB.  Both kernels write the LIW_LFE_ADD_* flags.
 //   k_lfe_reset_mgr   clear_all_scan that keeps the scan slots (the lane path of liw_lfe_rebuild = this + add_scan per frame)
+//   k_lfe_track_init / _begin / _end   the glue of a tracking frame on a 256-byte record per robot (last_keyframe_tf,
+//                  current_angular_local, stamp, counters): the de-skew twist, the min_delta_t gate, the window roll and the pose
+//                  prediction from the wheel increment before the scan; the key-frame decision after the solve.  A lane per robot,
+//                  work-groups of 256, no LDS, no atomics, no scratch; _begin evaluates its sin / cos / atan2
+//                  correctly rounded (liw_crmath.hpp)
 //   k_lfe_scan / k_lfe_pack   laser_off exclusive scan (one block), then the component-major laser arrays
 //   k_lfe_scan_init / k_lfe_pack_init   the same for INIT windows: blocks of frames 1 .. n-1, a work-group per window
 // The line_map of a slot is a list of 64-bit entries (cell key << 32 | line index) kept sorted: within a cell the host
@@ -56,6 +61,7 @@
 
 #include "../../include/liw_laser_batch.h"
 #include "liw_dual.hpp"
+#include "liw_crmath.hpp"
 
 void liw_normalize_rotation_host(double* R9);   // liw_capi.hip (params.cpp:44-54 round trip)
 
@@ -1450,6 +1456,109 @@ __global__ void __launch_bounds__(256) k_lfe_pack_init(int B, int n, int cap, in
     }
 }
 
+// ------------------------------------------------------------------------------------------------------ tracking glue
+// lvio_2d::trajectory::add_sensor_data(laser) around the stages above (trajectory.cpp:140-148, :176-184, :82-92, the key-frame
+// decision after do_tracking).  A lane per robot: a few hundred fp64 operations and a handful of strided 8-byte accesses each.
+struct Trk {               // tracking record of one robot (256 bytes, caller-owned, apart from the store)
+    double kf_R[9], kf_t[3];   // last_keyframe_tf
+    double ang[3];             // current_angular_local
+    double stamp;              // of the last accepted frame
+    int tracked, keys, skipped, pad;
+};
+constexpr size_t kTrkBytes = 256;
+static_assert(sizeof(Trk) <= kTrkBytes, "tracking record");
+struct TP { double Tiw_R[9], Tiw_t[3], min_dt, p_thr, q_thr; };
+__host__ __device__ inline Trk* trk_at(void* track, int b) { return (Trk*)((char*)track + (size_t)b * kTrkBytes); }
+
+__global__ void __launch_bounds__(256) k_lfe_track_init(int B, void* track, const double* x, long long robot_stride, const double* ang,
+                                                       const unsigned char* mask) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || (mask && !mask[b])) return;
+    Trk* t = trk_at(track, b);
+    const Iso<double> T = tf6(x + (long long)b * robot_stride);
+    double* z = (double*)t;
+    for (size_t k = 0; k < kTrkBytes / 8; ++k) z[k] = 0.0;
+    for (int k = 0; k < 9; ++k) t->kf_R[k] = T.R.m[k];
+    t->kf_t[0] = T.t.x; t->kf_t[1] = T.t.y; t->kf_t[2] = T.t.z;
+    if (ang) for (int k = 0; k < 3; ++k) t->ang[k] = ang[3 * (size_t)b + k];
+}
+
+// A double whose sin / cos / atan2 are the correctly rounded ones of liw_crmath.hpp; + - * / sqrt are the IEEE operations either
+// way.  k_lfe_track_begin runs liw_dual.hpp's make_tf / exp_so3 / log_SO3 on it: its twist goes into the de-skew of every point and
+// its pose is where the solve starts, and what a last-bit difference against the host's libm there becomes after a few free-running
+// solves is measured in docs/WIDENING.md ("Fleet tracking frame").
+struct CR {
+    double v;
+    __host__ __device__ CR() : v(0.0) {}
+    __host__ __device__ CR(double c) : v(c) {}  // NOLINT(implicit)
+};
+__host__ __device__ inline CR operator+(const CR& a, const CR& b) { return CR(a.v + b.v); }
+__host__ __device__ inline CR operator-(const CR& a, const CR& b) { return CR(a.v - b.v); }
+__host__ __device__ inline CR operator-(const CR& a) { return CR(-a.v); }
+__host__ __device__ inline CR operator*(const CR& a, const CR& b) { return CR(a.v * b.v); }
+__host__ __device__ inline CR operator/(const CR& a, const CR& b) { return CR(a.v / b.v); }
+__host__ __device__ inline bool operator>(const CR& a, const CR& b) { return a.v > b.v; }
+__host__ __device__ inline bool operator<(const CR& a, const CR& b) { return a.v < b.v; }
+__host__ __device__ inline CR dsqrt(const CR& a) { return CR(sqrt(a.v)); }
+__host__ __device__ inline CR dsin(const CR& a) { return CR(liw_cr::cr_sin(a.v)); }
+__host__ __device__ inline CR dcos(const CR& a) { return CR(liw_cr::cr_cos(a.v)); }
+__host__ __device__ inline CR datan2(const CR& y, const CR& x) { return CR(liw_cr::cr_atan2(y.v, x.v)); }
+__host__ __device__ inline CR dfloor(const CR& a) { return CR(floor(a.v)); }
+
+__global__ void __launch_bounds__(256) k_lfe_track_begin(int B, DP P, TP tp, void* track, double* x, const double* imu_X, const double* imu_Dt,
+                                                        const double* wheel_T, const double* stamps, const unsigned char* mask, double* linear,
+                                                        double* angular, double* pose_new, unsigned char* skip) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || (mask && !mask[b])) return;
+    Trk* t = trk_at(track, b);
+    double* x0 = x + 30 * (size_t)b;
+    double* x1 = x0 + 15;
+    typedef V3<CR> VC;
+    const Iso<CR> Twi = liw::make_tf(liw::cast_v3<CR>(x1), liw::cast_v3<CR>(x1 + 3)), Til = liw::cast_iso<CR>(P.Til_R, P.Til_t);
+    // de-skew with the current body twist (:140-148): R_w_laser^T v and log_SO3(R_il^T exp_so3(current_angular_local) R_il)
+    const VC lin = liw::mulT(liw::mul(Twi, Til).R, liw::cast_v3<CR>(x1 + 6));
+    const VC ang = liw::log_SO3(liw::mul(liw::mul(liw::transpose(Til.R), liw::exp_so3(liw::cast_v3<CR>(t->ang))), Til.R));
+    linear[3 * (size_t)b] = lin.x.v; linear[3 * (size_t)b + 1] = lin.y.v; linear[3 * (size_t)b + 2] = lin.z.v;
+    angular[3 * (size_t)b] = ang.x.v; angular[3 * (size_t)b + 1] = ang.y.v; angular[3 * (size_t)b + 2] = ang.z.v;
+    const double Dt = imu_Dt[b];
+    const bool sk = Dt < tp.min_dt;
+    skip[b] = sk ? 1 : 0;
+    if (sk) { t->skipped += 1; return; }
+    for (int k = 0; k < 15; ++k) x0[k] = x1[k];   // pop_frame_for_tracking: the newest frame becomes the window's front
+    // update_current_status with wheel_delta_to_imu_delta: T_w_i * (T_iw * dT * T_iw^-1)
+    const Iso<CR> Tiw = liw::cast_iso<CR>(tp.Tiw_R, tp.Tiw_t);
+    const double* w = wheel_T + 12 * (size_t)b;
+    const Iso<CR> delta = liw::mul(liw::mul(Tiw, liw::cast_iso<CR>(w, w + 9)), liw::inverse(Tiw));
+    const Iso<CR> N = liw::mul(Twi, delta);
+    const VC q = liw::log_SO3(N.R);
+    x1[0] = N.t.x.v; x1[1] = N.t.y.v; x1[2] = N.t.z.v; x1[3] = q.x.v; x1[4] = q.y.v; x1[5] = q.z.v;
+    for (int k = 0; k < 3; ++k) t->ang[k] = imu_X[15 * (size_t)b + 6 + k] / Dt;   // gamma / Dt
+    t->stamp = stamps[b];
+    for (int k = 0; k < 6; ++k) pose_new[6 * (size_t)b + k] = x1[k];
+}
+
+__global__ void __launch_bounds__(256) k_lfe_track_end(const void* store, Lay L, DP P, TP tp, void* track, int slot, const double* x, const int* count,
+                                                      const unsigned char* mask, unsigned char* key, double* pose) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B || (mask && !mask[b])) return;
+    Trk* t = trk_at(track, b);
+    const double* x1 = x + 30 * (size_t)b + 15;
+    for (int k = 0; k < 6; ++k) pose[6 * (size_t)b + k] = x1[k];
+    const Iso<double> Twl = liw::mul(tf6(x1), til(P));
+    const Iso<double> d = liw::mul(liw::inverse(liw::cast_iso<double>(t->kf_R, t->kf_t)), Twl);
+    const bool is_static = vnorm(d.t) < tp.p_thr && vnorm(liw::log_SO3(d.R)) < tp.q_thr;
+    const Slot s = slot_at(const_cast<void*>(store), L, b, slot);
+    const int n_match = count[b], n_no_match = n_lines(s, L) - n_match;
+    const bool kf = !is_static || n_match < n_no_match;
+    key[b] = kf ? 1 : 0;
+    t->tracked += 1;
+    if (kf) {
+        t->keys += 1;
+        for (int k = 0; k < 9; ++k) t->kf_R[k] = Twl.R.m[k];
+        t->kf_t[0] = Twl.t.x; t->kf_t[1] = Twl.t.y; t->kf_t[2] = Twl.t.z;
+    }
+}
+
 }  // namespace lfe
 
 using namespace lfe;
@@ -1751,6 +1860,64 @@ int liw_lfe_rebuild(liw_lfe_ctx* c, void* store, int first_slot, int F, const do
     LFE_DEV(c);
     if (!store || !poses || F < 1 || first_slot < 0 || (long long)first_slot + F > c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_rebuild: bad argument");
     return add_scan_launch(c, store, first_slot, F, true, poses, robot_stride, frame_stride, mask, nullptr, stream);
+}
+
+int liw_lfe_track_layout(const liw_lfe_dims* dims, size_t* bytes) {
+    Lay L;
+    if (!bytes || !make_lay(dims, L)) return LIW_EINVAL;
+    *bytes = (size_t)dims->B * kTrkBytes;
+    return LIW_OK;
+}
+
+namespace {
+TP track_tp(const liw_lfe_track_params* tp) {   // the extrinsic as liw_lie_from_matrix16 loads it
+    TP t;
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) t.Tiw_R[i * 3 + j] = tp->T_imu_to_wheel[i * 4 + j]; t.Tiw_t[i] = tp->T_imu_to_wheel[i * 4 + 3]; }
+    if (tp->normalize_extrinsics) liw_normalize_rotation_host(t.Tiw_R);
+    t.min_dt = tp->min_delta_t; t.p_thr = tp->key_frame_p_motion_threshold; t.q_thr = tp->key_frame_q_motion_threshold;
+    return t;
+}
+}  // namespace
+
+int liw_lfe_track_init(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* track, const double* x, long long robot_stride, const double* angular_local,
+                       const unsigned char* mask, void* stream) {
+    LFE_DEV(c);
+    if (!tp || !track || !x || robot_stride < 1) return fail(c, LIW_EINVAL, "liw_lfe_track_init: bad argument");
+    hipLaunchKernelGGL(k_lfe_track_init, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, c->L.B, track, x, robot_stride, angular_local, mask);
+    return launched(c);
+}
+
+int liw_lfe_track_begin(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* track, double* x, const double* imu_X, const double* imu_Dt,
+                        const double* wheel_T, const double* stamps, const unsigned char* mask, double* linear, double* angular, double* pose_new,
+                        unsigned char* skip, void* stream) {
+    LFE_DEV(c);
+    if (!tp || !track || !x || !imu_X || !imu_Dt || !wheel_T || !stamps || !linear || !angular || !pose_new || !skip)
+        return fail(c, LIW_EINVAL, "liw_lfe_track_begin: null argument");
+    hipLaunchKernelGGL(k_lfe_track_begin, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, c->L.B, c->P, track_tp(tp), track, x, imu_X, imu_Dt,
+                       wheel_T, stamps, mask, linear, angular, pose_new, skip);
+    return launched(c);
+}
+
+int liw_lfe_track_end(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* track, const void* store, int slot, const double* x, const int* count,
+                      const unsigned char* mask, unsigned char* key, double* pose, void* stream) {
+    LFE_DEV(c);
+    if (!tp || !track || !store || !x || !count || !key || !pose || slot < 0 || slot >= c->L.slots)
+        return fail(c, LIW_EINVAL, "liw_lfe_track_end: bad argument");
+    hipLaunchKernelGGL(k_lfe_track_end, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, store, c->L, c->P, track_tp(tp), track, slot, x, count,
+                       mask, key, pose);
+    return launched(c);
+}
+
+int liw_lfe_track_get(liw_lfe_ctx* c, const void* track, int robot, double* tf12, double* angular3, double* stamp, int* counters) {
+    LFE_DEV(c);
+    if (!track || robot < 0 || robot >= c->L.B) return fail(c, LIW_EINVAL, "liw_lfe_track_get: bad argument");
+    Trk t;
+    if (hipMemcpy(&t, (const char*)track + (size_t)robot * kTrkBytes, sizeof t, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, LIW_EHIP, "hipMemcpy");
+    if (tf12) { for (int k = 0; k < 9; ++k) tf12[k] = t.kf_R[k]; for (int k = 0; k < 3; ++k) tf12[9 + k] = t.kf_t[k]; }
+    if (angular3) for (int k = 0; k < 3; ++k) angular3[k] = t.ang[k];
+    if (stamp) *stamp = t.stamp;
+    if (counters) { counters[0] = t.tracked; counters[1] = t.keys; counters[2] = t.skipped; }
+    return LIW_OK;
 }
 
 int liw_lfe_status(liw_lfe_ctx* c, const void* store, int robot, int slot) {

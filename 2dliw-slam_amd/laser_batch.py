@@ -16,6 +16,7 @@ LFE_EXPORTS = [
     "liw_lfe_status", "liw_lfe_num_lines", "liw_lfe_get_lines", "liw_lfe_cell_lines", "liw_lfe_submap_pose",
     "liw_lfe_spawn_corners", "liw_lfe_corners_to_world", "liw_lfe_match_front", "liw_lfe_pack_init", "liw_lfe_rebuild",
     "liw_lfe_add_scan_flags", "liw_lfe_add_scan_path",
+    "liw_lfe_track_layout", "liw_lfe_track_init", "liw_lfe_track_begin", "liw_lfe_track_end", "liw_lfe_track_get",
 ]
 
 ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID, ST_CORNERS = 1, 2, 4, 8, 16, 32
@@ -26,6 +27,30 @@ NONE = -61   # LIW_LFE_NONE: a getter's "no such sub-map / outside the grid" (th
 
 class DimsC(C.Structure):
     _fields_ = [("B", C.c_int), ("slots", C.c_int), ("max_points", C.c_int), ("max_lines", C.c_int), ("max_cell_entries", C.c_int)]
+
+
+class TrackParamsC(C.Structure):
+    _fields_ = [("T_imu_to_wheel", C.c_double * 16), ("normalize_extrinsics", C.c_int), ("min_delta_t", C.c_double),
+                ("key_frame_p_motion_threshold", C.c_double), ("key_frame_q_motion_threshold", C.c_double)]
+
+
+def office_track_params(prm=None):
+    """liw_lfe_track_params with the trajectory values of reference config/office.yaml and the extrinsic of prm (synth.office_params)"""
+    from .synth import office_params
+    prm = prm or office_params()
+    return dict(T_imu_to_wheel=list(prm["T_imu_to_wheel"]), normalize_extrinsics=bool(prm.get("normalize_extrinsics", True)), min_delta_t=0.001,
+                key_frame_p_motion_threshold=0.05, key_frame_q_motion_threshold=0.05)
+
+
+def track_params_struct(tp):
+    if isinstance(tp, TrackParamsC):
+        return tp
+    s = TrackParamsC()
+    s.T_imu_to_wheel = (C.c_double * 16)(*[float(v) for v in np.asarray(tp["T_imu_to_wheel"], dtype=np.float64).reshape(16)])
+    s.normalize_extrinsics = int(bool(tp["normalize_extrinsics"]))
+    for k in ("min_delta_t", "key_frame_p_motion_threshold", "key_frame_q_motion_threshold"):
+        setattr(s, k, float(tp[k]))
+    return s
 
 
 def dims_struct(dims):
@@ -64,6 +89,12 @@ def _lib():
         L.liw_lfe_match_front.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, ll, ll, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_pack_init.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_rebuild.argtypes = [vp, vp, C.c_int, C.c_int, vp, ll, ll, vp, vp]
+        L.liw_lfe_track_layout.argtypes = [C.POINTER(DimsC), C.POINTER(C.c_size_t)]
+        tpp = C.POINTER(TrackParamsC)
+        L.liw_lfe_track_init.argtypes = [vp, tpp, vp, vp, ll, vp, vp, vp]
+        L.liw_lfe_track_begin.argtypes = [vp, tpp] + [vp] * 12
+        L.liw_lfe_track_end.argtypes = [vp, tpp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_track_get.argtypes = [vp, vp, C.c_int, dp, dp, dp, ip]
         L.liw_lfe_status.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_num_lines.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_get_lines.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int]
@@ -80,6 +111,16 @@ def store_bytes(dims):
     r = _lib().liw_lfe_store_layout(C.byref(dims_struct(dims)), C.byref(n))
     if r < 0:
         raise LiwError(r, "liw_lfe_store_layout")
+    return int(n.value)
+
+
+def track_bytes(dims):
+    """bytes of the tracking record for dims, 256 per robot (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
+    from . import LiwError
+    n = C.c_size_t(0)
+    r = _lib().liw_lfe_track_layout(C.byref(dims_struct(dims)), C.byref(n))
+    if r < 0:
+        raise LiwError(r, "liw_lfe_track_layout")
     return int(n.value)
 
 
@@ -377,6 +418,82 @@ class BatchFrontEnd:
         ps, rs, fs = self._strided_poses(poses, F)
         m = self._mask(mask)
         self._chk(self.L.liw_lfe_rebuild(self.h, self._p(self.store), int(first_slot), F, self._p(ps), rs, fs, self._p(m), self._s()))
+
+    # ------------------------------------------------------------------------------------------------ tracking glue
+    def track_layout(self):
+        """bytes of the tracking record of this front-end's dims (host-only)"""
+        return track_bytes(self.dims)
+
+    def _track(self, track):
+        torch = self.torch
+        assert torch.is_tensor(track) and track.dtype == torch.uint8 and track.is_contiguous() and track.device == self.dev
+        assert track.numel() >= self.track_layout()
+        return track
+
+    def _out(self, t, dtype, numel):
+        assert self.torch.is_tensor(t) and t.dtype == dtype and t.is_contiguous() and t.device == self.dev and t.numel() >= numel
+        return t
+
+    def track_init(self, tp, track, x, angular_local=None, mask=None):
+        """the tracking record (a uint8 device tensor of track_layout() bytes) of the masked robots (all when None) from the state
+        rows x: [B, 15] or any float64 device view [B, k >= 6] whose last stride is 1 (x.view(B, n, 15)[:, n - 1] is one):
+        last_keyframe_tf = make_tf(p, q), current_angular_local = angular_local [B, 3] (zero when None), counters 0."""
+        torch = self.torch
+        tps = track_params_struct(tp)
+        if not (torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.float64 and x.device == self.dev and x.shape[0] == self.B and x.shape[1] >= 6
+                and x.stride(1) == 1 and x.stride(0) >= 1):
+            x = self._t(x, torch.float64, (self.B, -1))
+        a = None if angular_local is None else self._t(angular_local, torch.float64, (self.B, 3))
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_track_init(self.h, C.byref(tps), self._p(self._track(track)), self._p(x), int(x.stride(0)), self._p(a), self._p(m), self._s()))
+        return track
+
+    def track_begin(self, tp, track, x, imu_X, imu_Dt, wheel_T, stamps, mask=None, out=None):
+        """before the scan is processed: the de-skew twist from the current state, the min_delta_t gate, the roll of the two-frame
+        window x [B, 2, 15] (float64, contiguous, updated in place) and the new frame's pose from the wheel increment.
+        -> dict(linear [B, 3], angular [B, 3], pose_new [B, 6], skip [B] uint8); `out` may supply any of them."""
+        torch = self.torch
+        tps = track_params_struct(tp)
+        self._out(x, torch.float64, self.B * 30)
+        iX, iD = self._t(imu_X, torch.float64, (self.B, 15)), self._t(imu_Dt, torch.float64, (self.B,))
+        wT, st = self._t(wheel_T, torch.float64, (self.B, 12)), self._t(stamps, torch.float64, (self.B,))
+        o = dict(out or {})
+        for k, w, dt in (("linear", 3, torch.float64), ("angular", 3, torch.float64), ("pose_new", 6, torch.float64), ("skip", 1, torch.uint8)):
+            if k not in o:
+                o[k] = torch.zeros((self.B, w) if w > 1 else (self.B,), dtype=dt, device=self.dev)
+            self._out(o[k], dt, self.B * w)
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_track_begin(self.h, C.byref(tps), self._p(self._track(track)), self._p(x), self._p(iX), self._p(iD), self._p(wT), self._p(st),
+                                             self._p(m), self._p(o["linear"]), self._p(o["angular"]), self._p(o["pose_new"]), self._p(o["skip"]), self._s()))
+        return o
+
+    def track_end(self, tp, track, slot, x, count, mask=None, out=None):
+        """after the solve: the key-frame decision of the masked robots (all when None; mask out the skipped ones) from the solved
+        x [B, 2, 15], the match count [B] int32 and the lines of scan `slot`.  -> dict(key [B] uint8, pose [B, 6]); key of frame t
+        is corners_to_world's `clear` of frame t + 1."""
+        torch = self.torch
+        tps = track_params_struct(tp)
+        self._out(x, torch.float64, self.B * 30)
+        cnt = self._t(count, torch.int32, (self.B,))
+        o = dict(out or {})
+        if "key" not in o:
+            o["key"] = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+        if "pose" not in o:
+            o["pose"] = torch.zeros(self.B, 6, dtype=torch.float64, device=self.dev)
+        self._out(o["key"], torch.uint8, self.B)
+        self._out(o["pose"], torch.float64, self.B * 6)
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_track_end(self.h, C.byref(tps), self._p(self._track(track)), self._p(self.store), int(slot), self._p(x), self._p(cnt),
+                                           self._p(m), self._p(o["key"]), self._p(o["pose"]), self._s()))
+        return o
+
+    def track_get(self, track, robot):
+        """-> dict(last_keyframe_tf [12], angular_local [3], stamp, tracked, keys, skipped) of one robot (synchronous)"""
+        tf, a, st, cn = np.zeros(12), np.zeros(3), C.c_double(0), np.zeros(3, dtype=np.int32)
+        dp = C.POINTER(C.c_double)
+        self._chk_get(self.L.liw_lfe_track_get(self.h, self._p(self._track(track)), int(robot), tf.ctypes.data_as(dp), a.ctypes.data_as(dp), C.byref(st),
+                                               cn.ctypes.data_as(C.POINTER(C.c_int))))
+        return dict(last_keyframe_tf=tf, angular_local=a, stamp=float(st.value), tracked=int(cn[0]), keys=int(cn[1]), skipped=int(cn[2]))
 
     # -------------------------------------------------------------------------------------------------------- getters
     def status(self, robot, slot=ROBOT):

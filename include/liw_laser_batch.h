@@ -214,6 +214,69 @@ int liw_lfe_pack_init(liw_lfe_ctx* ctx, int n, int cap, const int* count, const 
 int liw_lfe_rebuild(liw_lfe_ctx* ctx, void* store, int first_slot, int F, const double* poses, long long robot_stride, long long frame_stride,
                     const unsigned char* mask, void* stream);
 
+/* Tracking glue (lvio_2d::trajectory::add_sensor_data(laser) while status == TRACKING, around the stages above): the de-skew twist
+ * from the current state, the min_delta_t gate, update_current_status (the new frame's pose from the wheel increment), the roll of
+ * the two-frame window (pop_frame_for_tracking with keep_window_size = 1) and the key-frame decision against last_keyframe_tf.
+ * The key-frame deque and the INITIALIZING state machine stay with the caller.
+ *
+ * The tracking record is caller-owned device memory apart from the store (whose layout does not change), robot-major, 256 bytes per
+ * robot: last_keyframe_tf [12] (R row-major, then t), current_angular_local [3], the stamp of the last accepted frame, and the
+ * int counters tracked frames, key frames, skipped frames; the rest is padding.
+ * Mapping: a lane per robot, work-groups of 256, no LDS, no atomics.  The arithmetic is liw_lie.h's, in the reference's order, with
+ * the device sin / cos / atan2: results agree with the host to round-off, and a decision can differ from the host's only where a
+ * quantity is within round-off of its threshold.  liw_lfe_track_begin evaluates those three functions correctly rounded, which is
+ * what the host's libm returns for all but about 0.1 % of the arguments: its twist and pose are bit-identical to the host's then,
+ * so that a free-running chain of solves does not start from a last-bit difference. */
+typedef struct liw_lfe_track_params {
+    double T_imu_to_wheel[16];   /* 4x4 row-major, loaded as liw_lie_from_matrix16 does */
+    int normalize_extrinsics;    /* re-orthonormalise its rotation (T_imu_to_laser is the ctx's, from its laser parameters) */
+    double min_delta_t;          /* a frame whose IMU interval is shorter is skipped */
+    double key_frame_p_motion_threshold;
+    double key_frame_q_motion_threshold;
+} liw_lfe_track_params;
+
+/* bytes of the tracking record for `dims` (256 per robot); LIW_EINVAL for a non-positive dimension.  Host-only. */
+int liw_lfe_track_layout(const liw_lfe_dims* dims, size_t* bytes);
+
+/* What check_and_processing_initialize leaves behind for tracking, for the robots with mask[b] != 0 (all when NULL):
+ * last_keyframe_tf = make_tf(p, q) of the state row at x + b * robot_stride (stride in doubles; the IMU pose, without T_imu_to_laser,
+ * as the reference takes it), current_angular_local = angular_local [B][3] row b (zero when angular_local is NULL), stamp 0 and all
+ * counters 0; the padding is zeroed.  LIW_EINVAL: a null tp / track / x, robot_stride < 1. */
+int liw_lfe_track_init(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, void* track, const double* x, long long robot_stride,
+                       const double* angular_local, const unsigned char* mask, void* stream);
+
+/* Before the scan is processed.  x [B][2][15] are the states of the two-frame batch (row 1 the current state), imu_X [B][15],
+ * imu_Dt [B], wheel_T [B][12] the interval's liw_batch arrays, stamps [B] the scan stamps.  Per robot with mask[b] != 0 (all when
+ * NULL), in the reference's order:
+ *   1. the de-skew twist from the state before the update: linear [B][3] row b = R_w_laser^T v with R_w_laser = R(q) R_il,
+ *      angular [B][3] row b = log_SO3(R_il^T exp_so3(current_angular_local) R_il)  (what liw_lfe_deskew takes);
+ *   2. skip [B] byte b = imu_Dt[b] < min_delta_t.  A skipped robot gets linear / angular / skip and its skipped counter advances;
+ *      nothing else of it is written;
+ *   3. otherwise the window rolls: x[b][0] := x[b][1], a bitwise copy;
+ *   4. x[b][1].p, q := log_SE3(make_tf(p, q) * T_iw * wheel_T[b] * T_iw^-1); v, ba, bw are carried;
+ *   5. current_angular_local := imu_X[b][6 .. 8] / imu_Dt[b], the stamp is stored, pose_new [B][6] row b = x[b][1][0 .. 5]
+ *      (packed: what liw_lfe_match takes as pose2).
+ * Of a masked-out robot no byte of x, track or any output is written.  LIW_EINVAL: a null tp or a null array other than mask. */
+int liw_lfe_track_begin(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, void* track, double* x, const double* imu_X, const double* imu_Dt,
+                        const double* wheel_T, const double* stamps, const unsigned char* mask, double* linear, double* angular, double* pose_new,
+                        unsigned char* skip, void* stream);
+
+/* After the solve.  Per robot with mask[b] != 0 (all when NULL; the caller masks out the robots liw_lfe_track_begin skipped):
+ *   pose [B][6] row b = x[b][1][0 .. 5];  tf_w_l = make_tf(pose) * T_imu_to_laser;  delta = last_keyframe_tf^-1 * tf_w_l;
+ *   static = |delta.t| < key_frame_p_motion_threshold && |log_SO3(delta.R)| < key_frame_q_motion_threshold  (both strict);
+ *   n_match = count[b] (a liw_lfe_match count), n_no_match = n_lines - n_match with the clamped n_lines of scan slot `slot`;
+ *   key [B] byte b = !static || n_match < n_no_match;  on a key frame last_keyframe_tf := tf_w_l;
+ *   the tracked-frame counter advances, and the key-frame counter on a key frame.
+ * key of frame t is the `clear` argument of liw_lfe_corners_to_world in frame t + 1: the corners of the key frame itself belong to
+ * it.  The store is only read.  Of a masked-out robot nothing is written.  LIW_EINVAL: a null tp or a null array other than mask,
+ * slot outside 0 .. slots-1. */
+int liw_lfe_track_end(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, void* track, const void* store, int slot, const double* x,
+                      const int* count, const unsigned char* mask, unsigned char* key, double* pose, void* stream);
+
+/* the record of one robot (synchronous; tests and tools): tf12 = last_keyframe_tf, angular3, stamp, counters [3] = tracked, key,
+ * skipped frames.  Any output may be NULL.  LIW_EINVAL: a null track, robot outside 0 .. B-1. */
+int liw_lfe_track_get(liw_lfe_ctx* ctx, const void* track, int robot, double* tf12, double* angular3, double* stamp, int* counters);
+
 /* getters (synchronous device -> host copies; tests and tools).  slot: 0 .. slots-1, LIW_LFE_REF or LIW_LFE_SPAWNING. */
 /* status word of robot / slot (slot = LIW_LFE_ROBOT: the robot word); a missing sub-map reads LIW_LFE_NONE */
 int liw_lfe_status(liw_lfe_ctx* ctx, const void* store, int robot, int slot);

@@ -15,7 +15,16 @@ work as N - 1 calls of the lane-per-robot match, outputs reused), pack_init_ms (
 one launch of the wave-per-robot add_scan kernel) and rebuild_lane_ms (LIW_LFE_ADD_SCAN=lane: the reset and N launches), each
 with min / max, the ratios lane / wave, and whether the two paths' counts and rebuilt stores' headers agree.  --B "" runs that leg alone.
 
-  python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5] [--init 30 [--init-B 4096]]
+--track K adds the tracking frame of a fleet (key "track", per B of --track-B): K fleet.FleetTracker.step frames (track_begin ->
+ranges_to_points -> deskew -> spawn_corners -> match -> pack_track -> solve(TRACK) -> marginalize -> track_end -> corners_to_world
+-> add_scan) on --track-distinct trajectories of synth.make_window with scans cast from their truth poses in the tool's rooms.
+frame_ms: the median over the K frames of a host clock around step + synchronise, per repetition; its median / min / max over
+--reps repetitions after one warm-up run.  track_begin_ms / track_end_ms: the two glue kernels alone (HIP events).  host_glue: the
+baseline without them, the same stages with the glue done on the host from read-backs (tests/track_glue_reference.py
+HostGlueTracker: a loop over the robots through liw_lie_*), frame_ms over --track-host-frames frames of one run, and whether the
+two sides' key / skip decisions agree on those frames.
+
+  python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5] [--init 30 [--init-B 4096]] [--track 8 [--track-B 4096,49152]]
 """
 import argparse
 import importlib
@@ -235,6 +244,90 @@ def init_run(liw, torch, lp, B, N, nd, reps, cap=256):
     return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
 
 
+def track_scenes(liw, synth, prm, lp, nd, K):
+    """nd trajectories of K frames after the start frame: truth states, stamps, the intervals' arrays, scans cast from the truth"""
+    hp = liw.HostPreint(prm)
+    Til = synth.normalize_extrinsic(lp["T_imu_to_laser"])
+    trajs = [synth.make_window(hp, prm, seed=8100 + j, n=K + 1, L=0) for j in range(nd)]
+    truth = np.stack([np.asarray(t["truth_states"]).reshape(K + 1, 15) for t in trajs])
+    R = np.zeros((nd, K + 1, N_RAYS), dtype=np.float32)
+    for j in range(nd):
+        segs = liw.laser.room_segments(5000 + j)
+        for k in range(K + 1):
+            R[j, k] = liw.laser.cast_scan(segs, _T(truth[j, k, 0:3], truth[j, k, 3:6]) @ Til, n_rays=N_RAYS, seed=100 * j + k)[0]
+    iv = {key: np.stack([np.asarray(t[key]).reshape(K, -1) for t in trajs]) for key in liw.fleet.INTERVAL_KEYS}
+    return dict(truth=truth, ranges=R, times=np.stack([t["times"] for t in trajs]), iv=iv)
+
+
+def track_run(liw, torch, prm, lp, tp, B, K, sc, reps, host_frames):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import track_glue_reference as ref
+    nd = sc["truth"].shape[0]
+    rob = np.arange(B) % nd
+    robd = torch.from_numpy(rob).cuda()
+    dims = dict(B=B, slots=1, max_points=N_RAYS, max_lines=256, max_cell_entries=8192)
+    Rd, Td = torch.from_numpy(sc["ranges"]).cuda(), torch.from_numpy(sc["times"]).cuda()
+    ivd = {k: torch.from_numpy(v).cuda() for k, v in sc["iv"].items()}
+    frames = [(Rd[:, k][robd].contiguous(), Td[:, k][robd].contiguous(), {kk: v[:, k - 1][robd].contiguous() for kk, v in ivd.items()}) for k in range(1, K + 1)]
+    r0, t0, x0 = Rd[:, 0][robd].contiguous(), Td[:, 0][robd].contiguous(), sc["truth"][rob, 0]
+
+    def begin(tr):
+        tr.fe.reset()
+        tr.fe.set_geometry(N_RAYS, ANG_MIN, ANG_INC, T_INC)
+        pts, _, n = tr.fe.ranges_to_points(r0, t0)
+        tr.fe.spawn(0, pts, n)
+        tr.fe.add_scan(0, x0[:, 0:6])
+        tr.start(x0)
+
+    def run(tr, nf):
+        begin(tr)
+        torch.cuda.synchronize()
+        ts, dec = [], []
+        for r, st, iv in frames[:nf]:
+            t_a = time.perf_counter()
+            o = tr.step(r, st, iv)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t_a) * 1e3)
+            dec.append((np.asarray(o["key"].cpu() if torch.is_tensor(o["key"]) else o["key"]).copy(),
+                        np.asarray(o["skip"].cpu() if torch.is_tensor(o["skip"]) else o["skip"]).copy(), int(o["Ltot"])))
+        return ts, dec
+
+    out = dict(K=K, distinct=nd)
+    ft = liw.FleetTracker(prm, lp, tp, dims)
+    run(ft, K)   # warm-up
+    meds, dec_d = [], None
+    for _ in range(reps):
+        ts, dec_d = run(ft, K)
+        meds.append(float(np.median(ts)))
+    out["frame_ms"], out["frame_min_ms"], out["frame_max_ms"] = float(np.median(meds)), float(min(meds)), float(max(meds))
+    out["robot_frames_per_s"] = B / (out["frame_ms"] * 1e-3)
+    out["key_frames"], out["skipped"], out["Ltot_last"] = int(sum(d[0].sum() for d in dec_d)), int(sum(d[1].sum() for d in dec_d)), dec_d[-1][2]
+    # the two glue kernels alone, on the state the last run left
+    r, st, iv = frames[-1]
+    x = ft.x.clone()
+    sp = []
+    out["track_begin_ms"] = timed(torch, lambda: ft.fe.track_begin(ft.tp, ft.track, x, iv["imu_X"], iv["imu_Dt"], iv["wheel_T"], st, out=ft._tb), reps, sp)
+    out["track_begin_min_ms"], out["track_begin_max_ms"] = sp
+    eo = dict(key=torch.zeros_like(ft.key), pose=torch.zeros_like(ft.pose))
+    out["track_end_ms"] = timed(torch, lambda: ft.fe.track_end(ft.tp, ft.track, 0, x, ft._m["count"], out=eo), reps, sp)
+    out["track_end_min_ms"], out["track_end_max_ms"] = sp
+    ft.close()
+    del ft
+    torch.cuda.empty_cache()
+    if host_frames > 0:
+        ht = ref.HostGlueTracker(liw, prm, lp, tp, dims)
+        ts, dec_h = run(ht, min(host_frames, K))
+        out["host_glue"] = dict(frames=len(ts), frame_ms=float(np.median(ts)), frame_min_ms=float(min(ts)), frame_max_ms=float(max(ts)),
+                                decisions_agree=bool(all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+                                                         for a, b in zip(dec_d, dec_h))))
+        out["host_glue_over_device"] = out["host_glue"]["frame_ms"] / out["frame_ms"]
+        ht.fe.close()
+        ht.bs.close()
+        del ht
+        torch.cuda.empty_cache()
+    return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
+
+
 def host_run(liw, lp, sc, n=256):
     ra, rb, pa, pb = sc
     nd = ra.shape[0]
@@ -268,6 +361,10 @@ def main():
     ap.add_argument("--distinct", type=int, default=64)
     ap.add_argument("--init", type=int, default=0, help="frames per INIT window (0: no initialisation leg)")
     ap.add_argument("--init-B", default="4096")
+    ap.add_argument("--track", type=int, default=0, help="frames of the fleet tracking leg (0: none)")
+    ap.add_argument("--track-B", default="4096,49152")
+    ap.add_argument("--track-distinct", type=int, default=16)
+    ap.add_argument("--track-host-frames", type=int, default=2, help="frames of the host-glue baseline (0: none)")
     a = ap.parse_args()
     import torch
     liw = importlib.import_module("2dliw-slam_amd")
@@ -282,6 +379,14 @@ def main():
     if a.init:
         assert a.init >= 2, "--init N: at least two frames"
         res["init"] = {str(B): init_run(liw, torch, lp, B, a.init, a.distinct, a.reps) for B in [int(x) for x in a.init_B.split(",") if x]}
+    if a.track:
+        synth = importlib.import_module("2dliw-slam_amd.synth")
+        prm = synth.office_params()
+        lpt = dict(liw.laser.office_laser_params(prm), ref_n_accumulation=4)   # the reference sub-map exists at every frame
+        tp = liw.laser_batch.office_track_params(prm)
+        tsc = track_scenes(liw, synth, prm, lpt, a.track_distinct, a.track)
+        res["track"] = {str(B): track_run(liw, torch, prm, lpt, tp, B, a.track, tsc, a.reps, a.track_host_frames)
+                        for B in [int(x) for x in a.track_B.split(",") if x]}
     print(json.dumps(res))
 
 
