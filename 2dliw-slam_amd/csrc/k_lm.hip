@@ -53,6 +53,35 @@ struct AsmCtx {
     const double* x;          // states the partials were evaluated at, window base [n][15]
     const double* pJ; const double* pX; bool prior_on;
 };
+// what is fixed for window b over a kernel; the caller states when the prior factor is part of its problem.  Partial buffer and states: bind
+__device__ __forceinline__ AsmCtx asm_ctx(const WsView& w, int n, int mode, int fast, int b, const double* prior_J, const double* prior_X, bool prior_on) {
+    AsmCtx c;
+    c.pif = w.pi_frame; c.plc = w.pl_compact; c.n = n; c.mode = mode; c.fast = fast; c.b = b;
+    c.pJ = prior_J + (size_t)b * 225; c.pX = prior_X + (size_t)b * 15; c.prior_on = prior_on;
+    return c;
+}
+__device__ __forceinline__ void bind(AsmCtx& c, const WsView& w, int buf, const double* x) {   // partial buffer `buf`, evaluated at the states x
+    c.buf = buf; c.PL = w.PL[buf]; c.PI = w.PI[buf]; c.PW = w.PW[buf]; c.PG = w.PG[buf]; c.x = x;
+}
+
+// ---- one wave on the [n][15] states of its window
+__device__ __forceinline__ void copy_states(double* dst, const double* src, int n, int lane) {
+    for (int e = lane; e < n * 15; e += 64) dst[e] = src[e];
+}
+__device__ __forceinline__ double free_norm(const double* x, int mode, int fast, int n, int lane) {   // |x| over the entries Ceres holds variable
+    double s = 0.0;
+    for (int e = lane; e < n * 15; e += 64) if (!var_is_const(mode, fast, n, e / 15, e % 15)) s += x[e] * x[e];
+    return sqrt(wave_sum(s));
+}
+__device__ __forceinline__ void history_put(const StepArgs& a, int rec, int b, const double* x, int lane) {   // record `rec` of window b, if the caller keeps that many
+    if (a.w.history && rec < a.w.history_records)
+        for (int e = lane; e < a.n * 15; e += 64) a.w.history[((size_t)rec * a.B + b) * a.n * 15 + e] = x[e];
+}
+// a solve that ends after the prologue or the gradient test: the state as the step leaves it, no candidate pending (one lane)
+__device__ __forceinline__ void lm_store_exit(LmState& st, int term, double radius, double dec, double x_cost, double x_norm, int reuse, int cur) {
+    st.done = 1; st.termination = term; st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm;
+    st.reuse_diagonal = reuse; st.cur = cur; st.have_candidate = 0;
+}
 
 // prior residual r = linearized_J (X - linearized_X)  (marginalization_factor.h:22-53, linearized_R omitted there)
 __device__ __forceinline__ double prior_r(const AsmCtx& c, int k) {
@@ -551,6 +580,41 @@ __device__ double frame_diag(const AsmCtx& c, int i, LdsStep& T) {
     return d;
 }
 
+// ---- back substitution of the one-wave and the two-wave kernel: lane r < 15 owns unknown r of a frame
+struct BsRow { double row[22], gsv, xold, scv, dgv; };   // row r of the frame's record: Yo (15) | Yr (6) | yz; scaled gradient, state, Jacobi scale, LM diagonal
+// one batch of loads per frame.  A record row is 22 consecutive doubles on a 16-byte boundary (REC_LD and SOLVE_WS are even, the
+// workspace is 256-byte aligned): 11 128-bit loads instead of 22 64-bit ones
+__device__ __forceinline__ BsRow bs_fetch(const double* sws, const double* xw, const double* scl, const double* dgl, int i, int lane) {
+    static_assert(REC_LD % 2 == 0 && SOLVE_WS % 2 == 0, "16-byte aligned record rows");
+    const double* f = sws + (size_t)i * SOLVE_WS;
+    const int r = lane < 15 ? lane : 0;
+    const double2* f2 = reinterpret_cast<const double2*>(f + r * REC_LD);
+    BsRow R;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) { const double2 v = f2[k]; R.row[2 * k] = v.x; R.row[2 * k + 1] = v.y; }
+    R.gsv = f[REC_GS + r]; R.xold = xw[(size_t)i * 15 + r]; R.scv = scl[i * 15 + r]; R.dgv = dgl[i * 15 + r];
+    return R;
+}
+// candidate of frame i from its solution t: delta = -y * scale, so3 Plus on the rotation; the frame's share of |step|^2, y'g_s and
+// y'D^2 y (damp: LM diagonal over radius, in the form the caller holds the radius in)
+__device__ __forceinline__ void bs_emit(const StepArgs& a, int i, int lane, double t, const BsRow& R, double damp, double* xc, double& sn2, double& ytg, double& dsum) {
+    const bool cst = lane < 15 && var_is_const(a.mode, a.fast_mode, a.n, i, lane);
+    const double del = (lane < 15 && !cst) ? -t * R.scv : 0.0;
+    const double qv[3] = {rdlane(R.xold, 3), rdlane(R.xold, 4), rdlane(R.xold, 5)};
+    double dq[3] = {rdlane(del, 3), rdlane(del, 4), rdlane(del, 5)}, qn[3];
+    so3_plus(qv, dq, qn);
+    if (lane < 15) {
+        double xnew = R.xold + del;
+        if (lane >= 3 && lane < 6) xnew = var_is_const(a.mode, a.fast_mode, a.n, i, 3) ? R.xold : qn[lane - 3];
+        xc[(size_t)i * 15 + lane] = xnew;
+        if (!cst) {
+            sn2 += (R.xold - xnew) * (R.xold - xnew);
+            ytg += t * R.gsv;
+            dsum += damp * t * t;
+        }
+    }
+}
+
 // THROUGHPUT = false: 2 waves per SIMD, the next frame's loads are issued one frame ahead in the elimination sweep (lowest
 // latency of one window).  THROUGHPUT = true: 3 waves per SIMD (<= 168 VGPRs, no look-ahead there): the other waves hide
 // the round trip instead (large batches).
@@ -607,12 +671,7 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
     double* xw = a.x + (size_t)b * n * 15;
     double* xc = a.w.x_cand + (size_t)b * n * 15;
 
-    AsmCtx c;
-    c.pif = a.w.pi_frame;
-    c.plc = a.w.pl_compact;
-    c.n = n; c.mode = a.mode; c.fast = a.fast_mode; c.b = b;
-    c.pJ = a.prior_J + (size_t)b * 225; c.pX = a.prior_X + (size_t)b * 15;
-    c.prior_on = a.mode == LIW_MODE_TRACK && a.has_prior[b] && !a.fast_mode;
+    AsmCtx c = asm_ctx(a.w, n, a.mode, a.fast_mode, b, a.prior_J, a.prior_X, a.mode == LIW_MODE_TRACK && a.has_prior[b] && !a.fast_mode);
 
     double radius = st.radius, dec = st.decrease_factor, x_cost = st.x_cost, x_norm = st.x_norm;
     // wave-uniform by construction, but loaded with vector loads: made scalar explicitly, so that the partial-buffer base pointers
@@ -625,72 +684,54 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
 
     if (iteration == 0 && !st.have_candidate) {
         // ---- iteration 0: cost at the initial point
-        c.buf = cur; c.PL = a.w.PL[cur]; c.PI = a.w.PI[cur]; c.PW = a.w.PW[cur]; c.PG = a.w.PG[cur]; c.x = xw;
+        bind(c, a.w, cur, xw);
         x_cost = window_cost(c);
         if (lane == 0) { st.initial_cost = x_cost; st.minimum_cost = x_cost; }
         if (!isfinite(x_cost)) {   // IterationZero: "Residual and Jacobian evaluation failed." -> FAILURE, nothing applied (non-finite residual;
             if (lane == 0) { st.done = 1; st.termination = 6; st.x_cost = x_cost; }   // a non-finite Jacobian is caught in the pass below)
             return;
         }
-        double s = 0.0;
-        for (int e = lane; e < n * 15; e += 64) {
-            const double xv = xw[e];
-            st.x0[e] = xv;
-            if (!var_is_const(a.mode, a.fast_mode, n, e / 15, e % 15)) s += xv * xv;
-        }
-        x_norm = sqrt(wave_sum(s));
+        copy_states(st.x0, xw, n, lane);
+        x_norm = free_norm(xw, a.mode, a.fast_mode, n, lane);
         fresh = true;
-        if (a.w.history && a.w.history_records > 0)
-            for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)b) * n * 15 + e] = xw[e];
+        history_put(a, 0, b, xw, lane);
     } else if (st.have_candidate) {
         // ---- candidate evaluated by the previous linearise launch
         const int cb = 1 - cur;
-        c.buf = cb; c.PL = a.w.PL[cb]; c.PI = a.w.PI[cb]; c.PW = a.w.PW[cb]; c.PG = a.w.PG[cb]; c.x = xc;
+        bind(c, a.w, cb, xc);
         double cand_cost = window_cost(c);
         STAMPE(4001);
-        if (!isfinite(cand_cost)) cand_cost = 1.7976931348623157e308;
-        int term = 0;
-        if (st.cand_step_norm <= kParamTol * (x_norm + kParamTol)) term = 3;
-        else if (fabs(x_cost - cand_cost) <= kFuncTol * x_cost) term = 2;
+        if (!isfinite(cand_cost)) cand_cost = kFailedEvalCost;
+        const int term = lm_candidate_term(st.cand_step_norm, x_norm, x_cost, cand_cost);
         if (term) {
-            if (a.w.history && iteration < a.w.history_records)
-                for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)iteration * a.B + b) * n * 15 + e] = xw[e];
+            history_put(a, iteration, b, xw, lane);
             if (lane == 0) { st.done = 1; st.termination = term; }
             return;
         }
         const double rho = (x_cost - cand_cost) / st.model_cost_change;
-        if (rho > kMinRelDec) {
-            for (int e = lane; e < n * 15; e += 64) xw[e] = xc[e];
+        if (lm_accepts(rho)) {
+            copy_states(xw, xc, n, lane);
             cur = cb;
             x_cost = cand_cost;
-            double s = 0.0;
-            for (int e = lane; e < n * 15; e += 64) if (!var_is_const(a.mode, a.fast_mode, n, e / 15, e % 15)) s += xc[e] * xc[e];
-            x_norm = sqrt(wave_sum(s));
-            { const double t3 = 2.0 * rho - 1.0; radius = radius / fmax(1.0 / 3.0, 1.0 - t3 * t3 * t3); }   // (not pow(): 200 instructions of one wave)
-            radius = fmin(kMaxRadius, radius);
-            dec = 2.0; reuse = 0;
+            x_norm = free_norm(xc, a.mode, a.fast_mode, n, lane);
+            lm_step_accepted(rho, radius, dec, reuse);
             if (lane == 0) { st.successful += 1; if (x_cost < st.minimum_cost) st.minimum_cost = x_cost; }
             last_successful = true;
         } else {
-            radius = radius / dec; dec *= 2.0; reuse = 1;
+            lm_step_rejected(radius, dec, reuse);
             last_successful = false;
         }
         wave_mem_sync();
-        if (a.w.history && iteration < a.w.history_records)
-            for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)iteration * a.B + b) * n * 15 + e] = xw[e];
+        history_put(a, iteration, b, xw, lane);
     } else {
         last_successful = false;   // previous step was invalid
-        if (a.w.history && iteration < a.w.history_records)
-            for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)iteration * a.B + b) * n * 15 + e] = xw[e];
+        history_put(a, iteration, b, xw, lane);
     }
 
     // ---- FinalizeIterationAndCheckIfMinimizerCanContinue, part 1 (the gradient test needs the assembled g and is
     //      applied after the pass below; it can only pre-empt the min-radius exit, never the iteration cap)
-    if (iteration >= st.max_iters && !(iteration == 0 && fresh)) {
-        if (lane == 0) {
-            st.done = 1; st.termination = 4; st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm;
-            st.reuse_diagonal = reuse; st.cur = cur; st.have_candidate = 0;
-        }
+    if (lm_cap_reached(iteration, st.max_iters, fresh)) {
+        if (lane == 0) lm_store_exit(st, 4, radius, dec, x_cost, x_norm, reuse, cur);
         return;
     }
 
@@ -698,7 +739,7 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
     STAMPE(4002);
     wave_mem_sync();
     STAMPE(4003);
-    c.buf = cur; c.PL = a.w.PL[cur]; c.PI = a.w.PI[cur]; c.PW = a.w.PW[cur]; c.PG = a.w.PG[cur]; c.x = xw;
+    bind(c, a.w, cur, xw);
 
     if (fresh) {   // Jacobi scaling 1/(1+sqrt(H_jj)), computed once per solve
         for (int i = 0; i < n; ++i) {
@@ -946,7 +987,7 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
         if (!isfinite(gchk)) {
             // IterationZero / HandleSuccessfulStep: "Residual and Jacobian evaluation failed." -> FAILURE: the iteration is not recorded and
             // the solve hands back the states it started from
-            if (!fresh) for (int e = lane; e < n * 15; e += 64) xw[e] = st.x0[e];
+            if (!fresh) copy_states(xw, st.x0, n, lane);
             wave_mem_sync();
             if (lane == 0) {
                 st.done = 1; st.termination = 6; st.have_candidate = 0; st.cur = cur;
@@ -957,15 +998,9 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
     }
     // ---- FinalizeIterationAndCheck, part 2
     {
-        int term = 0;
-        if (iteration == 0 && fresh) { if (gmax <= kGradTol) term = 1; }
-        else if (last_successful && gmax <= kGradTol) term = 1;
-        if (!term && !(radius > kMinRadius)) term = 5;
+        const int term = lm_gradient_term(iteration == 0 && fresh, last_successful, gmax, radius > kMinRadius);
         if (term) {
-            if (lane == 0) {
-                st.done = 1; st.termination = term; st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm;
-                st.reuse_diagonal = reuse; st.cur = cur; st.have_candidate = 0;
-            }
+            if (lane == 0) lm_store_exit(st, term, radius, dec, x_cost, x_norm, reuse, cur);
             return;
         }
     }
@@ -1001,53 +1036,29 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
         }
         step_norm = sqrt(wave_sum(sn2));
         model_cost_change = 0.5 * (wave_sum(ytg) + wave_sum(dsum));
-        valid = model_cost_change > 0.0 && isfinite(model_cost_change);
+        valid = lm_step_valid(true, model_cost_change);
       } else {
         // ---- back substitution, frame 0 first.  Lane r owns unknown r: row r of Yo / Yr.
         double ytg = 0.0, dsum = 0.0, sn2 = 0.0;
         double yprev = 0.0, y0v = 0.0;   // lane r < 15: y_{i-1}[r], y_0[r]
         STAMP(2);
-        struct BsRegs { double t, Yo[15], Yr[6], gsv, xold, scv, dgv; };
-        // one batch of loads per frame: yz, row r of Yo / Yr, scaled gradient, state, scale, LM diagonal
-        auto bs_issue = [&](int i) {
-            const double* f = sws + (size_t)i * SOLVE_WS;
-            const int r = lane < 15 ? lane : 0;
-            BsRegs R;
-            // a record row is 22 consecutive doubles on a 16-byte boundary (REC_LD and SOLVE_WS are even, the workspace is 256-byte
-            // aligned): 11 128-bit loads instead of 22 64-bit ones
-            static_assert(REC_LD % 2 == 0 && SOLVE_WS % 2 == 0, "16-byte aligned record rows");
-            const double2* f2 = reinterpret_cast<const double2*>(f + r * REC_LD);
-            double row[22];
-#pragma unroll
-            for (int k = 0; k < 11; ++k) { const double2 v = f2[k]; row[2 * k] = v.x; row[2 * k + 1] = v.y; }
-            R.t = row[21];
-#pragma unroll
-            for (int k = 0; k < 15; ++k) R.Yo[k] = row[k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) R.Yr[k] = row[15 + k];
-            R.gsv = f[REC_GS + r];
-            R.xold = xw[(size_t)i * 15 + r];
-            R.scv = scl[i * 15 + r];
-            R.dgv = dgl[i * 15 + r];
-            return R;
-        };
-        BsRegs cur;
+        auto bs_issue = [&](int i) { return bs_fetch(sws, xw, scl, dgl, i, lane); };
+        BsRow cur;
         if (LIW_PF2) cur = bs_issue(0);
         for (int i = 0; i < n; ++i) {
             if (!LIW_PF2) cur = bs_issue(i);
             STAMP(300 + i * 4);
             // software pipeline: frame i+1's record is in flight while frame i is solved
-            BsRegs nxt;
+            BsRow nxt;
             if (LIW_PF2) {
             nxt = cur;
             __builtin_amdgcn_sched_barrier(0);
             if (i + 1 < n) nxt = bs_issue(i + 1);
             __builtin_amdgcn_sched_barrier(0);
             }
-            double t = cur.t;
-            const double* Yo = cur.Yo;
-            const double* Yr = cur.Yr;
-            const double gsv = cur.gsv, xold = cur.xold, scv = cur.scv, dgv = cur.dgv;
+            double t = cur.row[21];
+            const double* Yo = cur.row;
+            const double* Yr = cur.row + 15;
             if (i >= 1) {
 #pragma unroll
                 for (int k = 0; k < 15; ++k) t -= Yo[k] * rdlane(yprev, k);
@@ -1059,35 +1070,20 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
             STAMP(300 + i * 4 + 1);
             yprev = t;
             if (i == 0) y0v = t;
-            // candidate of this frame: delta = -y * scale ; Plus
-            const bool cst = lane < 15 && var_is_const(a.mode, a.fast_mode, n, i, lane);
-            const double del = (lane < 15 && !cst) ? -t * scv : 0.0;
-            const double qv[3] = {rdlane(xold, 3), rdlane(xold, 4), rdlane(xold, 5)};
-            double dq[3] = {rdlane(del, 3), rdlane(del, 4), rdlane(del, 5)}, qn[3];
-            so3_plus(qv, dq, qn);
-            if (lane < 15) {
-                double xnew = xold + del;
-                if (lane >= 3 && lane < 6) xnew = var_is_const(a.mode, a.fast_mode, n, i, 3) ? xold : qn[lane - 3];
-                xc[(size_t)i * 15 + lane] = xnew;
-                if (!cst) {
-                    sn2 += (xold - xnew) * (xold - xnew);
-                    ytg += t * gsv;
-                    dsum += dgv * inv_radius * t * t;
-                }
-            }
+            bs_emit(a, i, lane, t, cur, cur.dgv * inv_radius, xc, sn2, ytg, dsum);
             if (LIW_PF2) cur = nxt;
         }
         STAMP(3); SPAN(1);
         step_norm = sqrt(wave_sum(sn2));
         // model cost change -(s'g_s + s'A s/2) with s = -y and (A + D^2) y = g_s  ==  (y'g_s + y'D^2 y)/2
         model_cost_change = 0.5 * (wave_sum(ytg) + wave_sum(dsum));
-        valid = model_cost_change > 0.0 && isfinite(model_cost_change);
+        valid = lm_step_valid(true, model_cost_change);
       }
     }
     // max_num_consecutive_invalid_steps reached: FAILURE, which hands back the states the solve started from
-    const bool fail5 = !valid && st.invalid_steps + 1 >= 5;
+    const bool fail5 = !valid && lm_gives_up(st.invalid_steps);
     if (fail5 && st.successful > 0) {
-        for (int e = lane; e < n * 15; e += 64) xw[e] = st.x0[e];
+        copy_states(xw, st.x0, n, lane);
         x_cost = st.initial_cost;
     }
     wave_mem_sync();   // (every lane has read st.invalid_steps / st.successful before lane 0 updates the state)
@@ -1100,7 +1096,8 @@ __device__ __forceinline__ void lm_step_body(const StepArgs& a, const int b, LDS
             st.invalid_steps += 1;
             st.have_candidate = 0;
             if (fail5) { st.done = 1; st.termination = 6; st.iteration = iteration - 1; }
-            st.radius = radius / dec; st.decrease_factor = dec * 2.0; st.reuse_diagonal = 1;
+            lm_step_rejected(radius, dec, reuse);
+            st.radius = radius; st.decrease_factor = dec; st.reuse_diagonal = reuse;
         }
     }
     STAMP(4006);
@@ -1190,96 +1187,73 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
     LdsTwSide& SS = S.side[sd];
     LdsStep& T = SS.T;
 
-    AsmCtx c;
-    c.pif = a.w.pi_frame;
-    c.plc = a.w.pl_compact;
-    c.n = n; c.mode = a.mode; c.fast = a.fast_mode; c.b = b;
-    c.pJ = a.prior_J + (size_t)b * 225; c.pX = a.prior_X + (size_t)b * 15;
-    c.prior_on = a.mode == LIW_MODE_TRACK && a.has_prior[b] && !a.fast_mode;
+    AsmCtx c = asm_ctx(a.w, n, a.mode, a.fast_mode, b, a.prior_J, a.prior_X, a.mode == LIW_MODE_TRACK && a.has_prior[b] && !a.fast_mode);
 
     double radius = 0.0, dec = 0.0, x_cost = 0.0, x_norm = 0.0;
     int reuse = 0, iteration = 0, cur = 0;
     bool last_successful = true, fresh = false;
 
-    // ---- prologue on wave 0 (the candidate test / accept / reject logic of k_lm_step, statement for statement)
+    // ---- prologue on wave 0: candidate test / accept / reject by the rules of liw_lm_rules.hpp
     if (w == 0) {
         radius = st.radius; dec = st.decrease_factor; x_cost = st.x_cost; x_norm = st.x_norm;
         reuse = st.reuse_diagonal; iteration = st.iteration; cur = st.cur;
         int proceed = 1;
         if (iteration == 0 && !st.have_candidate) {
-            c.buf = cur; c.PL = a.w.PL[cur]; c.PI = a.w.PI[cur]; c.PW = a.w.PW[cur]; c.PG = a.w.PG[cur]; c.x = xw;
+            bind(c, a.w, cur, xw);
             double gchk;
             x_cost = window_cost(c, &gchk);
             if (lane == 0) { st.initial_cost = x_cost; st.minimum_cost = x_cost; }
-            double sq = 0.0;
-            for (int e = lane; e < n * 15; e += 64) {
-                const double xv = xw[e];
-                st.x0[e] = xv;
-                if (!var_is_const(a.mode, a.fast_mode, n, e / 15, e % 15)) sq += xv * xv;
-            }
-            x_norm = sqrt(wave_sum(sq));
+            copy_states(st.x0, xw, n, lane);
+            x_norm = free_norm(xw, a.mode, a.fast_mode, n, lane);
             fresh = true;
-            if (a.w.history && a.w.history_records > 0)
-                for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)b) * n * 15 + e] = xw[e];
+            history_put(a, 0, b, xw, lane);
             if (!isfinite(x_cost) || !isfinite(gchk)) {   // IterationZero: evaluation failed -> FAILURE, nothing applied (see k_lm_step)
                 if (lane == 0) { st.done = 1; st.termination = 6; st.x_cost = x_cost; }
                 proceed = 0;
             }
         } else if (st.have_candidate) {
             const int cb = 1 - cur;
-            c.buf = cb; c.PL = a.w.PL[cb]; c.PI = a.w.PI[cb]; c.PW = a.w.PW[cb]; c.PG = a.w.PG[cb]; c.x = xc;
+            bind(c, a.w, cb, xc);
             double cand_gchk;
             double cand_cost = window_cost(c, &cand_gchk);
-            if (!isfinite(cand_cost)) cand_cost = 1.7976931348623157e308;
-            int term = 0;
-            if (st.cand_step_norm <= kParamTol * (x_norm + kParamTol)) term = 3;
-            else if (fabs(x_cost - cand_cost) <= kFuncTol * x_cost) term = 2;
+            if (!isfinite(cand_cost)) cand_cost = kFailedEvalCost;
+            const int term = lm_candidate_term(st.cand_step_norm, x_norm, x_cost, cand_cost);
             const double rho = term ? 0.0 : (x_cost - cand_cost) / st.model_cost_change;
             if (term) {
-                if (a.w.history && iteration < a.w.history_records)
-                    for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)iteration * a.B + b) * n * 15 + e] = xw[e];
+                history_put(a, iteration, b, xw, lane);
                 if (lane == 0) { st.done = 1; st.termination = term; }
                 proceed = 0;
-            } else if (rho > kMinRelDec && !isfinite(cand_gchk)) {   // evaluation failed at the accepted point -> FAILURE (see k_lm_step)
+            } else if (lm_accepts(rho) && !isfinite(cand_gchk)) {   // evaluation failed at the accepted point -> FAILURE (see k_lm_step)
                 if (st.successful > 0)
-                    for (int e = lane; e < n * 15; e += 64) xw[e] = st.x0[e];
+                    copy_states(xw, st.x0, n, lane);
                 wave_mem_sync();
                 if (lane == 0) { st.done = 1; st.termination = 6; st.iteration = iteration - 1; st.x_cost = st.initial_cost; st.have_candidate = 0; }
                 proceed = 0;
             } else {
-                if (rho > kMinRelDec) {
-                    for (int e = lane; e < n * 15; e += 64) xw[e] = xc[e];
+                if (lm_accepts(rho)) {
+                    copy_states(xw, xc, n, lane);
                     cur = cb;
                     x_cost = cand_cost;
-                    double sq = 0.0;
-                    for (int e = lane; e < n * 15; e += 64) if (!var_is_const(a.mode, a.fast_mode, n, e / 15, e % 15)) sq += xc[e] * xc[e];
-                    x_norm = sqrt(wave_sum(sq));
-                    { const double t3 = 2.0 * rho - 1.0; radius = radius / fmax(1.0 / 3.0, 1.0 - t3 * t3 * t3); }   // (not pow(): 200 instructions of one wave)
-                    radius = fmin(kMaxRadius, radius);
-                    dec = 2.0; reuse = 0;
+                    x_norm = free_norm(xc, a.mode, a.fast_mode, n, lane);
+                    lm_step_accepted(rho, radius, dec, reuse);
                     if (lane == 0) { st.successful += 1; if (x_cost < st.minimum_cost) st.minimum_cost = x_cost; }
                     last_successful = true;
                 } else {
-                    radius = radius / dec; dec *= 2.0; reuse = 1;
+                    lm_step_rejected(radius, dec, reuse);
                     last_successful = false;
                 }
-                if (a.w.history && iteration < a.w.history_records)
-                    for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)iteration * a.B + b) * n * 15 + e] = xw[e];
+                history_put(a, iteration, b, xw, lane);
             }
         } else {
             last_successful = false;   // previous step was invalid
-            if (a.w.history && iteration < a.w.history_records)
-                for (int e = lane; e < n * 15; e += 64) a.w.history[((size_t)iteration * a.B + b) * n * 15 + e] = xw[e];
+            history_put(a, iteration, b, xw, lane);
         }
-        if (proceed && iteration >= st.max_iters && !(iteration == 0 && fresh)) {
-            if (lane == 0) {
-                st.done = 1; st.termination = 4; st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm;
-                st.reuse_diagonal = reuse; st.cur = cur; st.have_candidate = 0;
-            }
+        if (proceed && lm_cap_reached(iteration, st.max_iters, fresh)) {
+            if (lane == 0) lm_store_exit(st, 4, radius, dec, x_cost, x_norm, reuse, cur);
             proceed = 0;
         }
         if (proceed && fresh) {   // Jacobi scaling 1/(1+sqrt(H_jj)), computed once per solve
-            c.buf = cur; c.PL = a.w.PL[cur]; c.PI = a.w.PI[cur]; c.PW = a.w.PW[cur]; c.PG = a.w.PG[cur]; c.x = xw;
+            bind(c, a.w, cur, xw);
             for (int i = 0; i < n; ++i) {
                 const double hjj = frame_diag<true>(c, i, T);
                 if (lane < 15) st.scale[i * 15 + lane] = var_is_const(a.mode, a.fast_mode, n, i, lane) ? 1.0 : 1.0 / (1.0 + sqrt(hjj));
@@ -1290,7 +1264,7 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
     __syncthreads();   // (drains wave 0's global writes: accepted states, laser partial copy, scales)
     if (!S.ctl[0]) return;
     reuse = S.ctl[1]; cur = S.ctl[2]; radius = S.ctld[0];
-    c.buf = cur; c.PL = a.w.PL[cur]; c.PI = a.w.PI[cur]; c.PW = a.w.PW[cur]; c.PG = a.w.PG[cur]; c.x = xw;
+    bind(c, a.w, cur, xw);
     const double* scl = st.scale;
     double* dgl = st.diagonal;
     double* sws = a.w.solve_ws + (size_t)b * n * SOLVE_WS;
@@ -1520,19 +1494,13 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
     {
         if (w == 0) {
             const double gm = fmax(S.red[2][3], S.red[3][3]);
-            int term = 0;
-            if (iteration == 0 && fresh) { if (gm <= kGradTol) term = 1; }
-            else if (last_successful && gm <= kGradTol) term = 1;
-            if (!term && !(radius > kMinRadius)) term = 5;
+            const int term = lm_gradient_term(iteration == 0 && fresh, last_successful, gm, radius > kMinRadius);
             if (lane == 0) S.ctl[5] = term;
         }
         __syncthreads();
         const int term = S.ctl[5];
         if (term) {
-            if (w == 0 && lane == 0) {
-                st.done = 1; st.termination = term; st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm;
-                st.reuse_diagonal = reuse; st.cur = cur; st.have_candidate = 0;
-            }
+            if (w == 0 && lane == 0) lm_store_exit(st, term, radius, dec, x_cost, x_norm, reuse, cur);
             return;
         }
     }
@@ -1542,38 +1510,12 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
     if (all_solved && !producer) {
         // ---- back substitution: hub -> frame m -> wave 0: m+1 .. n-1, wave 1: m-1 .. 1, then frame 0's other entries.
         // Lane r owns unknown r: row r of Yo / Yr of the frame's record.
-        const int r15 = lane < 15 ? lane : 0;
-        auto load_row = [&](int i_, double* row, double& gsv, double& xold, double& scv, double& dgv_) {
-            const double* f = sws + (size_t)i_ * SOLVE_WS;
-            const double2* f2 = reinterpret_cast<const double2*>(f + r15 * REC_LD);
-#pragma unroll
-            for (int k = 0; k < 11; ++k) { const double2 v = f2[k]; row[2 * k] = v.x; row[2 * k + 1] = v.y; }
-            gsv = f[REC_GS + r15]; xold = xw[(size_t)i_ * 15 + r15]; scv = scl[i_ * 15 + r15]; dgv_ = dgl[i_ * 15 + r15];
-        };
         double yav[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) yav[k] = S.ya[k];
-        auto emit = [&](int i_, double t, double gsv, double xold, double scv, double dgv_) {
-            const bool cst = lane < 15 && var_is_const(a.mode, a.fast_mode, n, i_, lane);
-            const double del = (lane < 15 && !cst) ? -t * scv : 0.0;
-            const double qv[3] = {rdlane(xold, 3), rdlane(xold, 4), rdlane(xold, 5)};
-            double dq[3] = {rdlane(del, 3), rdlane(del, 4), rdlane(del, 5)}, qn[3];
-            so3_plus(qv, dq, qn);
-            if (lane < 15) {
-                double xnew = xold + del;
-                if (lane >= 3 && lane < 6) xnew = var_is_const(a.mode, a.fast_mode, n, i_, 3) ? xold : qn[lane - 3];
-                xc[(size_t)i_ * 15 + lane] = xnew;
-                if (!cst) {
-                    sn2 += (xold - xnew) * (xold - xnew);
-                    ytg += t * gsv;
-                    dsum += dgv_ / radius * t * t;
-                }
-            }
-        };
         // wave 0 walks m, m+1, .., n-1; wave 1 walks m (solution only: wave 0 emits that frame), m-1, .., 1, 0.  Frame k+1's record is in
         // flight while frame k is solved.
-        struct BsRow { double row[22], gsv, xold, scv, dgv_; };
-        auto fetch = [&](int i_) { BsRow R_; load_row(i_, R_.row, R_.gsv, R_.xold, R_.scv, R_.dgv_); return R_; };
+        auto fetch = [&](int i_) { return bs_fetch(sws, xw, scl, dgl, i_, lane); };
         const int cnt = w == 0 ? n - m : m + 1;
         BsRow curr = fetch(m);
         double yprev = 0.0;
@@ -1590,7 +1532,7 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
             for (int q = 0; q < 6; ++q) t -= curr.row[15 + q] * yav[q];
             if (w == 1 && i == 0 && lane < 6) t = S.ya[lane];                        // frame 0: pose entries from the hub, the rest from "0c"
             yprev = t;
-            if (!(w == 1 && k == 0)) emit(i, t, curr.gsv, curr.xold, curr.scv, curr.dgv_);
+            if (!(w == 1 && k == 0)) bs_emit(a, i, lane, t, curr, curr.dgv / radius, xc, sn2, ytg, dsum);
             curr = nxt;
         }
         sn2 = wave_sum(sn2); ytg = wave_sum(ytg); dsum = wave_sum(dsum);
@@ -1601,19 +1543,21 @@ __global__ __launch_bounds__(256, 1) void k_lm_step_tw(StepArgs a) {
         const double step_norm = sqrt(S.red[0][0] + S.red[1][0]);
         // model cost change -(s'g_s + s'A s/2) with s = -y and (A + D^2) y = g_s  ==  (y'g_s + y'D^2 y)/2
         const double model_cost_change = 0.5 * ((S.red[0][1] + S.red[1][1]) + (S.red[0][2] + S.red[1][2]));
-        const bool valid = all_solved && model_cost_change > 0.0 && isfinite(model_cost_change);
+        const bool valid = lm_step_valid(all_solved, model_cost_change);
         st.iteration = iteration; st.cur = cur; st.x_cost = x_cost; st.x_norm = x_norm;
         if (valid) {
             st.radius = radius; st.decrease_factor = dec; st.reuse_diagonal = 1;
             st.model_cost_change = model_cost_change; st.cand_step_norm = step_norm; st.have_candidate = 1; st.invalid_steps = 0;
         } else {
+            const bool fail5 = lm_gives_up(st.invalid_steps);
             st.invalid_steps += 1;
             st.have_candidate = 0;
-            if (st.invalid_steps >= 5) {   // FAILURE hands back the states the solve started from (rare: one lane copies)
+            if (fail5) {   // FAILURE hands back the states the solve started from (rare: one lane copies)
                 st.done = 1; st.termination = 6; st.iteration = iteration - 1;
                 if (st.successful > 0) { for (int e = 0; e < n * 15; ++e) xw[e] = st.x0[e]; st.x_cost = st.initial_cost; }
             }
-            st.radius = radius / dec; st.decrease_factor = dec * 2.0; st.reuse_diagonal = 1;
+            lm_step_rejected(radius, dec, reuse);
+            st.radius = radius; st.decrease_factor = dec; st.reuse_diagonal = reuse;
         }
     }
 }
@@ -1690,14 +1634,10 @@ __global__ void k_lm_finish(StepArgs a) {   // one thread per (window, frame, po
 __global__ __launch_bounds__(64) void k_export_dense(ExportArgs a) {
     __shared__ LdsTiles T;
     const int b = blockIdx.x, lane = threadIdx.x & 63, n = a.n, N = 15 * n;
-    AsmCtx c;
-    c.pif = a.w.pi_frame;
-    c.plc = a.w.pl_compact;
-    c.n = n; c.mode = a.mode; c.fast = a.fast_mode; c.b = b; c.buf = a.buf;
-    c.PL = a.w.PL[0]; c.PI = a.w.PI[0]; c.PW = a.w.PW[0]; c.PG = a.w.PG[0];   // standalone linearise writes buffer 0
-    c.x = a.x + (size_t)b * n * 15;
-    c.pJ = a.prior_J + (size_t)b * 225; c.pX = a.prior_X + (size_t)b * 15;
-    c.prior_on = a.has_prior[b] && ((a.mode == LIW_MODE_TRACK && !a.fast_mode) || a.mode == LIW_MODE_MARG);
+    AsmCtx c = asm_ctx(a.w, n, a.mode, a.fast_mode, b, a.prior_J, a.prior_X,
+                       a.has_prior[b] && ((a.mode == LIW_MODE_TRACK && !a.fast_mode) || a.mode == LIW_MODE_MARG));
+    bind(c, a.w, 0, a.x + (size_t)b * n * 15);   // standalone linearise writes buffer 0
+    c.buf = a.buf;
     double* H = a.H + (size_t)b * N * N;
     double* g = a.g + (size_t)b * N;
     for (size_t e = lane; e < (size_t)N * N; e += 64) H[e] = 0.0;
@@ -1727,15 +1667,10 @@ __global__ __launch_bounds__(64) void k_export_dense(ExportArgs a) {
 template <class TILES>
 __device__ __forceinline__ bool marg_chain(const MargArgs& a, const int b, TILES& T) {
     const int lane = threadIdx.x & 63, n = a.n;
-    AsmCtx c;
-    c.pif = a.w.pi_frame;
-    c.plc = a.w.pl_compact;
+    AsmCtx c = asm_ctx(a.w, n, LIW_MODE_MARG, 0, b, a.prior_J, a.prior_X, a.has_prior[b] != 0);
     const int sel = a.use_cur ? __builtin_amdgcn_readfirstlane(a.w.lm[b].cur) : 0;
-    c.n = n; c.mode = LIW_MODE_MARG; c.fast = 0; c.b = b; c.buf = sel;
+    c.buf = sel; c.x = a.x + (size_t)b * n * 15;
     c.PL = sel ? a.w.PL[1] : a.w.PL[0]; c.PI = sel ? a.w.PI[1] : a.w.PI[0]; c.PW = sel ? a.w.PW[1] : a.w.PW[0]; c.PG = sel ? a.w.PG[1] : a.w.PG[0];
-    c.x = a.x + (size_t)b * n * 15;
-    c.pJ = a.prior_J + (size_t)b * 225; c.pX = a.prior_X + (size_t)b * 15;
-    c.prior_on = a.has_prior[b] != 0;
     STAMPM(5000);
     for (int e = lane; e < 256; e += 64) { T.CD[e] = 0.0; T.W[e] = 0.0; }
     if (lane < 16) T.Cg[lane] = 0.0;
@@ -2287,26 +2222,21 @@ void launch_lm_begin(int B, int n, LmState* lm, int max_iters, hipStream_t s) {
     hipLaunchKernelGGL(k_lm_begin, dim3((B + 63) / 64), dim3(64), 0, s, B, n, lm, max_iters);
 }
 void launch_lm_step(const StepArgs& a, hipStream_t s) {
-    // LIW_STEP_VARIANT (read per launch) 0 / 1 / 2 / 3 / 4: force the one-wave latency / one-wave throughput / four-wave / quad / dense two-frame variant (profiling, tests)
-    const char* env = getenv("LIW_STEP_VARIANT");
-    const bool tp = env ? env[0] == '1' : a.B > 2048;
-    // two waves per window while that does not take CUs away from other windows, and the chain is long enough to be worth cutting
-    const bool tw = (env ? env[0] == '2' : a.B <= 512) && a.n >= 6;   // (tools/step_variant_sweep.py: 97 k vs 67 k solves/s at 256 windows, 120 k vs 116 k at 512)
+    const StepVariant f = forced_step_variant();
     // four windows per wave (k_lm_quad.hip) once the batch is large enough to fill the chip that way; the windows it leaves out
     // (a rotation vector outside the |theta| <= pi ball) are stepped by the one-wave kernel right behind it
-    const bool quad = (env ? env[0] == '3' : a.B >= QUAD_MIN_BATCH) && lm_step_quad_fits(a);
-    if (quad) {
+    if (pi_frame_format(a.B, f) && lm_step_quad_fits(a)) {
         launch_lm_step_quad(a, s);
         StepArgs a2 = a;
         a2.only_slow = 1;
         hipLaunchKernelGGL(k_lm_step_slow, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a2);
         return;
     }
-    // a two-frame window (what the reference's tracking loop solves every laser frame) is ONE dense 30 x 30 system; variant 4 forces it
-    const bool dense2 = a.n == 2 && (env ? env[0] == '4' : true);
-    if (dense2) hipLaunchKernelGGL(k_lm_step_dense2, dim3(a.B), dim3(64), 0, s, a);
-    else if (tw) hipLaunchKernelGGL(k_lm_step_tw, dim3(a.B), dim3(256), 0, s, a);
-    else if (tp) hipLaunchKernelGGL(k_lm_step<true>, dim3(a.B), dim3(64), 0, s, a);
+    // a two-frame window (what the reference's tracking loop solves every laser frame) is ONE dense 30 x 30 system
+    if (a.n == 2 && step_variant_is(f, STEP_DENSE2, true)) hipLaunchKernelGGL(k_lm_step_dense2, dim3(a.B), dim3(64), 0, s, a);
+    // two waves per window while that takes no CUs away from other windows and the chain is worth cutting (tools/step_variant_sweep.py: 97 k vs 67 k solves/s at 256 windows, 120 k vs 116 k at 512)
+    else if (a.n >= 6 && step_variant_is(f, STEP_TWO_WAVE, a.B <= 512)) hipLaunchKernelGGL(k_lm_step_tw, dim3(a.B), dim3(256), 0, s, a);
+    else if (step_variant_is(f, STEP_THROUGHPUT, a.B > 2048)) hipLaunchKernelGGL(k_lm_step<true>, dim3(a.B), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_lm_step<false>, dim3(a.B), dim3(64), 0, s, a);
 }
 void launch_lm_finish(const StepArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_lm_finish, dim3((a.B * a.n * 6 + 255) / 256), dim3(256), 0, s, a); }

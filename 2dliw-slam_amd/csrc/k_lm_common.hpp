@@ -1,13 +1,11 @@
-// k_lm_common.hpp — device helpers shared by the LM step kernels (k_lm.hip, k_lm_quad.hip): Ceres' trust-region constants, DPP wave /
-// row reductions, the so3 local parameterisation (reference src/factor/factor_common.h:37-60), the constant-block test of the TRACK
-// topology (solver.cpp:787-794).
+// k_lm_common.hpp — device helpers shared by the LM step kernels (k_lm.hip, k_lm_quad.hip): DPP wave / row reductions, the so3 local
+// parameterisation (reference src/factor/factor_common.h:37-60), the constant-block test of the TRACK topology (solver.cpp:787-794).
+// Ceres' trust-region constants and rules are not here: liw_lm_rules.hpp (through liw_kernels.hpp) states them for host and device.
 #pragma once
 #include "liw_kernels.hpp"
 
 namespace liw {
 
-constexpr double kMinDiag = 1e-6, kMaxDiag = 1e32, kMinRelDec = 1e-3, kFuncTol = 1e-6, kGradTol = 1e-10, kParamTol = 1e-8;
-constexpr double kMaxRadius = 1e16, kMinRadius = 1e-32, kInitRadius = 1e4;
 constexpr double kPi = 3.141592653589793238462643383279, kTwoPi = 6.283185307179586476925286766559;
 
 // Cross-lane reductions on DPP row operations (v_mov_b32_dpp on both halves of the double): a row of 16 lanes in 4 steps, the four

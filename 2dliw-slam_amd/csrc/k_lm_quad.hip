@@ -173,7 +173,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     if (clk_k) g_qclk[12] = clock64();
     double inv_radius;
     // ---------------------------------------------------------------- prologue: cost of the initial point / the pending candidate,
-    //      accept / reject, Ceres' termination tests (k_lm_step's prologue, statement for statement, per row)
+    //      accept / reject, Ceres' termination tests (liw_lm_rules.hpp), per row
     {
         double radius = st.radius, dec = st.decrease_factor, x_cost = st.x_cost, x_norm = st.x_norm;
         const int max_iters = st.max_iters, successful0 = st.successful;
@@ -211,20 +211,19 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
             x_cost = cost; initial_cost = cost; minimum_cost = cost;
             fail_eval = !isfinite(cost);          // IterationZero: non-finite residual -> FAILURE, nothing applied (Jacobians: after the sweep below)
         } else if (have_cand) {
-            const double cand_cost = isfinite(cost) ? cost : 1.7976931348623157e308;
-            if (cand_step_norm <= kParamTol * (x_norm + kParamTol)) term = 3;
-            else if (fabs(x_cost - cand_cost) <= kFuncTol * x_cost) term = 2;
+            const double cand_cost = isfinite(cost) ? cost : kFailedEvalCost;
+            term = lm_candidate_term(cand_step_norm, x_norm, x_cost, cand_cost);
             if (!term) {
                 const double rho = (x_cost - cand_cost) / model0;
-                accept = rho > kMinRelDec;
+                accept = lm_accepts(rho);
                 if (accept) {
                     cur = cb; x_cost = cand_cost;
-                    const double t3 = 2.0 * rho - 1.0;
-                    radius = fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - t3 * t3 * t3));
-                    dec = 2.0; reuse = 0; successful += 1;
+                    lm_step_accepted(rho, radius, dec, reuse);
+                    successful += 1;
                     if (x_cost < minimum_cost) minimum_cost = x_cost;
                 } else {
-                    radius = radius / dec; dec *= 2.0; reuse = 1; last_successful = false;
+                    lm_step_rejected(radius, dec, reuse);
+                    last_successful = false;
                 }
             }
         } else {
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
             }
             proceed = false;
         }
-        const bool cap = proceed && iteration >= max_iters && !fresh;
+        const bool cap = proceed && lm_cap_reached(iteration, max_iters, fresh);
         // the LM state as k_lm_step leaves it when a launch ends after the prologue; the tail below re-reads radius / decrease_factor
         if (proceed && j == 0) {
             st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm; st.cur = cur;
@@ -752,10 +751,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     }
     // ---- FinalizeIterationAndCheckIfMinimizerCanContinue, part 2
     {
-        int t2 = 0;
-        if (fresh) { if (gmax <= kGradTol) t2 = 1; }
-        else if (last_successful && gmax <= kGradTol) t2 = 1;
-        if (!t2 && !(1.0 > kMinRadius * inv_radius)) t2 = 5;     // radius > min_trust_region_radius
+        const int t2 = lm_gradient_term(fresh, last_successful, gmax, 1.0 > kMinRadius * inv_radius);   // (radius > min_trust_region_radius)
         if (proceed && t2) {
             if (j == 0) { st.done = 1; st.termination = t2; st.reuse_diagonal = reuse; st.have_candidate = 0; }
             proceed = false;
@@ -884,14 +880,14 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     const double step_norm = sqrt(row_sum(sn2));
     // model cost change -(s'g_s + s'A s/2) with s = -y and (A + D^2) y = g_s  ==  (y'g_s + y'D^2 y)/2
     const double model_cost_change = 0.5 * (ytg + row_sum(dsum));
-    const bool valid = solved && model_cost_change > 0.0 && isfinite(model_cost_change);
+    const bool valid = lm_step_valid(solved, model_cost_change);
     const int invalid0 = st.invalid_steps, successful = st.successful;
-    const bool fail5 = !valid && invalid0 + 1 >= 5;
+    const bool fail5 = !valid && lm_gives_up(invalid0);
     if (proceed && fail5 && successful > 0) {   // max_num_consecutive_invalid_steps: FAILURE hands back the states the solve started from
         for (int e = j; e < n * 15; e += 16) X[oX + (unsigned)e] = LMD[oLM + LM_X0 + (unsigned)e];
     }
     if (proceed && j == 0) {
-        const double radius = st.radius, dec = st.decrease_factor;
+        double radius = st.radius, dec = st.decrease_factor;
         st.iteration = iteration + 1;
         if (fail5 && successful > 0) st.x_cost = st.initial_cost;
         if (valid) {
@@ -901,7 +897,8 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
             st.invalid_steps = invalid0 + 1;
             st.have_candidate = 0;
             if (fail5) { st.done = 1; st.termination = 6; st.iteration = iteration; }
-            st.radius = radius / dec; st.decrease_factor = dec * 2.0; st.reuse_diagonal = 1;
+            lm_step_rejected(radius, dec, reuse);
+            st.radius = radius; st.decrease_factor = dec; st.reuse_diagonal = reuse;
         }
     }
 }

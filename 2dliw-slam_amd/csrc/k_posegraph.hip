@@ -794,11 +794,10 @@ static int pg_run(const PgCall& q) {
         return m;
     };
 
-    // ---- Ceres trust-region Levenberg-Marquardt (defaults)
+    // ---- Ceres trust-region Levenberg-Marquardt (defaults): constants and rules of liw_lm_rules.hpp
     const int K = max_iters > 0 ? max_iters : 50;
-    const double kMinDiagH = 1e-6, kMaxDiagH = 1e32, kMinRelDecH = 1e-3, kFuncTolH = 1e-6, kGradTolH = 1e-10, kParamTolH = 1e-8;
-    double radius = 1e4, decrease_factor = 2.0, x_cost = 0.0;
-    bool reuse_diagonal = false;
+    double radius = kInitRadius, decrease_factor = 2.0, x_cost = 0.0;
+    int reuse_diagonal = 0;
     liw_summary sum{};
     if (int r = evaluate(x, dx, true, &x_cost)) return r;
     if (linearize_only) {   // dense tangent-space normal equations (lower triangle mirrored), constant key frame = identity block
@@ -819,16 +818,14 @@ static int pg_run(const PgCall& q) {
     double gmax = gradient_max_norm();
     int iteration = 0, invalid_steps = 0, termination = 0, successful = 0;
     bool last_successful = true;
-    if (gmax <= kGradTolH) termination = 1;
     while (!termination) {
-        if (iteration >= K) { termination = 4; break; }
-        if (iteration > 0 && last_successful && gmax <= kGradTolH) { termination = 1; break; }
-        if (!(radius > 1e-32)) { termination = 5; break; }
+        if (iteration >= K) { termination = 4; break; }   // (K >= 1: never at iteration zero)
+        if ((termination = lm_gradient_term(iteration == 0, last_successful, gmax, radius > kMinRadius))) break;
         ++iteration;
         for (int i = 0; i < n; ++i) gs[i] = is_const(i) ? 0.0 : g[i] * scale[i];
         if (!reuse_diagonal)
-            for (int i = 0; i < n; ++i) dgn[i] = is_const(i) ? 0.0 : std::min(std::max(Hdiag[i] * scale[i] * scale[i], kMinDiagH), kMaxDiagH);
-        reuse_diagonal = true;
+            for (int i = 0; i < n; ++i) dgn[i] = is_const(i) ? 0.0 : std::min(std::max(Hdiag[i] * scale[i] * scale[i], kMinDiag), kMaxDiag);
+        reuse_diagonal = 1;
         up(dscale, scale.data(), sizeof(double) * n); up(ddgn, dgn.data(), sizeof(double) * n);
         std::fill(y.begin(), y.end(), 0.0);
         std::memcpy(y.data(), gs.data(), sizeof(double) * n);
@@ -861,16 +858,14 @@ static int pg_run(const PgCall& q) {
         for (int i = 0; i < n && solved; ++i) if (!std::isfinite(y[i])) solved = false;
         // model cost change with (A + D^2) y = g_s, step = -y:  (y'g_s + y'D^2 y) / 2
         double model_cost_change = 0.0;
-        bool valid = false;
         if (solved) {
             double ytg = 0.0, dsum = 0.0;
             for (int i = 0; i < n; ++i) if (!is_const(i)) { ytg += y[i] * gs[i]; dsum += dgn[i] / radius * y[i] * y[i]; }
             model_cost_change = 0.5 * (ytg + dsum);
-            valid = model_cost_change > 0.0 && std::isfinite(model_cost_change);
         }
-        if (!valid) {
-            if (++invalid_steps >= 5) { termination = 6; --iteration; break; }
-            radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
+        if (!lm_step_valid(solved, model_cost_change)) {
+            if (lm_gives_up(invalid_steps++)) { termination = 6; --iteration; break; }
+            lm_step_rejected(radius, decrease_factor, reuse_diagonal);
             last_successful = false;
             continue;
         }
@@ -880,26 +875,27 @@ static int pg_run(const PgCall& q) {
         plus(x, delta, cand);
         double candidate_cost = 0.0;
         if (int r = evaluate(cand, dxc, false, &candidate_cost)) return r;
-        if (!std::isfinite(candidate_cost)) candidate_cost = 1.7976931348623157e308;
+        if (!std::isfinite(candidate_cost)) candidate_cost = kFailedEvalCost;
         double step_norm = 0.0;
         for (int i = 0; i < n; ++i) if (!is_const(i)) step_norm += (x[i] - cand[i]) * (x[i] - cand[i]);
         step_norm = std::sqrt(step_norm);
-        if (step_norm <= kParamTolH * (x_norm + kParamTolH)) { termination = 3; break; }
-        if (std::fabs(x_cost - candidate_cost) <= kFuncTolH * x_cost) { termination = 2; break; }
+        if ((termination = lm_candidate_term(step_norm, x_norm, x_cost, candidate_cost))) break;
         const double rho = (x_cost - candidate_cost) / model_cost_change;
-        if (rho > kMinRelDecH) {
+        if (lm_accepts(rho)) {
             x = cand;
             if (int r = evaluate(x, dx, true, &x_cost)) return r;
             x_norm = 0.0;
             for (int i = 0; i < n; ++i) if (!is_const(i)) x_norm += x[i] * x[i];
             x_norm = std::sqrt(x_norm);
             gmax = gradient_max_norm();
-            radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3.0)));
-            decrease_factor = 2.0; reuse_diagonal = false;
+            // not lm_step_accepted: this loop is compared against the oracle, which cubes with pow() as Ceres does; the kernels' two
+            // multiplications may differ from it in the last bit
+            radius = std::min(kMaxRadius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3.0)));
+            decrease_factor = 2.0; reuse_diagonal = 0;
             ++successful;
             last_successful = true;
         } else {
-            radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
+            lm_step_rejected(radius, decrease_factor, reuse_diagonal);
             last_successful = false;
         }
     }

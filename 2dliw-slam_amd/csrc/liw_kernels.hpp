@@ -6,6 +6,7 @@
 
 #include "../../include/liw_window.h"
 #include "liw_dual.hpp"
+#include "liw_lm_rules.hpp"
 
 namespace liw {
 
@@ -45,10 +46,17 @@ constexpr int PIF_D = 0, PIF_IJ = 120, PIF_GJ = 345, PIF_GI = 360, PIF_C = 375, 
 // (tools/step_variant_sweep.py, end of round 4, C2 windows, 12 iterations: 1 024 windows 185 k solves/s with the quad kernel against 173 k with
 //  the one-wave kernels, 2 048: 280 k against 255 k; 512: 111 k against 122 k for the four-wave kernel.  The threshold was 2 049 until then.)
 constexpr int QUAD_MIN_BATCH = 1024;
-inline bool pi_frame_format(int B) {
+// The LM step kernels (launch_lm_step picks one per launch by batch size and window length).  LIW_STEP_VARIANT = 0 .. 4, read per call,
+// forces one (profiling, tests): a forced variant that cannot take the launch, or any other text, leaves the latency kernel.
+enum StepVariant { STEP_AUTO = -1, STEP_LATENCY = 0, STEP_THROUGHPUT = 1, STEP_TWO_WAVE = 2, STEP_QUAD = 3, STEP_DENSE2 = 4 };
+inline StepVariant forced_step_variant() {
     const char* env = getenv("LIW_STEP_VARIANT");
-    return env ? env[0] == '3' : B >= QUAD_MIN_BATCH;
+    if (!env) return STEP_AUTO;
+    return env[0] >= '1' && env[0] <= '4' ? (StepVariant)(env[0] - '0') : STEP_LATENCY;
 }
+// is variant v in play: forced, or — with nothing forced — by the size rule the caller states
+inline bool step_variant_is(StepVariant forced, StepVariant v, bool by_size) { return forced == STEP_AUTO ? by_size : forced == v; }
+inline bool pi_frame_format(int B, StepVariant forced = forced_step_variant()) { return step_variant_is(forced, STEP_QUAD, B >= QUAD_MIN_BATCH); }
 __host__ __device__ inline size_t pi_doubles_per_window(int n) {               // room for either format
     const size_t a = (size_t)(n > 1 ? n - 1 : 1) * PIS, b = (size_t)n * PIFS;
     return a > b ? a : b;
@@ -93,7 +101,7 @@ struct LmState {
 
 // state of a window at the start of a solve (k_lm_begin; the first k_lin_all of a single-window solve)
 __device__ __forceinline__ void lm_reset(LmState& s, int max_iters) {
-    s.radius = 1e4; s.decrease_factor = 2.0; s.x_cost = 0.0; s.x_norm = 0.0; s.minimum_cost = 0.0;
+    s.radius = kInitRadius; s.decrease_factor = 2.0; s.x_cost = 0.0; s.x_norm = 0.0; s.minimum_cost = 0.0;
     s.cand_step_norm = 0.0; s.model_cost_change = 0.0; s.reuse_diagonal = 0; s.iteration = 0; s.done = 0; s.termination = 0;
     s.successful = 0; s.cur = 0; s.invalid_steps = 0; s.have_candidate = 0; s.initial_cost = 0.0; s.max_iters = max_iters; s.pad_ = 0;
 }
