@@ -41,6 +41,7 @@
 //                  prediction from the wheel increment before the scan; the key-frame decision after the solve.  A lane per robot,
 //                  work-groups of 256, no LDS, no atomics, no scratch; _begin evaluates its sin / cos / atan2
 //                  correctly rounded (liw_crmath.hpp)
+//   k_lfe_crmath   liw_crmath.hpp's sin / cos / atan2 element by element (liw_lfe_crmath_eval: a diagnostic entry for the tests)
 //   k_lfe_scan / k_lfe_pack   laser_off exclusive scan (one block), then the component-major laser arrays
 //   k_lfe_scan_init / k_lfe_pack_init   the same for INIT windows: blocks of frames 1 .. n-1, a work-group per window
 // The line_map of a slot is a list of 64-bit entries (cell key << 32 | line index) kept sorted: within a cell the host
@@ -1559,6 +1560,16 @@ __global__ void __launch_bounds__(256) k_lfe_track_end(const void* store, Lay L,
     }
 }
 
+// liw_lfe_crmath_eval: the three functions of liw_crmath.hpp as the CR scalar above calls them, a lane per element (a diagnostic
+// entry: tests/test_gpu_crmath.py compares the device compile of the header with a multi-precision reference).  out may alias a:
+// a lane reads its element before it writes it.
+__global__ void __launch_bounds__(256) k_lfe_crmath(int op, int n, const double* a, const double* b, double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    out[i] = op == 0 ? liw_cr::cr_sin(x) : (op == 1 ? liw_cr::cr_cos(x) : liw_cr::cr_atan2(x, b[i]));
+}
+
 }  // namespace lfe
 
 using namespace lfe;
@@ -1918,6 +1929,14 @@ int liw_lfe_track_get(liw_lfe_ctx* c, const void* track, int robot, double* tf12
     if (stamp) *stamp = t.stamp;
     if (counters) { counters[0] = t.tracked; counters[1] = t.keys; counters[2] = t.skipped; }
     return LIW_OK;
+}
+
+int liw_lfe_crmath_eval(liw_lfe_ctx* c, int op, int n, const double* a, const double* b, double* out, void* stream) {
+    LFE_DEV(c);
+    if (op < 0 || op > 2 || n < 0 || !a || !out || (op == 2 && !b)) return fail(c, LIW_EINVAL, "liw_lfe_crmath_eval: bad argument");
+    if (n == 0) return LIW_OK;
+    hipLaunchKernelGGL(k_lfe_crmath, dim3(blocks((size_t)n, 256)), dim3(256), 0, (hipStream_t)stream, op, n, a, b, out);
+    return launched(c);
 }
 
 int liw_lfe_status(liw_lfe_ctx* c, const void* store, int robot, int slot) {

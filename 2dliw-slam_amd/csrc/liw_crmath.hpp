@@ -3,9 +3,18 @@
 // up to an ulp or two, glibc's by at most 0.55 ulp, so the correctly rounded value is what glibc returns in all but a fraction of
 // a per cent of the arguments.  Used by the tracking glue (k_lfe_track_begin): a last-bit difference in the de-skew twist or the
 // predicted pose is amplified by every free-running solve that follows.
-//   cr_sincos: |x| scaled by 2^-k to at most 0.25, Taylor series to x^27 in double-double, k double-angle steps (the error grows
-//   by 4 per step from 2^-104; arguments beyond 2^20 go to the plain functions).  cr_atan2: one Newton correction of the plain
-//   atan2 with the double-double sine and cosine of that estimate: y + (s C - c S) / (c C + s S).
+//   sincos_dd: x - n pi/2 with n = rint(x 2/pi) and pi/2 carried as four doubles, as a double-double r, |r| <= pi/4: the
+//   products n P_i are error-free, the terms down to 2^-53 |x| are summed exactly and what is left, below 2^-105 |x|, is added in
+//   double-double: the absolute error of r is about 2^-209 |x| <= 2^-189, while no double at all is closer than 2^-62 to a
+//   multiple of pi/2 (the known worst case of this reduction), so r keeps its 2^-104 relative error however close x comes to one.
+//   Then r is halved at most twice to |r| <= 0.25, the Taylor series runs to r^27 in double-double, the halvings are undone by
+//   double-angle steps (the cosine stays above 0.7 there: no cancellation) and n & 3 picks the quadrant.  The relative error of
+//   the sine and of the cosine is below 2^-98 everywhere, which a rounding to 53 bits cannot see unless the exact value lies within
+//   2^-45 ulp of a rounding boundary.  Arguments beyond 2^20, infinities and NaN go to the plain functions.
+//   cr_atan2: one Newton correction of the plain atan2 with the double-double sine and cosine of that estimate:
+//   y + (s C - c S) / (c C + s S).  Where |result| < 2^-969 the low word of the quotient is subnormal and the result is within an
+//   ulp, not correctly rounded.
+// Tested on the host and on the device against a 500-bit reference (tests/test_crmath.py, tests/test_gpu_crmath.py).
 // fma() is called explicitly (error-free products); the translation unit may have contraction off.
 #pragma once
 #include <cmath>
@@ -56,26 +65,42 @@ LIW_CR_HD inline DD div_d(const DD& a, double b) { return div(a, DD{b, 0.0}); }
 
 // double-double sine and cosine of the double x, |x| <= 2^20
 LIW_CR_HD inline void sincos_dd(double x, DD& s, DD& c) {
+    // pi/2 = P0 + P1 + P2 + P3 to 2^-218; n < 2^20: what is missing from n pi/2 is below 2^-197
+    const double P0 = 0x1.921fb54442d18p+0, P1 = 0x1.1a62633145c07p-54, P2 = -0x1.f1976b7ed8fbcp-110, P3 = 0x1.4cf98e804177dp-164;
+    const double n = rint(x * 0x1.45f306dc9c883p-1);
+    DD r = DD{x, 0.0};
+    if (n != 0.0) {
+        const DD a0 = two_prod(n, P0), a1 = two_prod(n, P1), a2 = two_prod(n, P2);
+        const double t = x - a0.h;                        // exact (Sterbenz): a0.h / 2 <= x <= 2 a0.h for every n != 0
+        const DD u = two_sum(-a0.l, -a1.h);               // the two terms of order 2^-53 |x|, exactly
+        const DD v = two_sum(t, u.h);                     // v.h + v.l + u.l = x - n (P0 + P1) + a1.l exactly
+        DD w = add(two_sum(v.l, u.l), two_sum(-a1.l, -a2.h));   // all below 2^-105 |x|: double-double is 2^-209 |x| here
+        w = add(w, two_sum(-a2.l, -(n * P3)));
+        r = add(DD{v.h, 0.0}, w);
+    }
     int k = 0;
-    double r = x;
-    while (fabs(r) > 0.25) { r *= 0.5; ++k; }   // exact
-    const DD rr = DD{r, 0.0}, r2 = two_prod(r, r);
-    DD ts = rr, tc = DD{1.0, 0.0};
-    s = rr;
-    c = tc;
+    while (fabs(r.h) > 0.25) { r.h *= 0.5; r.l *= 0.5; ++k; }   // exact, at most twice
+    const DD r2 = mul(r, r);
+    DD ts = r, tc = DD{1.0, 0.0};
+    DD ss = r, cc = tc;
 #pragma unroll 1
     for (int i = 1; i <= 13; ++i) {
         tc = neg(div_d(mul(tc, r2), (double)((2 * i - 1) * (2 * i))));
         ts = neg(div_d(mul(ts, r2), (double)((2 * i) * (2 * i + 1))));
-        c = add(c, tc);
-        s = add(s, ts);
+        cc = add(cc, tc);
+        ss = add(ss, ts);
     }
 #pragma unroll 1
     for (int i = 0; i < k; ++i) {   // sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a
-        const DD sc = mul(s, c), ss = mul(s, s);
-        s = DD{2.0 * sc.h, 2.0 * sc.l};
-        c = sub(DD{1.0, 0.0}, DD{2.0 * ss.h, 2.0 * ss.l});
+        const DD sc = mul(ss, cc), s2 = mul(ss, ss);
+        ss = DD{2.0 * sc.h, 2.0 * sc.l};
+        cc = sub(DD{1.0, 0.0}, DD{2.0 * s2.h, 2.0 * s2.l});
     }
+    const int q = (int)n & 3;   // x = r + n pi/2
+    s = (q & 1) ? cc : ss;
+    c = (q & 1) ? ss : cc;
+    if (q == 2 || q == 3) s = neg(s);
+    if (q == 1 || q == 2) c = neg(c);
 }
 
 LIW_CR_HD inline double cr_sin(double x) {

@@ -17,6 +17,7 @@ LFE_EXPORTS = [
     "liw_lfe_spawn_corners", "liw_lfe_corners_to_world", "liw_lfe_match_front", "liw_lfe_pack_init", "liw_lfe_rebuild",
     "liw_lfe_add_scan_flags", "liw_lfe_add_scan_path",
     "liw_lfe_track_layout", "liw_lfe_track_init", "liw_lfe_track_begin", "liw_lfe_track_end", "liw_lfe_track_get",
+    "liw_lfe_crmath_eval",
 ]
 
 ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID, ST_CORNERS = 1, 2, 4, 8, 16, 32
@@ -95,6 +96,7 @@ def _lib():
         L.liw_lfe_track_begin.argtypes = [vp, tpp] + [vp] * 12
         L.liw_lfe_track_end.argtypes = [vp, tpp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_track_get.argtypes = [vp, vp, C.c_int, dp, dp, dp, ip]
+        L.liw_lfe_crmath_eval.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
         L.liw_lfe_status.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_num_lines.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_get_lines.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int]
@@ -494,6 +496,22 @@ class BatchFrontEnd:
         self._chk_get(self.L.liw_lfe_track_get(self.h, self._p(self._track(track)), int(robot), tf.ctypes.data_as(dp), a.ctypes.data_as(dp), C.byref(st),
                                                cn.ctypes.data_as(C.POINTER(C.c_int))))
         return dict(last_keyframe_tf=tf, angular_local=a, stamp=float(st.value), tracked=int(cn[0]), keys=int(cn[1]), skipped=int(cn[2]))
+
+    # ----------------------------------------------------------------------------------------------------- diagnostics
+    CR_SIN, CR_COS, CR_ATAN2 = 0, 1, 2
+
+    def crmath_eval(self, op, a, b=None, out=None):
+        """the sin (op 0), cos (op 1) or atan2(a, b) (op 2) of csrc/liw_crmath.hpp as track_begin evaluates them on the device, element
+        by element in one launch: a, b float64 device tensors of n elements (b only for op 2), out such a tensor to write into (a
+        itself is allowed) or None for a fresh one.  A diagnostic entry for the tests, on no tracking path."""
+        torch = self.torch
+        a = self._out(a, torch.float64, 0)
+        n = a.numel()
+        if b is not None:
+            self._out(b, torch.float64, n)
+        out = torch.empty_like(a) if out is None else self._out(out, torch.float64, n)
+        self._chk(self.L.liw_lfe_crmath_eval(self.h, int(op), int(n), self._p(a), self._p(b), self._p(out), self._s()))
+        return out
 
     # -------------------------------------------------------------------------------------------------------- getters
     def status(self, robot, slot=ROBOT):

@@ -225,7 +225,8 @@ int liw_lfe_rebuild(liw_lfe_ctx* ctx, void* store, int first_slot, int F, const 
  * Mapping: a lane per robot, work-groups of 256, no LDS, no atomics.  The arithmetic is liw_lie.h's, in the reference's order, with
  * the device sin / cos / atan2: results agree with the host to round-off, and a decision can differ from the host's only where a
  * quantity is within round-off of its threshold.  liw_lfe_track_begin evaluates those three functions correctly rounded, which is
- * what the host's libm returns for all but about 0.1 % of the arguments: its twist and pose are bit-identical to the host's then,
+ * what the host's libm returns for all but about 0.1 % of the arguments (sin and cos of |x| <= 2^20, multiples of pi/2 included:
+ * liw_lfe_crmath_eval below is how the tests see it): its twist and pose are bit-identical to the host's then,
  * so that a free-running chain of solves does not start from a last-bit difference. */
 typedef struct liw_lfe_track_params {
     double T_imu_to_wheel[16];   /* 4x4 row-major, loaded as liw_lie_from_matrix16 does */
@@ -276,6 +277,15 @@ int liw_lfe_track_end(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, void* tr
 /* the record of one robot (synchronous; tests and tools): tf12 = last_keyframe_tf, angular3, stamp, counters [3] = tracked, key,
  * skipped frames.  Any output may be NULL.  LIW_EINVAL: a null track, robot outside 0 .. B-1. */
 int liw_lfe_track_get(liw_lfe_ctx* ctx, const void* track, int robot, double* tf12, double* angular3, double* stamp, int* counters);
+
+/* A diagnostic entry, on no tracking path: the sin (op 0), cos (op 1) or atan2(a, b) (op 2) that liw_lfe_track_begin evaluates
+ * (csrc/liw_crmath.hpp, as compiled for the device), element by element: out[i] = f(a[i]) or f(a[i], b[i]) for i = 0 .. n-1.  a, b,
+ * out are device arrays of n doubles; b is not read and may be NULL for ops 0 and 1; out may alias a or b.  A lane per element,
+ * work-groups of 256, one launch on `stream`; n = 0 launches nothing.  Results are the correctly rounded values for finite
+ * |a| <= 2^20 (sin, cos) and for finite arguments below 1e300 that are not both below 1e-300 (atan2; within an ulp where the
+ * result is below 2^-969); every other argument goes to the device library's function (tests/test_gpu_crmath.py).
+ * LIW_EINVAL: op outside 0 .. 2, n < 0, a null a or out, a null b with op 2. */
+int liw_lfe_crmath_eval(liw_lfe_ctx* ctx, int op, int n, const double* a, const double* b, double* out, void* stream);
 
 /* getters (synchronous device -> host copies; tests and tools).  slot: 0 .. slots-1, LIW_LFE_REF or LIW_LFE_SPAWNING. */
 /* status word of robot / slot (slot = LIW_LFE_ROBOT: the robot word); a missing sub-map reads LIW_LFE_NONE */

@@ -63,7 +63,8 @@ def _rel(a, b):
 @pytest.mark.parametrize("name", ["office", "second"])
 def test_begin_end_against_restatement(liw, synth, name):
     """B = 130 (two full waves and a two-lane tail), room scans in slot 0, count a free input, strided state rows for track_init, five
-    robots masked out; two pages of cases cover the generator's full cross product.  "second" is the parameter set with a 0.48 rad
+    robots masked out; two pages of cases cover the generator's full cross product, and a third page (make_planar_cases) is the
+    workload's own geometry, rotation about z only, with yaws at and next to +-pi/2, +-3 pi/4 and +-(pi - 2e-3).  "second" is the parameter set with a 0.48 rad
     turn and a lever arm in T_imu_to_wheel and a laser extrinsic off the office value (a transposed extrinsic would show:
     tests/test_laser_track_abi.py::test_transposed_extrinsics_would_show)."""
     import torch
@@ -91,8 +92,8 @@ def test_begin_end_against_restatement(liw, synth, name):
     mask[masked] = 0
     worst = dict(linear=0.0, angular=0.0, pose_new=0.0, kf=0.0, ang=0.0)
     combos = set()
-    for page in range(2):
-        c = ref.make_cases(g, synth, B, lines, seed=40 + page, page=page)
+    for page in range(3):   # two pages of random axes, then the planar page: yaws at and next to +-pi/2, +-3 pi/4, +-(pi - 2e-3)
+        c = (ref.make_cases if page < 2 else ref.make_planar_cases)(g, synth, B, lines, seed=40 + page, page=page)
         combos.update(tuple(int(v) for v in row) for row in c["combo"])
         e = ref.expected(g, c, lines, mask=mask)
         for b in np.nonzero(mask)[0]:   # the cases keep their distance from the thresholds at this parameter set too
@@ -173,7 +174,7 @@ def test_begin_end_against_restatement(liw, synth, name):
         for buf, fill in [(tbuf, FILL_B), (xbuf, FILL)] + [(v[0], FILL_B if v[0].dtype == torch.uint8 else FILL) for v in list(outs.values()) + list(eo.values())]:
             assert _guards_ok(buf, fill)
     assert len(combos) == ref.N_COMBOS
-    print("track_begin / track_end, %s set, 2 x %d robots: worst |device - restatement| / max(1, |value|): %s"
+    print("track_begin / track_end, %s set, 3 x %d robots: worst |device - restatement| / max(1, |value|): %s"
           % (name, B, ", ".join("%s %.2e" % kv for kv in worst.items())))
     for k, v in worst.items():
         assert v <= BAR, (k, v)

@@ -84,6 +84,8 @@ def test_no_cpu_fallback(liw):
         assert L.liw_lfe_get_lines(h, p, 0, 0, buf.ctypes.data_as(C.POINTER(C.c_double)), 1) == ENODEV
         assert L.liw_lfe_cell_lines(h, p, 0, 0, 0.0, 0.0, None, 0) == ENODEV
         assert L.liw_lfe_submap_pose(h, p, 0, -1, None, None) == ENODEV
+        assert L.liw_lfe_crmath_eval(h, 0, 8, p, None, p, None) == ENODEV
+        assert L.liw_lfe_crmath_eval(None, 0, 8, p, None, p, None) == -22
         assert b"gfx950" in L.liw_lfe_last_error(h) or b"no HIP device" in L.liw_lfe_last_error(h)
     finally:
         L.liw_lfe_destroy(h)

@@ -179,3 +179,44 @@ def test_transposed_extrinsics_would_show(liw, synth, generated):
         # wheel: the predicted pose; laser: both twist vectors and the key-frame delta
         watched = cols[0:6] if which == "Tiw" else np.concatenate([cols[6:12], cols[12:14]])
         assert watched.max() > 1000 * BAR and np.median(watched) > 1000 * BAR, (which, cols)
+
+
+@pytest.mark.parametrize("name", ["office", "second"])
+def test_planar_page(liw, synth, name):
+    """make_planar_cases, the page of rotations about z that tests/test_gpu_laser_track.py adds to the random axes: it holds the yaws
+    it promises, its geometry is planar, every angle a logarithm returns stays within the restatements' range, its quantities keep
+    make_cases's distances from the thresholds, and on it the two restatements agree at the same bar."""
+    _, tp, lp = [s for s in ref.param_sets(liw, synth, projected=True) if s[0] == name][0]
+    g = ref.Glue(liw, tp, lp["T_imu_to_laser"], lp["normalize_extrinsics"])
+    gn = ref.GlueNumpy(synth, g.tp, None, None, T12_wheel=g.Tiw, T12_laser=g.Til)
+    B = 130
+    c = ref.make_planar_cases(g, synth, B, POOL, seed=42, page=2)
+    e = ref.expected(g, c, POOL)
+    yaws = ref.planar_yaws()
+    assert len(set(yaws)) == 18 and max(abs(y) for y in yaws) < ref.PLANAR_MAX_ANGLE
+    for base in (np.pi / 2, 3 * np.pi / 4, np.pi - 2e-3):
+        for v in (base, np.nextafter(base, 0.0), np.nextafter(base, 4.0)):
+            assert v in yaws and -v in yaws
+    assert set(c["x"][:, 1, 5]) == set(yaws)
+    assert not c["x"][:, :, [2, 3, 4, 8]].any() and not c["angular_local"][:, 0:2].any() and c["angular_local"][:, 2].all()
+    worst = 0.0
+    for b in range(B):
+        W = c["wheel_T"][b]
+        assert W[8] == 1.0 and W[11] == 0.0 and not W[[2, 5, 6, 7]].any() and abs(W[3]) > 5e-3   # a pure yaw, a planar translation
+        i_dt, i_p, i_q, i_c = (int(v) for v in c["combo"][b])
+        for value, thr, f in ((c["imu_Dt"][b], tp["min_delta_t"], ref.FACTORS[i_dt]), (e["dp"][b], tp["key_frame_p_motion_threshold"], ref.FACTORS[i_p]),
+                              (e["dq"][b], tp["key_frame_q_motion_threshold"], ref.FACTORS[i_q])):
+            assert abs(value / thr - f) <= 1e-9, (b, value, thr, f)
+        for q in (c["x"][b, 0, 3:6], c["x"][b, 1, 3:6], e["x"][b, 1, 3:6], c["kf_pose"][b, 3:6]):
+            assert np.linalg.norm(q) <= ref.PLANAR_MAX_ANGLE
+        st = c["x"][b, 1]
+        for a, h in zip(g.twist(st, c["angular_local"][b]), gn.twist(st, c["angular_local"][b])):
+            worst = max(worst, _close(h, a))
+        pn = g.predict(st, W)
+        worst = max(worst, _close(gn.predict(st, W), pn), _close(gn.tf_w_l(pn), g.tf_w_l(pn)))
+        kf = g.lie.make_tf(c["kf_pose"][b, 0:3], c["kf_pose"][b, 3:6])
+        for pose in (pn, st[0:6]):
+            worst = max(worst, _close(gn.delta(kf, pose), g.delta(kf, pose)))
+    assert 20 < int(e["skip"].sum()) < B - 20 and 10 < int(e["key"].sum()) < B - 10
+    print("track glue, %s set, planar page: liw_lie restatement against plain numpy, worst |difference| / max(1, |value|) %.3e" % (name, worst))
+    assert worst <= BAR, worst

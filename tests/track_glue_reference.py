@@ -231,16 +231,78 @@ def make_cases(glue, synth, B, pool_lines, seed=0, page=0):
         o["angular_local"][b] = _unit(rng) * rng.uniform(0.05, 1.5)
         o["imu_X"][b] = rng.normal(0.0, 0.05, 15)
         o["stamps"][b] = 100.0 + 0.1 * b
-        case = COUNT_CASES[i_c]
-        if case == "empty":
-            s, cnt = empties[b % len(empties)], 0
-        elif case == "equal":
-            s = evens[b % len(evens)]
-            cnt = pool_lines[s] // 2
+        o["scan"][b], o["count"][b] = _scan_and_count(COUNT_CASES[i_c], b, pool_lines)
+    return o
+
+
+def _scan_and_count(case, b, pool_lines):
+    """the scan of the pool and the match count that put robot b on the asked side of n_match < n_lines - n_match"""
+    empties = [i for i, n in enumerate(pool_lines) if n == 0]
+    evens = [i for i, n in enumerate(pool_lines) if n > 0 and n % 2 == 0]
+    full = [i for i, n in enumerate(pool_lines) if n >= 4]
+    if case == "empty":
+        return empties[b % len(empties)], 0
+    if case == "equal":
+        s = evens[b % len(evens)]
+        return s, pool_lines[s] // 2
+    s = full[b % len(full)]
+    return s, ((pool_lines[s] - 1) // 2 if case == "fewer" else pool_lines[s] // 2 + 1)
+
+
+PLANAR_MAX_ANGLE = np.pi - 1e-3   # the range the restatements state
+
+
+def planar_yaws():
+    """+-pi/2, +-3 pi/4, +-(pi - 2e-3) and the two neighbouring doubles of each: 18 angles.  The half angle exp_so3 takes of the first
+    is the double nearest pi/4, the arguments of the third sit next to pi/2: where a sine or a cosine reduced without enough words of
+    pi is wrong"""
+    out = []
+    for base in (np.pi / 2, 3 * np.pi / 4, np.pi - 2e-3):
+        for sgn in (1.0, -1.0):
+            out += [sgn * np.nextafter(base, 0.0), sgn * base, sgn * np.nextafter(base, 4.0)]
+    return out
+
+
+def make_planar_cases(glue, synth, B, pool_lines, seed=0, page=0):
+    """make_cases for the workload's own geometry, a robot that turns about z only: the state rotation vectors are (0, 0, yaw) with
+    the yaws of planar_yaws() (robot b takes number b % 18 in its current row), positions and velocities lie in the plane, the wheel
+    increment is a pure yaw with a planar translation and current_angular_local is along z.  The combinations of FACTORS^3 x
+    COUNT_CASES, the key-frame delta and the counts are make_cases's.  Every rotation angle a logarithm returns (the predicted pose,
+    the key-frame pose) is at most PLANAR_MAX_ANGLE."""
+    rng = np.random.default_rng(seed)
+    lie, tp = glue.lie, glue.tp
+    pool_lines = [int(v) for v in pool_lines]
+    yaws = planar_yaws()
+    o = dict(x=np.zeros((B, 2, 15)), kf_pose=np.zeros((B, 6)), angular_local=np.zeros((B, 3)), imu_X=np.zeros((B, 15)), imu_Dt=np.zeros(B),
+             wheel_T=np.zeros((B, 12)), stamps=np.zeros(B), scan=np.zeros(B, dtype=np.int64), count=np.zeros(B, dtype=np.int32),
+             combo=np.zeros((B, 4), dtype=np.int64))
+    nf = len(FACTORS)
+    for b in range(B):
+        ci = ((page * B + b) * 101) % N_COMBOS
+        i_dt, i_p, i_q, i_c = np.unravel_index(ci, (nf, nf, nf, len(COUNT_CASES)))
+        o["combo"][b] = (i_dt, i_p, i_q, i_c)
+        x = np.zeros((2, 15))
+        for r in range(2):
+            x[r, 0:2] = rng.uniform(-8.0, 8.0, 2)
+            x[r, 5] = yaws[(b + 7 * (1 - r)) % len(yaws)]
+            x[r, 6:8] = rng.uniform(-1.5, 1.5, 2)
+            x[r, 9:15] = rng.normal(0.0, 1e-2, 6)
+        Dt = FACTORS[i_dt] * tp["min_delta_t"]
+        for attempt in range(200):
+            turn = rng.uniform(0.01, 0.25) * (-np.sign(x[1, 5]) if attempt % 4 < 3 else np.sign(x[1, 5]))   # mostly away from pi
+            wheel = lie.make_tf(np.concatenate([rng.uniform(-0.2, 0.2, 2), [0.0]]), np.array([0.0, 0.0, turn]))
+            pose_end = x[1, 0:6].copy() if glue.skip(Dt) else glue.predict(x[1], wheel)
+            D = lie.make_tf(_unit(rng) * FACTORS[i_p] * tp["key_frame_p_motion_threshold"], _unit(rng) * FACTORS[i_q] * tp["key_frame_q_motion_threshold"])
+            kp, kq = lie.log_SE3(lie.mul(glue.tf_w_l(pose_end), lie.inverse(D)))
+            if max(np.linalg.norm(pose_end[3:6]), np.linalg.norm(kq)) <= PLANAR_MAX_ANGLE:
+                break
         else:
-            s = full[b % len(full)]
-            cnt = (pool_lines[s] - 1) // 2 if case == "fewer" else pool_lines[s] // 2 + 1
-        o["scan"][b], o["count"][b] = s, cnt
+            raise AssertionError("no planar case within the restatement's range for robot %d" % b)
+        o["x"][b], o["kf_pose"][b], o["wheel_T"][b], o["imu_Dt"][b] = x, np.concatenate([kp, kq]), wheel, Dt
+        o["angular_local"][b] = np.array([0.0, 0.0, rng.choice([-1.0, 1.0]) * rng.uniform(0.05, 1.5)])
+        o["imu_X"][b] = rng.normal(0.0, 0.05, 15)
+        o["stamps"][b] = 100.0 + 0.1 * b
+        o["scan"][b], o["count"][b] = _scan_and_count(COUNT_CASES[i_c], b, pool_lines)
     return o
 
 
