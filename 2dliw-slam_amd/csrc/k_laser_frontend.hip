@@ -41,6 +41,13 @@
 //                  prediction from the wheel increment before the scan; the key-frame decision after the solve.  A lane per robot,
 //                  work-groups of 256, no LDS, no atomics, no scratch; _begin evaluates its sin / cos / atan2
 //                  correctly rounded (liw_crmath.hpp)
+//   k_lfe_init_reset / _begin / _select / _commit   the per-robot INITIALIZING state machine on a 256-byte record per robot (current
+//                  state, status, n_frames, counters): the is_static gate and the pose prediction, correctly rounded as in
+//                  _track_begin, with the frame's state and interval rows written into the robot's window (a lane per robot
+//                  decides, then k_lfe_init_rows copies the rows a wavefront per robot); the ascending list of robots whose window is full, by prefix
+//                  counts in one block; take_back_state / init_current_status after the INIT solve.  No atomics, no scratch
+//   k_lfe_slot_copy   scan slot 0 -> a slot per robot, a work-group per robot, 16-byte words (header, lines, entries)
+//   k_lfe_scan_init_sel / k_lfe_pack_init_sel   k_lfe_scan_init / k_lfe_pack_init for a list of robots (one body each)
 //   k_lfe_crmath   liw_crmath.hpp's sin / cos / atan2 element by element (liw_lfe_crmath_eval: a diagnostic entry for the tests)
 //   k_lfe_scan / k_lfe_pack   laser_off exclusive scan (one block), then the component-major laser arrays
 //   k_lfe_scan_init / k_lfe_pack_init   the same for INIT windows: blocks of frames 1 .. n-1, a work-group per window
@@ -1389,15 +1396,17 @@ __global__ void __launch_bounds__(256) k_lfe_pack(int B, int n, int frame, int c
 }
 
 // laser_off of B INIT windows = exclusive scan over the robots of their F = n - 1 clamped counts (frame 0 has no blocks, so the
-// offset of (b, frame 0) is the window's); one block of 1024 as k_lfe_scan
-__global__ void __launch_bounds__(1024) k_lfe_scan_init(int B, int F, int cap, const int* count, int* off) {
+// offset of (b, frame 0) is the window's); one block of 1024 as k_lfe_scan.  With `sel` window r is robot sel[r] (count stays
+// robot-major): liw_lfe_pack_init_sel
+template <bool SEL> __device__ __forceinline__ void scan_init_body(int B, int F, int cap, const int* count, const int* sel, int* off) {
     __shared__ long long part[1024];
     const int t = threadIdx.x;
     const int per = (B + 1023) / 1024;
     const int lo = t * per, hi = lo + per < B ? lo + per : B;
     auto total = [&](int b) {
+        const size_t rb = SEL ? (size_t)sel[b] : (size_t)b;
         long long s = 0;
-        for (int k = 0; k < F; ++k) { const int c = count[(size_t)b * F + k]; s += c < 0 ? 0 : (c > cap ? cap : c); }
+        for (int k = 0; k < F; ++k) { const int c = count[rb * F + k]; s += c < 0 ? 0 : (c > cap ? cap : c); }
         return s;
     };
     long long s = 0;
@@ -1417,17 +1426,27 @@ __global__ void __launch_bounds__(1024) k_lfe_scan_init(int B, int F, int cap, c
     }
     if (t == 1023) off[B] = (int)part[1023];
 }
+__global__ void __launch_bounds__(1024) k_lfe_scan_init(int B, int F, int cap, const int* count, int* off) {
+    scan_init_body<false>(B, F, cap, count, nullptr, off);
+}
+__global__ void __launch_bounds__(1024) k_lfe_scan_init_sel(int R, int F, int cap, const int* count, const int* sel, int* off) {
+    scan_init_body<true>(R, F, cap, count, sel, off);
+}
 
 // one work-group per window: the frames' offsets inside the window in LDS (fo [n + 1], frame 0 empty), then a thread per block of
-// the window, ascending by owning frame; match_pose / has_match rows of all n frames and init_ok
-__global__ void __launch_bounds__(256) k_lfe_pack_init(int B, int n, int cap, int Ltot, const int* off, const int* count, const double* recs,
-                                                      const double* match_pose, const double* pose_front, int* laser_frame, double* laser_pts,
-                                                      double* mp_out, unsigned char* has_match, unsigned char* init_ok) {
+// the window, ascending by owning frame; match_pose / has_match rows of all n frames and init_ok.  With `sel` window b of the output
+// is robot sel[b] of the inputs, and the front pose is read at pose_front + robot * front_stride (liw_lfe_pack_init_sel)
+template <bool SEL> __device__ __forceinline__ void pack_init_body(int B, int n, int cap, int Ltot, const int* off, const int* count, const double* recs,
+                                                                   const double* match_pose, const double* pose_front, long long front_stride,
+                                                                   const int* sel, int* laser_frame, double* laser_pts, double* mp_out,
+                                                                   unsigned char* has_match, unsigned char* init_ok) {
     extern __shared__ __align__(16) unsigned char lds[];
     int* fo = (int*)lds;
     const int b = blockIdx.x, t = threadIdx.x, F = n - 1;
     if (b >= B) return;
-    const int* cnt = count + (size_t)b * F;
+    const size_t rb = SEL ? (size_t)sel[b] : (size_t)b;
+    const int* cnt = count + rb * F;
+    const double* pf = SEL ? pose_front + (long long)rb * front_stride : pose_front + 6 * rb;
     if (t == 0) {
         int run = 0, ok = 1;
         fo[0] = 0;
@@ -1442,7 +1461,7 @@ __global__ void __launch_bounds__(256) k_lfe_pack_init(int B, int n, int cap, in
     }
     for (int e = t; e < n * 12; e += 256) {
         const int f = e / 12, q = e % 12;
-        mp_out[(size_t)b * n * 12 + e] = f == 0 ? pose_front[6 * (size_t)b + q % 6] : match_pose[((size_t)b * F + f - 1) * 12 + q];
+        mp_out[(size_t)b * n * 12 + e] = f == 0 ? pf[q % 6] : match_pose[(rb * F + f - 1) * 12 + q];
     }
     for (int f = t; f < n; f += 256) has_match[(size_t)b * n + f] = 1;
     __syncthreads();
@@ -1452,9 +1471,20 @@ __global__ void __launch_bounds__(256) k_lfe_pack_init(int B, int n, int cap, in
         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (fo[mid] <= j) lo = mid; else hi = mid - 1; }
         const int f = lo, o = o0 + j;
         laser_frame[o] = f;
-        const double* r = recs + (((size_t)b * F + f - 1) * cap + (j - fo[f])) * 12;
+        const double* r = recs + ((rb * F + f - 1) * cap + (j - fo[f])) * 12;
         for (int q = 0; q < 12; ++q) laser_pts[(size_t)q * Ltot + o] = r[q];
     }
+}
+__global__ void __launch_bounds__(256) k_lfe_pack_init(int B, int n, int cap, int Ltot, const int* off, const int* count, const double* recs,
+                                                      const double* match_pose, const double* pose_front, int* laser_frame, double* laser_pts,
+                                                      double* mp_out, unsigned char* has_match, unsigned char* init_ok) {
+    pack_init_body<false>(B, n, cap, Ltot, off, count, recs, match_pose, pose_front, 6, nullptr, laser_frame, laser_pts, mp_out, has_match, init_ok);
+}
+__global__ void __launch_bounds__(256) k_lfe_pack_init_sel(int R, int n, int cap, int Ltot, const int* off, const int* count, const double* recs,
+                                                          const double* match_pose, const double* pose_front, long long front_stride, const int* sel,
+                                                          int* laser_frame, double* laser_pts, double* mp_out, unsigned char* has_match,
+                                                          unsigned char* init_ok) {
+    pack_init_body<true>(R, n, cap, Ltot, off, count, recs, match_pose, pose_front, front_stride, sel, laser_frame, laser_pts, mp_out, has_match, init_ok);
 }
 
 // ------------------------------------------------------------------------------------------------------ tracking glue
@@ -1560,6 +1590,190 @@ __global__ void __launch_bounds__(256) k_lfe_track_end(const void* store, Lay L,
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- initialisation glue
+// lvio_2d::trajectory::add_sensor_data(laser) while status == INITIALIZING (trajectory.cpp: the is_static gate, update_current_status,
+// the frame pushed into the window) and the bookkeeping of check_and_processing_initialize around the INIT solve.
+struct Ini {               // initialisation record of one robot (256 bytes, caller-owned, apart from the store and the tracking record)
+    double p[3], q[3], v[3], bs[6];   // current_p / q / v / bs
+    double ang[3];                    // current_angular_local
+    int status, n_frames;             // LIW_LFE_INITIALIZING / _TRACKING; frames in the window being filled
+    int inits, failed, dropped, pad;  // initialisations, failed windows, dropped frames
+};
+constexpr size_t kIniBytes = 256;
+static_assert(sizeof(Ini) <= kIniBytes, "initialisation record");
+struct IP { double Tiw_R[9], Tiw_t[3], p_thr, q_thr; int N; };
+__host__ __device__ inline Ini* ini_at(void* init, int b) { return (Ini*)((char*)init + (size_t)b * kIniBytes); }
+constexpr int kIvDoubles = 15 + 225 + 225 + 1 + 12 + 9;   // one interval of the liw_batch arrays
+
+// init_current_status: p, q = log_SE3(T_imu_to_wheel^-1), the rest 0, INITIALIZING with an empty window.  The counters are left
+// as they are (a failed window restarts with them; liw_lfe_init_reset zeroes the whole record first)
+__device__ inline void ini_restart(Ini* r, const IP& ip) {
+    const Iso<CR> inv = liw::inverse(liw::cast_iso<CR>(ip.Tiw_R, ip.Tiw_t));
+    const V3<CR> q = liw::log_SO3(inv.R);
+    r->p[0] = inv.t.x.v; r->p[1] = inv.t.y.v; r->p[2] = inv.t.z.v;
+    r->q[0] = q.x.v; r->q[1] = q.y.v; r->q[2] = q.z.v;
+    for (int k = 0; k < 3; ++k) r->v[k] = r->ang[k] = 0.0;
+    for (int k = 0; k < 6; ++k) r->bs[k] = 0.0;
+    r->status = LIW_LFE_INITIALIZING;
+    r->n_frames = 0;
+}
+
+__global__ void __launch_bounds__(256) k_lfe_init_reset(int B, IP ip, void* init, const unsigned char* mask) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || (mask && !mask[b])) return;
+    Ini* r = ini_at(init, b);
+    double* z = (double*)r;
+    for (size_t k = 0; k < kIniBytes / 8; ++k) z[k] = 0.0;
+    ini_restart(r, ip);
+}
+
+// Two launches.  k_lfe_init_begin: a lane per robot decides (gate, prediction, the record, the state row) and leaves in `row` (B
+// ints of the ctx, not caller memory) the interval row the robot's arrays go to, -1 for a robot that copies nothing.
+// k_lfe_init_rows: a wavefront per robot copies the 487 doubles of an accepted robot, 64 consecutive doubles at a time, so the copy
+// runs B waves wide instead of a lane reading and writing 8 bytes at a stride.  No LDS, no atomics.
+__global__ void __launch_bounds__(256) k_lfe_init_begin(int B, DP P, IP ip, void* init, const double* imu_X, const double* imu_Dt, const double* wheel_T,
+                                                       const unsigned char* mask, double* x_init, unsigned char* drop, int* slot_of, int* rows) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int row = -1;   // the interval row this robot's arrays go to (k - 1); -1: nothing to copy
+    if (!(mask && !mask[b])) {
+        Ini* r = ini_at(init, b);
+        const int k = r->n_frames;
+        if (r->status == LIW_LFE_INITIALIZING && k >= 0 && k < ip.N) {
+            typedef V3<CR> VC;
+            const Iso<CR> Tiw = liw::cast_iso<CR>(ip.Tiw_R, ip.Tiw_t), Til = liw::cast_iso<CR>(P.Til_R, P.Til_t);
+            const double* w = wheel_T + 12 * (size_t)b;
+            const Iso<CR> dW = liw::cast_iso<CR>(w, w + 9);
+            // wheel_delta_to(T_imu_to_laser, delta): T_lw * delta * T_lw^-1 with T_lw = T_il^-1 * T_iw; is_static on its log_SE3
+            const Iso<CR> Tlw = liw::mul(liw::inverse(Til), Tiw);
+            const Iso<CR> dL = liw::mul(liw::mul(Tlw, dW), liw::inverse(Tlw));
+            const bool st = liw::norm(dL.t).v < ip.p_thr && liw::norm(liw::log_SO3(dL.R)).v < ip.q_thr;
+            drop[b] = st ? 1 : 0;
+            if (st) {
+                r->dropped += 1;
+            } else {
+                // update_current_status with wheel_delta_to_imu_delta: T_w_i * (T_iw * dT * T_iw^-1)
+                const Iso<CR> N = liw::mul(liw::make_tf(liw::cast_v3<CR>(r->p), liw::cast_v3<CR>(r->q)), liw::mul(liw::mul(Tiw, dW), liw::inverse(Tiw)));
+                const VC q = liw::log_SO3(N.R);
+                r->p[0] = N.t.x.v; r->p[1] = N.t.y.v; r->p[2] = N.t.z.v; r->q[0] = q.x.v; r->q[1] = q.y.v; r->q[2] = q.z.v;
+                double* x = x_init + ((size_t)b * ip.N + k) * 15;
+                for (int i = 0; i < 3; ++i) { x[i] = r->p[i]; x[3 + i] = r->q[i]; x[6 + i] = r->v[i]; }
+                for (int i = 0; i < 6; ++i) x[9 + i] = r->bs[i];
+                const double Dt = imu_Dt[b];
+                for (int i = 0; i < 3; ++i) r->ang[i] = imu_X[15 * (size_t)b + 6 + i] / Dt;   // gamma / Dt
+                slot_of[b] = 1 + k;
+                r->n_frames = k + 1;
+                row = k - 1;   // frame 0's interval is not stored
+            }
+        }
+    }
+    rows[b] = row;
+}
+
+__global__ void __launch_bounds__(kBlock) k_lfe_init_rows(int F, const int* rows, const double* imu_X, const double* imu_J, const double* imu_sqrtP,
+                                                         const double* imu_Dt, const double* wheel_T, const double* wheel_sqrtP, double* w_imu_X,
+                                                         double* w_imu_J, double* w_imu_sqrtP, double* w_imu_Dt, double* w_wheel_T, double* w_wheel_sqrtP) {
+    const size_t src = blockIdx.x;
+    const int r = rows[src];
+    if (r < 0) return;
+    const size_t dst = src * F + r;
+    for (int e = threadIdx.x; e < kIvDoubles; e += kBlock) {
+        if (e < 15) w_imu_X[dst * 15 + e] = imu_X[src * 15 + e];
+        else if (e < 240) w_imu_J[dst * 225 + (e - 15)] = imu_J[src * 225 + (e - 15)];
+        else if (e < 465) w_imu_sqrtP[dst * 225 + (e - 240)] = imu_sqrtP[src * 225 + (e - 240)];
+        else if (e < 466) w_imu_Dt[dst] = imu_Dt[src];
+        else if (e < 478) w_wheel_T[dst * 12 + (e - 466)] = wheel_T[src * 12 + (e - 466)];
+        else w_wheel_sqrtP[dst * 9 + (e - 478)] = wheel_sqrtP[src * 9 + (e - 478)];
+    }
+}
+
+// Scan slot 0 -> slot dst_slot[b] of the same robot: the 32-byte header (status word, n_lines, n_entries, time), lines[0 .. n_lines)
+// and ent[0 .. n_entries).  A work-group of 256 per robot, 16-byte loads and stores: slots start on 256-byte boundaries, a line is
+// five 16-byte words and the entries start on one; an odd entry count ends with one 8-byte copy.  Nothing is computed: the kernel
+// is bounded by the store traffic, at most slot_bytes read and written per robot (about 86 KB at 256 lines / 8 192 entries).
+__global__ void __launch_bounds__(256) k_lfe_slot_copy(void* store, Lay L, const int* dst_slot, const unsigned char* mask) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= L.B || (mask && !mask[b])) return;
+    const int d = dst_slot[b];
+    if (d < 1 || d >= L.slots) {
+        if (t == 0) ((Mgr*)robot_ptr(store, L, b))->status |= LIW_LFE_ST_INVALID;
+        return;
+    }
+    const Slot s = slot_at(store, L, b, 0), o = slot_at(store, L, b, d);
+    const int nl = n_lines(s, L), ne = n_entries(s, L);
+    typedef ulonglong2 W;   // 16 bytes
+    const W* sl = (const W*)s.lines;
+    W* ol = (W*)o.lines;
+    for (int i = t; i < 5 * nl; i += 256) ol[i] = sl[i];
+    const W* se = (const W*)s.ent;
+    W* oe = (W*)o.ent;
+    for (int i = t; i < ne / 2; i += 256) oe[i] = se[i];
+    if ((ne & 1) && t == 0) o.ent[ne - 1] = s.ent[ne - 1];
+    if (t < 2) ((W*)o.h)[t] = ((const W*)s.h)[t];
+}
+
+// ready[b] = INITIALIZING with a full window; sel = the ready robots in ascending order, n_sel[0] = their number.  One block of 1024 as
+// k_lfe_scan: positions are prefix counts, so the list does not depend on the order the lanes run in.
+__global__ void __launch_bounds__(1024) k_lfe_init_select(int B, int N, const void* init, unsigned char* ready, int* sel, int* n_sel) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const int per = (B + 1023) / 1024;
+    const int lo = t * per, hi = lo + per < B ? lo + per : B;
+    auto is_ready = [&](int b) { const Ini* r = ini_at(const_cast<void*>(init), b); return r->status == LIW_LFE_INITIALIZING && r->n_frames == N; };
+    int s = 0;
+    for (int b = lo; b < hi; ++b) s += is_ready(b) ? 1 : 0;
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - s;
+    for (int b = lo; b < hi; ++b) {
+        const bool r = is_ready(b);
+        ready[b] = r ? 1 : 0;
+        if (r) sel[run++] = b;
+    }
+    if (t == 1023) n_sel[0] = part[1023];
+}
+
+// After the INIT solve and the marginalisation, a lane per selected robot b = sel[r].  init_ok[r]: take_back_state (the record's
+// p q v bs := the last solved frame), the solved window back into x_init (what liw_lfe_rebuild reads), both rows of the tracking
+// window := the last solved frame, the tracking record as k_lfe_track_init makes it (the same make_tf, so a robot committed here and
+// one handed to liw_lfe_track_init start from the same bytes) with current_angular_local from the record, TRACKING.  Otherwise
+// init_current_status and the failed-window counter.
+__global__ void __launch_bounds__(256) k_lfe_init_commit(int R, IP ip, void* init, void* track, const int* sel, const unsigned char* init_ok,
+                                                        const double* x_sol, double* x_init, double* x_track) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int b = sel[r], N = ip.N;
+    Ini* rec = ini_at(init, b);
+    if (!init_ok[r]) {
+        ini_restart(rec, ip);
+        rec->failed += 1;
+        return;
+    }
+    const double* xs = x_sol + (size_t)r * N * 15;
+    double* xi = x_init + (size_t)b * N * 15;
+    for (int k = 0; k < N * 15; ++k) xi[k] = xs[k];
+    const double* last = xs + (size_t)(N - 1) * 15;
+    double* xt = x_track + 30 * (size_t)b;
+    for (int k = 0; k < 15; ++k) xt[k] = xt[15 + k] = last[k];
+    for (int k = 0; k < 3; ++k) { rec->p[k] = last[k]; rec->q[k] = last[3 + k]; rec->v[k] = last[6 + k]; }
+    for (int k = 0; k < 6; ++k) rec->bs[k] = last[9 + k];
+    rec->status = LIW_LFE_TRACKING;
+    rec->inits += 1;
+    Trk* t = trk_at(track, b);
+    const Iso<double> T = tf6(last);
+    double* z = (double*)t;
+    for (size_t k = 0; k < kTrkBytes / 8; ++k) z[k] = 0.0;
+    for (int k = 0; k < 9; ++k) t->kf_R[k] = T.R.m[k];
+    t->kf_t[0] = T.t.x; t->kf_t[1] = T.t.y; t->kf_t[2] = T.t.z;
+    for (int k = 0; k < 3; ++k) t->ang[k] = rec->ang[k];
+}
+
 // liw_lfe_crmath_eval: the three functions of liw_crmath.hpp as the CR scalar above calls them, a lane per element (a diagnostic
 // entry: tests/test_gpu_crmath.py compares the device compile of the header with a multi-precision reference).  out may alias a:
 // a lane reads its element before it writes it.
@@ -1582,6 +1796,7 @@ struct liw_lfe_ctx {
     bool have_device = false;
     std::string err;
     float2* d_cs = nullptr;
+    int* d_rows = nullptr;   // B ints between the two launches of liw_lfe_init_begin
     int n_rays = 0;
     float tinc = 0.0f;
     int add_path = -1;   // the kernel of the last add_scan / rebuild: 0 lane, 1 wave (liw_lfe_add_scan_path)
@@ -1707,6 +1922,7 @@ liw_lfe_ctx* liw_lfe_create(const liw_laser_params* prm, const liw_lfe_dims* dim
 void liw_lfe_destroy(liw_lfe_ctx* c) {
     if (!c) return;
     if (c->d_cs) { (void)hipSetDevice(c->device); (void)hipFree(c->d_cs); }
+    if (c->d_rows) { (void)hipSetDevice(c->device); (void)hipFree(c->d_rows); }
     delete c;
 }
 
@@ -1929,6 +2145,121 @@ int liw_lfe_track_get(liw_lfe_ctx* c, const void* track, int robot, double* tf12
     if (stamp) *stamp = t.stamp;
     if (counters) { counters[0] = t.tracked; counters[1] = t.keys; counters[2] = t.skipped; }
     return LIW_OK;
+}
+
+int liw_lfe_init_layout(const liw_lfe_dims* dims, size_t* bytes) {
+    Lay L;
+    if (!bytes || !make_lay(dims, L)) return LIW_EINVAL;
+    *bytes = (size_t)dims->B * kIniBytes;
+    return LIW_OK;
+}
+
+namespace {
+IP init_ip(const liw_lfe_track_params* tp, const liw_lfe_init_params* ip) {
+    const TP t = track_tp(tp);
+    IP p;
+    for (int k = 0; k < 9; ++k) p.Tiw_R[k] = t.Tiw_R[k];
+    for (int k = 0; k < 3; ++k) p.Tiw_t[k] = t.Tiw_t[k];
+    p.N = ip ? ip->slide_window_size : 0;
+    p.p_thr = ip ? ip->p_motion_threshold : 0.0;
+    p.q_thr = ip ? ip->q_motion_threshold : 0.0;
+    return p;
+}
+}  // namespace
+
+int liw_lfe_init_reset(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* init, const unsigned char* mask, void* stream) {
+    LFE_DEV(c);
+    if (!tp || !init) return fail(c, LIW_EINVAL, "liw_lfe_init_reset: bad argument");
+    hipLaunchKernelGGL(k_lfe_init_reset, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, c->L.B, init_ip(tp, nullptr), init, mask);
+    return launched(c);
+}
+
+int liw_lfe_init_get(liw_lfe_ctx* c, const void* init, int robot, int* status, int* n_frames, double* state15, double* angular3, int* counters) {
+    LFE_DEV(c);
+    if (!init || robot < 0 || robot >= c->L.B) return fail(c, LIW_EINVAL, "liw_lfe_init_get: bad argument");
+    Ini r;
+    if (hipMemcpy(&r, (const char*)init + (size_t)robot * kIniBytes, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, LIW_EHIP, "hipMemcpy");
+    if (status) *status = r.status;
+    if (n_frames) *n_frames = r.n_frames;
+    if (state15) {
+        for (int k = 0; k < 3; ++k) { state15[k] = r.p[k]; state15[3 + k] = r.q[k]; state15[6 + k] = r.v[k]; }
+        for (int k = 0; k < 6; ++k) state15[9 + k] = r.bs[k];
+    }
+    if (angular3) for (int k = 0; k < 3; ++k) angular3[k] = r.ang[k];
+    if (counters) { counters[0] = r.inits; counters[1] = r.failed; counters[2] = r.dropped; }
+    return LIW_OK;
+}
+
+int liw_lfe_init_begin(liw_lfe_ctx* c, const liw_lfe_track_params* tp, const liw_lfe_init_params* ip, void* init, const double* imu_X,
+                       const double* imu_J, const double* imu_sqrtP, const double* imu_Dt, const double* wheel_T, const double* wheel_sqrtP,
+                       const unsigned char* mask, double* x_init, double* w_imu_X, double* w_imu_J, double* w_imu_sqrtP, double* w_imu_Dt,
+                       double* w_wheel_T, double* w_wheel_sqrtP, unsigned char* drop, int* slot_of, void* stream) {
+    LFE_DEV(c);
+    if (!tp || !ip || !init || !imu_X || !imu_J || !imu_sqrtP || !imu_Dt || !wheel_T || !wheel_sqrtP || !x_init || !w_imu_X || !w_imu_J ||
+        !w_imu_sqrtP || !w_imu_Dt || !w_wheel_T || !w_wheel_sqrtP || !drop || !slot_of)
+        return fail(c, LIW_EINVAL, "liw_lfe_init_begin: null argument");
+    if (ip->slide_window_size < 2 || ip->slide_window_size > c->L.slots - 1)
+        return fail(c, LIW_EINVAL, "liw_lfe_init_begin: slide_window_size must be 2 .. slots - 1");
+    if (!c->d_rows && hipMalloc(&c->d_rows, sizeof(int) * (size_t)c->L.B) != hipSuccess) { c->d_rows = nullptr; return fail(c, LIW_ENOMEM, "hipMalloc"); }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_lfe_init_begin, dim3(blocks(c->L.B, 256)), dim3(256), 0, s, c->L.B, c->P, init_ip(tp, ip), init, imu_X, imu_Dt, wheel_T, mask, x_init,
+                       drop, slot_of, c->d_rows);
+    if (int r = launched(c)) return r;
+    hipLaunchKernelGGL(k_lfe_init_rows, dim3(c->L.B), dim3(kBlock), 0, s, ip->slide_window_size - 1, c->d_rows, imu_X, imu_J, imu_sqrtP, imu_Dt, wheel_T,
+                       wheel_sqrtP, w_imu_X, w_imu_J, w_imu_sqrtP, w_imu_Dt, w_wheel_T, w_wheel_sqrtP);
+    return launched(c);
+}
+
+int liw_lfe_slot_copy(liw_lfe_ctx* c, void* store, const int* dst_slot, const unsigned char* mask, void* stream) {
+    LFE_DEV(c);
+    if (!store || !dst_slot) return fail(c, LIW_EINVAL, "liw_lfe_slot_copy: null argument");
+    if (((size_t)store & 15) != 0) return fail(c, LIW_EINVAL, "liw_lfe_slot_copy: the store must be 16-byte aligned");
+    hipLaunchKernelGGL(k_lfe_slot_copy, dim3(c->L.B), dim3(256), 0, (hipStream_t)stream, store, c->L, dst_slot, mask);
+    return launched(c);
+}
+
+int liw_lfe_init_select(liw_lfe_ctx* c, const liw_lfe_init_params* ip, const void* init, unsigned char* ready, int* sel, int* n_sel, int* R_host,
+                        void* stream) {
+    LFE_DEV(c);
+    if (!ip || !init || !ready || !sel || !n_sel || ip->slide_window_size < 2) return fail(c, LIW_EINVAL, "liw_lfe_init_select: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_lfe_init_select, dim3(1), dim3(1024), 0, s, c->L.B, ip->slide_window_size, init, ready, sel, n_sel);
+    if (int r = launched(c)) return r;
+    if (R_host && hipMemcpyAsync(R_host, n_sel, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return fail(c, LIW_EHIP, "liw_lfe_init_select: copy of R");
+    return LIW_OK;
+}
+
+int liw_lfe_pack_init_sel(liw_lfe_ctx* c, int R, const int* sel, int n, int cap, const int* count, const double* recs, const double* match_pose,
+                          const double* pose_front, long long front_stride, int L_cap, int* laser_off, int* laser_frame, double* laser_pts,
+                          double* match_pose_out, unsigned char* has_match, unsigned char* init_ok, void* stream) {
+    LFE_DEV(c);
+    if (R < 1 || R > c->L.B || !sel || n < 2 || cap < 1 || L_cap < 0 || front_stride < 6 || !count || !recs || !match_pose || !pose_front || !laser_off ||
+        !laser_frame || !laser_pts || !match_pose_out || !has_match)
+        return fail(c, LIW_EINVAL, "liw_lfe_pack_init_sel: bad argument");
+    if ((long long)c->L.B * (n - 1) * cap >= (1LL << 31)) return fail(c, LIW_EINVAL, "liw_lfe_pack_init_sel: B * (n - 1) * cap must fit in int32");
+    const size_t lds = 4 * ((size_t)n + 1);
+    if (lds > kWaveLdsMax) return fail(c, LIW_EINVAL, "liw_lfe_pack_init_sel: n needs more than 64 KiB of LDS");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_lfe_scan_init_sel, dim3(1), dim3(1024), 0, s, R, n - 1, cap, count, sel, laser_off);
+    if (int r = launched(c)) return r;
+    int Ltot = 0;
+    if (hipMemcpyAsync(&Ltot, laser_off + R, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(c, LIW_EHIP, "liw_lfe_pack_init_sel: read-back of Ltot");
+    if (Ltot > L_cap) return fail(c, LIW_ENOMEM, "liw_lfe_pack_init_sel: Ltot exceeds L_cap");
+    hipLaunchKernelGGL(k_lfe_pack_init_sel, dim3(R), dim3(256), lds, s, R, n, cap, Ltot, laser_off, count, recs, match_pose, pose_front, front_stride, sel,
+                       laser_frame, laser_pts, match_pose_out, has_match, init_ok);
+    if (int r = launched(c)) return r;
+    return Ltot;
+}
+
+int liw_lfe_init_commit(liw_lfe_ctx* c, const liw_lfe_track_params* tp, const liw_lfe_init_params* ip, void* init, void* track, int R, const int* sel,
+                        const unsigned char* init_ok, const double* x_sol, double* x_init, double* x_track, void* stream) {
+    LFE_DEV(c);
+    if (!tp || !ip || !init || !track || R < 1 || R > c->L.B || !sel || !init_ok || !x_sol || !x_init || !x_track || ip->slide_window_size < 2)
+        return fail(c, LIW_EINVAL, "liw_lfe_init_commit: bad argument");
+    hipLaunchKernelGGL(k_lfe_init_commit, dim3(blocks(R, 256)), dim3(256), 0, (hipStream_t)stream, R, init_ip(tp, ip), init, track, sel, init_ok, x_sol, x_init,
+                       x_track);
+    return launched(c);
 }
 
 int liw_lfe_crmath_eval(liw_lfe_ctx* c, int op, int n, const double* a, const double* b, double* out, void* stream) {

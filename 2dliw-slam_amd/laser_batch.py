@@ -18,11 +18,14 @@ LFE_EXPORTS = [
     "liw_lfe_add_scan_flags", "liw_lfe_add_scan_path",
     "liw_lfe_track_layout", "liw_lfe_track_init", "liw_lfe_track_begin", "liw_lfe_track_end", "liw_lfe_track_get",
     "liw_lfe_crmath_eval",
+    "liw_lfe_init_layout", "liw_lfe_init_reset", "liw_lfe_init_get", "liw_lfe_init_begin", "liw_lfe_slot_copy", "liw_lfe_init_select",
+    "liw_lfe_pack_init_sel", "liw_lfe_init_commit",
 ]
 
 ST_POINTS, ST_LINES, ST_CELLS, ST_MATCH, ST_INVALID, ST_CORNERS = 1, 2, 4, 8, 16, 32
 ADD_ADDED, ADD_FIRST, ADD_SPAWNED, ADD_SWAPPED = 1, 2, 4, 8   # LIW_LFE_ADD_*: what an add_scan did for a robot
 REF, SPAWNING, ROBOT = -1, -2, -3
+INITIALIZING, TRACKING = 0, 1   # LIW_LFE_INITIALIZING / LIW_LFE_TRACKING: the status of an initialisation record
 NONE = -61   # LIW_LFE_NONE: a getter's "no such sub-map / outside the grid" (the Python getters turn it into -1 / None)
 
 
@@ -51,6 +54,24 @@ def track_params_struct(tp):
     s.normalize_extrinsics = int(bool(tp["normalize_extrinsics"]))
     for k in ("min_delta_t", "key_frame_p_motion_threshold", "key_frame_q_motion_threshold"):
         setattr(s, k, float(tp[k]))
+    return s
+
+
+class InitParamsC(C.Structure):
+    _fields_ = [("slide_window_size", C.c_int), ("p_motion_threshold", C.c_double), ("q_motion_threshold", C.c_double)]
+
+
+def office_init_params():
+    """liw_lfe_init_params with the trajectory values of reference config/office.yaml"""
+    return dict(slide_window_size=10, p_motion_threshold=0.1, q_motion_threshold=0.1)
+
+
+def init_params_struct(ip):
+    if isinstance(ip, InitParamsC):
+        return ip
+    s = InitParamsC()
+    s.slide_window_size = int(ip["slide_window_size"])
+    s.p_motion_threshold, s.q_motion_threshold = float(ip["p_motion_threshold"]), float(ip["q_motion_threshold"])
     return s
 
 
@@ -97,6 +118,15 @@ def _lib():
         L.liw_lfe_track_end.argtypes = [vp, tpp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_track_get.argtypes = [vp, vp, C.c_int, dp, dp, dp, ip]
         L.liw_lfe_crmath_eval.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        ipp = C.POINTER(InitParamsC)
+        L.liw_lfe_init_layout.argtypes = [C.POINTER(DimsC), C.POINTER(C.c_size_t)]
+        L.liw_lfe_init_reset.argtypes = [vp, tpp, vp, vp, vp]
+        L.liw_lfe_init_get.argtypes = [vp, vp, C.c_int, ip, ip, dp, dp, ip]
+        L.liw_lfe_init_begin.argtypes = [vp, tpp, ipp] + [vp] * 18
+        L.liw_lfe_slot_copy.argtypes = [vp, vp, vp, vp, vp]
+        L.liw_lfe_init_select.argtypes = [vp, ipp, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_pack_init_sel.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, ll, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.liw_lfe_init_commit.argtypes = [vp, tpp, ipp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.liw_lfe_status.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_num_lines.argtypes = [vp, vp, C.c_int, C.c_int]
         L.liw_lfe_get_lines.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int]
@@ -124,6 +154,19 @@ def track_bytes(dims):
     if r < 0:
         raise LiwError(r, "liw_lfe_track_layout")
     return int(n.value)
+
+
+def init_bytes(dims):
+    """bytes of the initialisation record for dims, 256 per robot (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
+    from . import LiwError
+    n = C.c_size_t(0)
+    r = _lib().liw_lfe_init_layout(C.byref(dims_struct(dims)), C.byref(n))
+    if r < 0:
+        raise LiwError(r, "liw_lfe_init_layout")
+    return int(n.value)
+
+
+WINDOW_KEYS = (("imu_X", 15), ("imu_J", 225), ("imu_sqrtP", 225), ("imu_Dt", 1), ("wheel_T", 12), ("wheel_sqrtP", 9))
 
 
 def pad_points(point_lists, max_points):
@@ -496,6 +539,132 @@ class BatchFrontEnd:
         self._chk_get(self.L.liw_lfe_track_get(self.h, self._p(self._track(track)), int(robot), tf.ctypes.data_as(dp), a.ctypes.data_as(dp), C.byref(st),
                                                cn.ctypes.data_as(C.POINTER(C.c_int))))
         return dict(last_keyframe_tf=tf, angular_local=a, stamp=float(st.value), tracked=int(cn[0]), keys=int(cn[1]), skipped=int(cn[2]))
+
+    # ------------------------------------------------------------------------------------------- initialisation glue
+    def init_layout(self):
+        """bytes of the initialisation record of this front-end's dims (host-only)"""
+        return init_bytes(self.dims)
+
+    def _init(self, init):
+        torch = self.torch
+        assert torch.is_tensor(init) and init.dtype == torch.uint8 and init.is_contiguous() and init.device == self.dev
+        assert init.numel() >= self.init_layout()
+        return init
+
+    def init_reset(self, tp, init, mask=None):
+        """init_current_status for the masked robots (all when None) of the initialisation record `init` (a uint8 device tensor of
+        init_layout() bytes): p, q = log_SE3(T_imu_to_wheel^-1), the rest 0, INITIALIZING, an empty window, counters 0"""
+        tps = track_params_struct(tp)
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_init_reset(self.h, C.byref(tps), self._p(self._init(init)), self._p(m), self._s()))
+        return init
+
+    def init_get(self, init, robot):
+        """-> dict(status, n_frames, state [15] = p q v bs, angular_local [3], inits, failed, dropped) of one robot (synchronous)"""
+        st, nf, x, a, cn = C.c_int(0), C.c_int(0), np.zeros(15), np.zeros(3), np.zeros(3, dtype=np.int32)
+        dp = C.POINTER(C.c_double)
+        self._chk_get(self.L.liw_lfe_init_get(self.h, self._p(self._init(init)), int(robot), C.byref(st), C.byref(nf), x.ctypes.data_as(dp),
+                                              a.ctypes.data_as(dp), cn.ctypes.data_as(C.POINTER(C.c_int))))
+        return dict(status=int(st.value), n_frames=int(nf.value), state=x, angular_local=a, inits=int(cn[0]), failed=int(cn[1]), dropped=int(cn[2]))
+
+    def init_window(self, N):
+        """zeroed window arrays of B N-frame INIT windows: dict(x_init [B, N, 15] and the six interval arrays [B, N - 1, w])"""
+        z = lambda *s: self.torch.zeros(*s, dtype=self.torch.float64, device=self.dev)
+        return dict(x_init=z(self.B, N, 15), **{k: z(self.B, N - 1, w) for k, w in WINDOW_KEYS})
+
+    def init_begin(self, tp, ip, init, interval, window, mask=None, out=None):
+        """before the scan is processed, for the INITIALIZING robots of the mask (all when None): the is_static gate on the wheel
+        increment, the pose prediction, the frame's state into row n_frames of window["x_init"] and its interval (dict of the six
+        liw_batch arrays, [B, w]) into row n_frames - 1 of the window arrays (init_window), updated in place.
+        -> dict(drop [B] uint8, slot_of [B] int32); `out` may supply them.  Rows of robots that are not INITIALIZING are not written."""
+        torch = self.torch
+        tps, ips = track_params_struct(tp), init_params_struct(ip)
+        N = ips.slide_window_size
+        iv = [self._t(interval[k], torch.float64, (self.B, w)) for k, w in WINDOW_KEYS]
+        self._out(window["x_init"], torch.float64, self.B * N * 15)
+        wv = [self._out(window[k], torch.float64, self.B * (N - 1) * w) for k, w in WINDOW_KEYS]
+        o = dict(out or {})
+        if "drop" not in o:
+            o["drop"] = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+        if "slot_of" not in o:
+            o["slot_of"] = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        self._out(o["drop"], torch.uint8, self.B)
+        self._out(o["slot_of"], torch.int32, self.B)
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_init_begin(self.h, C.byref(tps), C.byref(ips), self._p(self._init(init)), *[self._p(t) for t in iv], self._p(m),
+                                            self._p(window["x_init"]), *[self._p(t) for t in wv], self._p(o["drop"]), self._p(o["slot_of"]), self._s()))
+        return o
+
+    def slot_copy(self, dst_slot, mask=None):
+        """scan slot 0 of the masked robots (all when None) -> slot dst_slot[b] [B] int32 of the same robot: header, status word,
+        lines and line_map entries.  A dst_slot outside 1 .. slots-1 sets ST_INVALID in the robot word and copies nothing."""
+        d = self._t(dst_slot, self.torch.int32, (self.B,))
+        m = self._mask(mask)
+        self._chk(self.L.liw_lfe_slot_copy(self.h, self._p(self.store), self._p(d), self._p(m), self._s()))
+
+    def init_select(self, ip, init, out=None, R_host=None):
+        """-> dict(ready [B] uint8, sel [B] int32 with the ready robots ascending in sel[:R], n_sel [1] int32 = R), all on the device
+        and without a synchronisation; `out` may supply them.  R_host: a pinned int32 host tensor of one element that R is also
+        copied into asynchronously (valid after the stream's next synchronisation)."""
+        torch = self.torch
+        ips = init_params_struct(ip)
+        o = dict(out or {})
+        for k, n, dt in (("ready", self.B, torch.uint8), ("sel", self.B, torch.int32), ("n_sel", 1, torch.int32)):
+            if k not in o:
+                o[k] = torch.zeros(n, dtype=dt, device=self.dev)
+            self._out(o[k], dt, n)
+        rh = None
+        if R_host is not None:
+            assert torch.is_tensor(R_host) and R_host.dtype == torch.int32 and R_host.device.type == "cpu" and R_host.numel() >= 1
+            rh = C.c_void_p(R_host.data_ptr())
+        self._chk(self.L.liw_lfe_init_select(self.h, C.byref(ips), self._p(self._init(init)), self._p(o["ready"]), self._p(o["sel"]), self._p(o["n_sel"]),
+                                             rh, self._s()))
+        return o
+
+    def pack_init_sel(self, R, sel, m, n, pose_front, out=None, L_cap=None, bufs=None):
+        """pack_init for the R robots sel[:R] (int32 device tensor) of a match_front() result over all B robots: window r of the
+        output is robot sel[r].  pose_front: [B, 6], or a float64 device view [B, k >= 6] with last stride 1 (x_init[:, 0] is one).
+        out / bufs as pack_init, sized for R windows.  -> (dict for BatchSolver.rebind, Ltot, init_ok [R] uint8)."""
+        torch = self.torch
+        R, n, cap = int(R), int(n), int(m["cap"])
+        assert int(m["F"]) == n - 1, "pack_init_sel needs a match_front result with F = n - 1"
+        L_cap = R * (n - 1) * cap if L_cap is None else int(L_cap)
+        sel = self._out(sel, torch.int32, R)
+        pf = pose_front
+        if not (torch.is_tensor(pf) and pf.dim() == 2 and pf.dtype == torch.float64 and pf.device == self.dev and pf.shape[0] == self.B
+                and pf.shape[1] >= 6 and pf.stride(1) == 1 and pf.stride(0) >= 6):
+            pf = self._t(pf, torch.float64, (self.B, 6))
+        out = dict(out or {})
+        for k, size, dt in (("match_pose", R * n * 12, torch.float64), ("has_match", R * n, torch.uint8), ("init_ok", R, torch.uint8)):
+            if k not in out:
+                out[k] = torch.zeros(max(size, 1), dtype=dt, device=self.dev)
+            assert out[k].dtype == dt and out[k].is_contiguous() and out[k].numel() >= size, k
+        if bufs is None:
+            bufs = dict(laser_off=torch.empty(R + 1, dtype=torch.int32, device=self.dev),
+                        laser_frame=torch.empty(max(L_cap, 1), dtype=torch.int32, device=self.dev),
+                        laser_pts=torch.empty(12 * max(L_cap, 1), dtype=torch.float64, device=self.dev))
+        off, lf, lp = bufs["laser_off"], bufs["laser_frame"], bufs["laser_pts"]
+        assert off.numel() >= R + 1 and lf.numel() >= max(L_cap, 1) and lp.numel() >= 12 * max(L_cap, 1)
+        Ltot = self._chk(self.L.liw_lfe_pack_init_sel(self.h, R, self._p(sel), n, cap, self._p(m["count"]), self._p(m["recs"]), self._p(m["match_pose"]),
+                                                      self._p(pf), int(pf.stride(0)), L_cap, self._p(off), self._p(lf), self._p(lp),
+                                                      self._p(out["match_pose"]), self._p(out["has_match"]), self._p(out["init_ok"]), self._s()))
+        res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
+        return res, Ltot, out["init_ok"]
+
+    def init_commit(self, tp, ip, init, track, R, sel, init_ok, x_sol, x_init, x_track):
+        """after the INIT solve of the compact batch (window r = robot sel[r]): for the robots with init_ok[r] the solved window
+        x_sol[r] [N, 15] goes back into x_init [B, N, 15], both rows of x_track [B, 2, 15] and the records become the last solved
+        frame, status TRACKING; the others restart (init_current_status, failed-window counter).  All tensors are updated in place."""
+        torch = self.torch
+        tps, ips = track_params_struct(tp), init_params_struct(ip)
+        R, N = int(R), ips.slide_window_size
+        self._out(sel, torch.int32, R)
+        self._out(init_ok, torch.uint8, R)
+        self._out(x_sol, torch.float64, R * N * 15)
+        self._out(x_init, torch.float64, self.B * N * 15)
+        self._out(x_track, torch.float64, self.B * 30)
+        self._chk(self.L.liw_lfe_init_commit(self.h, C.byref(tps), C.byref(ips), self._p(self._init(init)), self._p(self._track(track)), R, self._p(sel),
+                                             self._p(init_ok), self._p(x_sol), self._p(x_init), self._p(x_track), self._s()))
 
     # ----------------------------------------------------------------------------------------------------- diagnostics
     CR_SIN, CR_COS, CR_ATAN2 = 0, 1, 2

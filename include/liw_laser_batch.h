@@ -171,7 +171,8 @@ int liw_lfe_pack_track(liw_lfe_ctx* ctx, int n, int frame, int cap, const int* c
                        int L_cap, int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match,
                        void* stream);
 
-/* Initialisation (lvio_2d::trajectory while status == INITIALIZING).  The caller keeps the window's scans in scan slots; the
+/* Initialisation (lvio_2d::trajectory while status == INITIALIZING).  The window's scans are kept in scan slots (by the caller, or per
+ * robot by liw_lfe_init_begin + liw_lfe_slot_copy below); the
  * reference's per-frame add_scan calls while INITIALIZING only feed the key-frame deque (here: the caller's slots) and sub-maps
  * that clear_all_scan discards before anything reads them, so the device path does not make them: a window is
  * spawn (per frame) -> liw_lfe_match_front -> liw_lfe_pack_init -> the INIT solve -> liw_lfe_rebuild at the solved poses.
@@ -217,7 +218,8 @@ int liw_lfe_rebuild(liw_lfe_ctx* ctx, void* store, int first_slot, int F, const 
 /* Tracking glue (lvio_2d::trajectory::add_sensor_data(laser) while status == TRACKING, around the stages above): the de-skew twist
  * from the current state, the min_delta_t gate, update_current_status (the new frame's pose from the wheel increment), the roll of
  * the two-frame window (pop_frame_for_tracking with keep_window_size = 1) and the key-frame decision against last_keyframe_tf.
- * The key-frame deque and the INITIALIZING state machine stay with the caller.
+ * The INITIALIZING state machine is the initialisation glue below; the key-frame deque and the sensor-inited latch (imu_inited /
+ * wheel_odom_inited: the caller starts stepping once it has intervals) stay with the caller.
  *
  * The tracking record is caller-owned device memory apart from the store (whose layout does not change), robot-major, 256 bytes per
  * robot: last_keyframe_tf [12] (R row-major, then t), current_angular_local [3], the stamp of the last accepted frame, and the
@@ -277,6 +279,94 @@ int liw_lfe_track_end(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, void* tr
 /* the record of one robot (synchronous; tests and tools): tf12 = last_keyframe_tf, angular3, stamp, counters [3] = tracked, key,
  * skipped frames.  Any output may be NULL.  LIW_EINVAL: a null track, robot outside 0 .. B-1. */
 int liw_lfe_track_get(liw_lfe_ctx* ctx, const void* track, int robot, double* tf12, double* angular3, double* stamp, int* counters);
+
+/* Initialisation glue (lvio_2d::trajectory::add_sensor_data(laser) while status == INITIALIZING, per robot): the is_static gate on
+ * the wheel increment, update_current_status, the frame and its interval pushed into the robot's window, and the bookkeeping of
+ * check_and_processing_initialize around the INIT solve, so that robots whose windows fill at different frames share the uniform
+ * liw_lfe_match_front / liw_lfe_rebuild calls.  Conventions as the tracking glue: no FMA contraction, of a masked-out robot no byte
+ * is written, a failing call writes nothing, LIW_ENODEV without a device, the layout query is host-only.
+ *
+ * The initialisation record is caller-owned device memory apart from the store and from the tracking record, robot-major, 256 bytes
+ * per robot: current_p / q / v [3 each], current_bs [6], current_angular_local [3], then the ints status (LIW_LFE_INITIALIZING /
+ * LIW_LFE_TRACKING), n_frames (frames in the window being filled) and the counters initialisations, failed windows, dropped
+ * frames; the rest is padding.  The extrinsic T_imu_to_wheel is taken from liw_lfe_track_params, which does not change. */
+#define LIW_LFE_INITIALIZING 0
+#define LIW_LFE_TRACKING 1
+
+typedef struct liw_lfe_init_params {
+    int slide_window_size;       /* N: frames of an INIT window */
+    double p_motion_threshold;   /* is_static: a frame that moved less than both thresholds since the last one is dropped */
+    double q_motion_threshold;
+} liw_lfe_init_params;
+
+/* bytes of the initialisation record for `dims` (256 per robot); LIW_EINVAL for a non-positive dimension.  Host-only. */
+int liw_lfe_init_layout(const liw_lfe_dims* dims, size_t* bytes);
+
+/* init_current_status for the robots with mask[b] != 0 (all when NULL): p, q = log_SE3(T_imu_to_wheel^-1), v, bs and
+ * current_angular_local 0, INITIALIZING, n_frames 0, all counters 0; the padding is zeroed.  LIW_EINVAL: a null tp / init. */
+int liw_lfe_init_reset(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, void* init, const unsigned char* mask, void* stream);
+
+/* the record of one robot (synchronous; tests and tools): status, n_frames, state15 = p q v bs, angular3, counters [3] =
+ * initialisations, failed windows, dropped frames.  Any output may be NULL.  LIW_EINVAL: a null init, robot outside 0 .. B-1. */
+int liw_lfe_init_get(liw_lfe_ctx* ctx, const void* init, int robot, int* status, int* n_frames, double* state15, double* angular3, int* counters);
+
+/* Before the scan is processed, for the robots with mask[b] != 0 (all when NULL) whose status is INITIALIZING and whose window is not
+ * full (n_frames < N; a full window is committed before the next frame); of every other robot no byte is written.  imu_X [B][15],
+ * imu_J [B][225], imu_sqrtP [B][225], imu_Dt [B], wheel_T [B][12], wheel_sqrtP [B][9] are the interval's liw_batch arrays.  In the
+ * reference's order:
+ *   1. laser_delta = T_lw * wheel_T[b] * T_lw^-1 with T_lw = T_imu_to_laser^-1 * T_imu_to_wheel (wheel_delta_to);
+ *   2. drop [B] byte b = |laser_delta.t| < p_motion_threshold && |log_SO3(laser_delta.R)| < q_motion_threshold (both strict).  A
+ *      dropped robot gets drop and its dropped counter advances; nothing else of it is written (the caller merges the interval into
+ *      the next one, as for a skipped tracking frame);
+ *   3. otherwise, with k = n_frames: p, q := log_SE3(make_tf(p, q) * T_iw * wheel_T[b] * T_iw^-1) (update_current_status); row k of
+ *      x_init [B][N][15] := p q v bs; for k >= 1 the six interval arrays are copied into row k - 1 of the window arrays
+ *      w_imu_X [B][N-1][15], w_imu_J [B][N-1][225], w_imu_sqrtP [B][N-1][225], w_imu_Dt [B][N-1], w_wheel_T [B][N-1][12],
+ *      w_wheel_sqrtP [B][N-1][9] (the liw_batch layout of B N-frame windows; frame 0's interval is not stored);
+ *      current_angular_local := imu_X[b][6 .. 8] / imu_Dt[b]; slot_of [B] int b = 1 + k, the scan slot the frame's scan belongs in
+ *      (liw_lfe_slot_copy); n_frames := k + 1.
+ * sin / cos / atan2 are evaluated correctly rounded, as in liw_lfe_track_begin: the predicted poses are where liw_lfe_match_front and
+ * the INIT solve start.  Mapping: a lane per robot for the decision, then a second launch with a wavefront per robot for the rows; the
+ * B row indices between the two launches live in the ctx, so calls on one ctx must not overlap on different streams.
+ * LIW_EINVAL: a null tp / ip or a null array other than mask, slide_window_size outside 2 .. slots - 1. */
+int liw_lfe_init_begin(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, const liw_lfe_init_params* ip, void* init, const double* imu_X,
+                       const double* imu_J, const double* imu_sqrtP, const double* imu_Dt, const double* wheel_T, const double* wheel_sqrtP,
+                       const unsigned char* mask, double* x_init, double* w_imu_X, double* w_imu_J, double* w_imu_sqrtP, double* w_imu_Dt,
+                       double* w_wheel_T, double* w_wheel_sqrtP, unsigned char* drop, int* slot_of, void* stream);
+
+/* Scan slot 0 of the robots with mask[b] != 0 (all when NULL) copied into slot dst_slot[b] of the same robot, in one launch: the
+ * header with the slot's status word, lines[0 .. n_lines) and ent[0 .. n_entries), so an invalid slot stays invalid.  A dst_slot
+ * outside 1 .. slots-1 sets LIW_LFE_ST_INVALID in the robot word and writes nothing else of that robot.  A work-group per robot with
+ * 16-byte accesses: a pure copy, bounded by the store traffic of at most one slot read and written per robot.
+ * LIW_EINVAL: a null store / dst_slot, a store that is not 16-byte aligned. */
+int liw_lfe_slot_copy(liw_lfe_ctx* ctx, void* store, const int* dst_slot, const unsigned char* mask, void* stream);
+
+/* ready [B] byte b = status == INITIALIZING && n_frames == slide_window_size; sel [B]: the ready robots in ascending order in
+ * sel[0 .. R), entries past R untouched; n_sel [1] (device) = R.  Positions are prefix counts (no atomics): deterministic.  One
+ * launch and no synchronisation: when R_host is not NULL, R is also copied there asynchronously on `stream` and is valid after the
+ * stream's next synchronisation (the read-back of liw_lfe_pack_track's Ltot is one).
+ * LIW_EINVAL: a null ip / init / ready / sel / n_sel, slide_window_size < 2. */
+int liw_lfe_init_select(liw_lfe_ctx* ctx, const liw_lfe_init_params* ip, const void* init, unsigned char* ready, int* sel, int* n_sel, int* R_host,
+                        void* stream);
+
+/* liw_lfe_pack_init for the R robots of sel only: window r of the output is robot sel[r].  count, recs and match_pose are the
+ * robot-major arrays liw_lfe_match_front wrote for all B robots; the front pose of robot b is read at pose_front + b * front_stride
+ * (doubles; x_init itself has stride 15 N).  The outputs laser_off [R+1], laser_frame, laser_pts, match_pose_out [R][n][12],
+ * has_match [R][n], init_ok [R] (may be NULL) are the bytes liw_lfe_pack_init writes for a fleet that consists of exactly those
+ * robots.  Returns Ltot (one read-back); Ltot > L_cap is LIW_ENOMEM with nothing but laser_off written.
+ * LIW_EINVAL: R outside 1 .. B, n < 2, cap < 1, L_cap < 0, front_stride < 6, a null array other than init_ok. */
+int liw_lfe_pack_init_sel(liw_lfe_ctx* ctx, int R, const int* sel, int n, int cap, const int* count, const double* recs, const double* match_pose,
+                          const double* pose_front, long long front_stride, int L_cap, int* laser_off, int* laser_frame, double* laser_pts,
+                          double* match_pose_out, unsigned char* has_match, unsigned char* init_ok, void* stream);
+
+/* After the INIT solve and the marginalisation of the compact batch whose window r is robot sel[r] (x_sol [>= R][N][15], init_ok [R]).
+ * For r = 0 .. R-1 with init_ok[r]: row block sel[r] of x_init [B][N][15] := x_sol[r] (what liw_lfe_rebuild reads through strides);
+ * both rows of x_track [B][2][15] := the last solved frame; the record's p q v bs := that frame (take_back_state); the robot's
+ * tracking record as liw_lfe_track_init makes it from that frame, with current_angular_local from the initialisation record;
+ * status := TRACKING and the initialisation counter advances.  Without init_ok[r]: init_current_status (as liw_lfe_init_reset, the
+ * counters kept) and the failed-window counter advances; the caller gives the robot to liw_lfe_store_reset.  The priors of the
+ * compact batch are plain row scatters and stay with the caller.  LIW_EINVAL: R outside 1 .. B, slide_window_size < 2, a null argument. */
+int liw_lfe_init_commit(liw_lfe_ctx* ctx, const liw_lfe_track_params* tp, const liw_lfe_init_params* ip, void* init, void* track, int R, const int* sel,
+                        const unsigned char* init_ok, const double* x_sol, double* x_init, double* x_track, void* stream);
 
 /* A diagnostic entry, on no tracking path: the sin (op 0), cos (op 1) or atan2(a, b) (op 2) that liw_lfe_track_begin evaluates
  * (csrc/liw_crmath.hpp, as compiled for the device), element by element: out[i] = f(a[i]) or f(a[i], b[i]) for i = 0 .. n-1.  a, b,

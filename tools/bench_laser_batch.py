@@ -24,7 +24,19 @@ baseline without them, the same stages with the glue done on the host from read-
 HostGlueTracker: a loop over the robots through liw_lie_*), frame_ms over --track-host-frames frames of one run, and whether the
 two sides' key / skip decisions agree on those frames.
 
+--cold-start N adds the cold start of a fleet (key "cold_start", per B of --cold-B): fleet.FleetTrajectory from reset(), windows of N
+frames, robot b starting to move b % 4 frames late (until then it is dropped by the motion gate).  cold: the N + 3 frames until the
+last robot tracks, frame_ms per frame (median over --reps runs after one warm-up, host clock around step + synchronise), their sum
+first_scan_to_tracking_ms with min / max over the runs, and per frame with an INIT solve the ready robots R and the bucket.
+all_tracking: the --cold-frames frames after that through FleetTrajectory.step and, from a copy of the same state and on the same
+inputs, through FleetTracker.step (median / min / max over --reps of the per-run median frame).  mixed: the same frames after a
+quarter of the robots was put back to INITIALIZING and kept at rest: frame_ms, and the LM iterations of the tracking solve per
+group of rows (robots that track / robots that do not).  host_glue: the baseline with every piece of glue on the host from
+read-backs (tests/fleet_init_reference.py HostGlueTrajectory: a Python loop over the robots), the same N + 3 frames from reset in one
+run (--cold-host-frames fewer), per frame and in total, beside the device's total over the same frames; at the first B only.
+
   python tools/bench_laser_batch.py [--B 4096,49152] [--reps 5] [--init 30 [--init-B 4096]] [--track 8 [--track-B 4096,49152]]
+                                    [--cold-start 4 [--cold-B 4096,49152] [--cold-frames 4] [--cold-host-frames -1]]
 """
 import argparse
 import importlib
@@ -328,6 +340,133 @@ def track_run(liw, torch, prm, lp, tp, B, K, sc, reps, host_frames):
     return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
 
 
+def cold_run(liw, torch, prm, lp, tp, ip, B, K, sc, reps, host_frames):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fleet_init_reference as ref
+    N = int(ip["slide_window_size"])
+    Tc = N + 3                                   # the last robot (three frames late) tracks after this many frames
+    nd = sc["truth"].shape[0]
+    assert sc["truth"].shape[1] - 1 >= Tc + K
+    robd = torch.from_numpy(np.arange(B) % nd).cuda()
+    lag = torch.arange(B, device="cuda") % 4
+    dims = dict(B=B, slots=N + 1, max_points=N_RAYS, max_lines=256, max_cell_entries=8192)
+    Rd, Td = torch.from_numpy(sc["ranges"]).cuda(), torch.from_numpy(sc["times"]).cuda()
+    ivd = {k: torch.from_numpy(v).cuda() for k, v in sc["iv"].items()}
+    eye = torch.tensor([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device="cuda")
+
+    def frame(t, rest=None):
+        """the inputs of frame t: robot b is at trajectory frame t - lag[b]; before its first frame, and where rest[b], it stands still"""
+        kf = (t - lag).clamp(0, Tc + K)
+        if rest is not None:
+            kf = torch.where(rest, torch.zeros_like(kf), kf)
+        mv, kc = kf >= 1, kf.clamp(min=1)
+        iv = {}
+        for k, v in ivd.items():
+            a = v[robd, kc - 1]
+            iv[k] = (torch.where(mv[:, None], a, eye[None, :]) if k == "wheel_T" else a).contiguous()
+        return Rd[robd, kc].contiguous(), Td[robd, kc].contiguous(), iv
+
+    def clock(tr, args):
+        torch.cuda.synchronize()
+        t_a = time.perf_counter()
+        o = tr.step(*args)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t_a) * 1e3, o
+
+    stat = lambda v: dict(ms=round(float(np.median(v)), 4), min_ms=round(float(min(v)), 4), max_ms=round(float(max(v)), 4))
+    out = dict(N=N, K=K, distinct=nd)
+    ft = liw.FleetTrajectory(prm, lp, tp, ip, dims)
+    ft.fe.set_geometry(N_RAYS, ANG_MIN, ANG_INC, T_INC)
+    cold_frames = [frame(t) for t in range(1, Tc + 1)]
+    runs, inits = [], []
+    for rep in range(reps + 1):                  # the first run is the warm-up: it also makes the INIT solvers
+        ft.reset()
+        ts, inits = [], []
+        for t, args in enumerate(cold_frames, 1):
+            ms, o = clock(ft, args)
+            ts.append(ms)
+            if bool(o["ready"].any()):
+                inits.append(dict(frame=t, bucket=ft.last_init[0], R=ft.last_init[1], blocks=ft.last_init[2], committed=int(o["init_ok"].sum())))
+        if rep:
+            runs.append(ts)
+    per = np.median(np.array(runs), axis=0)
+    for d in inits:
+        d["frame_ms"] = round(float(per[d["frame"] - 1]), 4)
+    out["cold"] = dict(frames=Tc, frame_ms=[round(float(v), 4) for v in per], inits=inits, tracking_after=int((ft.status() == 1).sum()),
+                       first_scan_to_tracking=stat([sum(r) for r in runs]))
+    # ---- every robot tracks: the same frames through FleetTrajectory.step and FleetTracker.step, from the same state
+    state = [ft.fe.store, ft.init, ft.track, ft.x, ft.match_pose, ft.has_match, ft.acc, ft.n_acc, ft.key, ft.pose, ft.flags] + [ft.bs.t[k] for k in liw.fleet.PRIOR_KEYS]
+    snap = [t.clone() for t in state]
+    track_frames = [frame(t) for t in range(Tc + 1, Tc + K + 1)]
+
+    def restore():
+        for t, s_ in zip(state, snap):
+            t.copy_(s_)
+
+    def frames_ms(tr, frames, prepare):
+        meds = []
+        for rep in range(reps + 1):
+            prepare()
+            ts = [clock(tr, args)[0] for args in frames]
+            if rep:
+                meds.append(float(np.median(ts)))
+        return meds
+
+    all_t = dict(trajectory=stat(frames_ms(ft, track_frames, restore)))
+    tk = liw.FleetTracker(prm, lp, tp, dims)
+    tk.fe.set_geometry(N_RAYS, ANG_MIN, ANG_INC, T_INC)
+    pairs = [(tk.fe.store, 0), (tk.track, 2), (tk.x, 3), (tk.match_pose, 4), (tk.has_match, 5), (tk.acc, 6), (tk.n_acc, 7), (tk.key, 8), (tk.pose, 9), (tk.flags, 10)]
+    pairs += [(tk.bs.t[k], 11 + i) for i, k in enumerate(liw.fleet.PRIOR_KEYS)]
+
+    def restore_tk():
+        for t, i in pairs:
+            t.copy_(snap[i])
+
+    all_t["tracker"] = stat(frames_ms(tk, track_frames, restore_tk))
+    all_t["trajectory_over_tracker"] = round(all_t["trajectory"]["ms"] / all_t["tracker"]["ms"], 4)
+    out["all_tracking"] = all_t
+    tk.close()
+    del tk
+    torch.cuda.empty_cache()
+    # ---- a quarter of the fleet INITIALIZING and at rest
+    quarter = (torch.arange(B, device="cuda") % 4) == 1
+    qm = quarter.to(torch.uint8)
+    mixed_frames = [frame(t, rest=quarter) for t in range(Tc + 1, Tc + K + 1)]
+    its = []
+
+    def to_mixed():
+        restore()
+        ft.fe.reset(mask=qm)
+        ft.fe.init_reset(ft.tp, ft.init, mask=qm)
+
+    out["mixed"] = dict(initializing=int(quarter.sum()), **stat(frames_ms(ft, mixed_frames, to_mixed)))
+    to_mixed()
+    qh = quarter.cpu().numpy()
+    for args in mixed_frames:
+        ft.step(*args)
+        it = np.array([s_["iterations"] for s_ in ft.bs.summaries()])
+        its.append(dict(tracking_max=int(it[~qh].max()), tracking_mean=round(float(it[~qh].mean()), 3), other_max=int(it[qh].max()),
+                        other_mean=round(float(it[qh].mean()), 3)))
+    out["mixed"]["iterations"] = its
+    out["mixed"]["over_all_tracking"] = round(out["mixed"]["ms"] / all_t["trajectory"]["ms"], 4)
+    ft.close()
+    del ft, snap, state
+    torch.cuda.empty_cache()
+    if host_frames:
+        host_frames = Tc if host_frames < 0 else min(host_frames, Tc)
+        ht = ref.HostGlueTrajectory(liw, prm, lp, tp, ip, dims)
+        ht.fe.set_geometry(N_RAYS, ANG_MIN, ANG_INC, T_INC)
+        ts = [clock(ht, args)[0] for args in cold_frames[:host_frames]]
+        dev_ms = float(sum(per[:len(ts)]))
+        out["host_glue"] = dict(frames=len(ts), label="Python loop over the robots, one run", frame_ms=[round(float(v), 4) for v in ts],
+                                total_ms=round(float(sum(ts)), 4), device_total_ms=round(dev_ms, 4), tracking_after=int((ht.status == 1).sum()))
+        out["host_glue_over_device"] = round(float(sum(ts)) / dev_ms, 2)
+        ht.close()
+        del ht
+        torch.cuda.empty_cache()
+    return out
+
+
 def host_run(liw, lp, sc, n=256):
     ra, rb, pa, pb = sc
     nd = ra.shape[0]
@@ -365,6 +504,10 @@ def main():
     ap.add_argument("--track-B", default="4096,49152")
     ap.add_argument("--track-distinct", type=int, default=16)
     ap.add_argument("--track-host-frames", type=int, default=2, help="frames of the host-glue baseline (0: none)")
+    ap.add_argument("--cold-start", type=int, default=0, help="frames per INIT window of the cold-start leg (0: none)")
+    ap.add_argument("--cold-B", default="4096,49152")
+    ap.add_argument("--cold-frames", type=int, default=4, help="tracking frames timed after the cold start")
+    ap.add_argument("--cold-host-frames", type=int, default=-1, help="frames of the host-glue baseline (-1: the whole cold start, 0: none)")
     a = ap.parse_args()
     import torch
     liw = importlib.import_module("2dliw-slam_amd")
@@ -387,6 +530,16 @@ def main():
         tsc = track_scenes(liw, synth, prm, lpt, a.track_distinct, a.track)
         res["track"] = {str(B): track_run(liw, torch, prm, lpt, tp, B, a.track, tsc, a.reps, a.track_host_frames)
                         for B in [int(x) for x in a.track_B.split(",") if x]}
+    if a.cold_start:
+        synth = importlib.import_module("2dliw-slam_amd.synth")
+        prm = synth.office_params()
+        lpt = dict(liw.laser.office_laser_params(prm), ref_n_accumulation=4)
+        tp = liw.laser_batch.office_track_params(prm)
+        ip = dict(slide_window_size=a.cold_start, p_motion_threshold=0.1, q_motion_threshold=0.1)
+        csc = track_scenes(liw, synth, prm, lpt, a.track_distinct, a.cold_start + 3 + a.cold_frames)
+        res["cold_start"] = {}
+        for B in [int(x) for x in a.cold_B.split(",") if x]:   # the host-glue baseline at the first B only: a Python loop over the robots
+            res["cold_start"][str(B)] = cold_run(liw, torch, prm, lpt, tp, ip, B, a.cold_frames, csc, a.reps, a.cold_host_frames if not res["cold_start"] else 0)
     print(json.dumps(res))
 
 
