@@ -352,5 +352,6 @@ class HostPreint:
 
 
 from .batch import BatchPreint, BatchSolver, shard_laser  # noqa: E402,F401
-from . import fleet, gridmap, laser, laser_batch, loop, outputs, posegraph  # noqa: E402,F401
+from . import fleet, gridmap, laser, laser_batch, loop, loop_batch, outputs, posegraph  # noqa: E402,F401
 from .fleet import FleetTracker, FleetTrajectory  # noqa: E402,F401
+from .loop_batch import FleetLoopDetector  # noqa: E402,F401

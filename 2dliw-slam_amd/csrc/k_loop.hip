@@ -28,31 +28,6 @@
 
 namespace liw_loop_dev {
 
-constexpr double kPi = 3.14159265358979323846;
-
-// match_des's bin of a pair: wrap the angle difference to [-pi, pi), truncate toward zero, shift by nAngle / 2.  Clamped to
-// the histogram (finite inputs never leave it: |bin - orign| <= int(pi / a_res) < orign).
-__device__ __forceinline__ int angle_bin(double a1, double a2, double a_res, int orign, int nb) {
-    double d = a1 - a2;
-    if (d >= kPi) d -= kPi * 2;
-    else if (d < -kPi) d += kPi * 2;
-    const double q = d / a_res;
-    int b = (q == q) ? (int)q : 0;
-    b += orign;
-    return b < 0 ? 0 : (b >= nb ? nb - 1 : b);
-}
-
-// first index in keys[0, n) with keys[e] >= v (keys ascending)
-__device__ __forceinline__ int lower_bound_u32(const uint32_t* keys, int n, uint32_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(64) void k_loop_describe(const double* __restrict__ pts, int n, int slot, Geom g, double d_res,
                                                       uint32_t* __restrict__ keys, double* __restrict__ aij, uint64_t* __restrict__ quick,
                                                       int* __restrict__ inv) {

@@ -22,6 +22,32 @@ struct Geom {                    // store strides and the matching constants
     double a_res;
 };
 
+constexpr double kPi = 3.14159265358979323846;
+
+// ---- row routines shared by k_loop.hip and k_loop_batch.hip (both include this header under fp contract(off))
+// match_des's bin of a pair: wrap the angle difference to [-pi, pi), truncate toward zero, shift by nAngle / 2.  Clamped to
+// the histogram (finite inputs never leave it: |bin - orign| <= int(pi / a_res) < orign).
+__device__ __forceinline__ int angle_bin(double a1, double a2, double a_res, int orign, int nb) {
+    double d = a1 - a2;
+    if (d >= kPi) d -= kPi * 2;
+    else if (d < -kPi) d += kPi * 2;
+    const double q = d / a_res;
+    int b = (q == q) ? (int)q : 0;
+    b += orign;
+    return b < 0 ? 0 : (b >= nb ? nb - 1 : b);
+}
+
+// first index in keys[0, n) with keys[e] >= v (keys ascending)
+__device__ __forceinline__ int lower_bound_u32(const uint32_t* keys, int n, uint32_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (keys[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // one wave per point of slot `slot`: rows of (dij << 12 | j) keys, aij and quick_des; inv[slot] = 1 on a dij overflow
 int launch_describe(const double* pts, int n, int slot, const Geom& g, double d_res, uint32_t* keys, double* aij, uint64_t* quick, int* inv,
                     hipStream_t s);
