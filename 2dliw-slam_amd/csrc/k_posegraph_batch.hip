@@ -1,0 +1,729 @@
+// k_posegraph_batch.hip — the fleet's pose-graph back-end on the MI355X (C ABI include/liw_posegraph_batch.h): B key-frame queues with
+// their edges, and keyframe_manager::solve for the robots that are due, all in lock-step with the LM bookkeeping on the device.
+//
+// Bookkeeping (add_keyframes, add_loops, due, correct): a lane per robot, make_tf / log_SE3 with liw_crmath.hpp.
+// Solve: per LM iteration the linear system liw_posegraph_solve's sparse path solves (k_posegraph.hip), one robot at a time there, all
+// selected robots here.  Every kernel has a fixed grid over (robot, item) slots; a wave whose robot is finished, not selected, or not
+// in the phase the kernel serves exits at once, so the launches of all iterations can be enqueued without a read-back.
+//   k_fpg_setup       wave per robot: poses -> x, the separator list (frame 0, the last frame, loop end points, every 48th frame) by
+//                     ballots and prefix counts, LM state.
+//   k_fpg_linearize   16 lanes per (robot, edge) and 8 per (robot, key frame): edge_res / pg_ground_res of k_posegraph_dev.hpp with a
+//                     dual direction per lane, always with the Jacobian (a candidate that is accepted needs no second pass).
+//   k_fpg_assemble    wave per (robot, key frame): 6x6 diagonal block, gradient, off-diagonal blocks.  A chain needs no incidence
+//                     list: key frame f touches sequential edges f-1 and f, then the robot's loops in edge order (the order
+//                     k_pg_assemble_blocks sums in).
+//   k_fpg_head        wave per robot: cost / norms of a new point, termination 1 / 4 / 5, the LM diagonal.
+//   k_fpg_seg_elim    wave per (robot, segment): pg_seg_elim_wave with the robot's own radius.
+//   k_fpg_reduced     work-group per robot: the separator system (packed lower triangle, in LDS when it fits, else in the robot's work
+//                     area: the same instructions on another pointer), loop blocks in edge order by one wave, right-looking Cholesky,
+//                     both triangular solves, scatter.
+//   k_fpg_backsub     wave per (robot, segment): pg_seg_backsub_wave.
+//   k_fpg_decide1     wave per robot: step validity, model cost change, Plus into the candidate, step norm; termination 6.
+//   k_fpg_decide2     wave per robot: candidate cost, termination 2 / 3, rho, accept / reject, radius.
+// The rules are the functions of liw_lm_rules.hpp.  A robot that terminates writes its poses, summary and the commit
+// (modify_delta_tf, pending flag, last_solve_time, solves) itself.
+#include "k_posegraph_batch.hpp"
+#include "k_posegraph_dev.hpp"
+#include "liw_crmath.hpp"
+
+namespace liw_fpg_dev {
+
+using namespace liw;
+
+// A double whose sin / cos / atan2 are the correctly rounded ones of liw_crmath.hpp (as the tracking glue's and k_loop_batch.hip's)
+struct CR {
+    double v;
+    __host__ __device__ CR() : v(0.0) {}
+    __host__ __device__ CR(double c) : v(c) {}  // NOLINT(implicit)
+};
+__host__ __device__ inline CR operator+(const CR& a, const CR& b) { return CR(a.v + b.v); }
+__host__ __device__ inline CR operator-(const CR& a, const CR& b) { return CR(a.v - b.v); }
+__host__ __device__ inline CR operator-(const CR& a) { return CR(-a.v); }
+__host__ __device__ inline CR operator*(const CR& a, const CR& b) { return CR(a.v * b.v); }
+__host__ __device__ inline CR operator/(const CR& a, const CR& b) { return CR(a.v / b.v); }
+__host__ __device__ inline bool operator>(const CR& a, const CR& b) { return a.v > b.v; }
+__host__ __device__ inline bool operator<(const CR& a, const CR& b) { return a.v < b.v; }
+__host__ __device__ inline CR dsqrt(const CR& a) { return CR(sqrt(a.v)); }
+__host__ __device__ inline CR dsin(const CR& a) { return CR(liw_cr::cr_sin(a.v)); }
+__host__ __device__ inline CR dcos(const CR& a) { return CR(liw_cr::cr_cos(a.v)); }
+__host__ __device__ inline CR datan2(const CR& y, const CR& x) { return CR(liw_cr::cr_atan2(y.v, x.v)); }
+__host__ __device__ inline CR dfloor(const CR& a) { return CR(floor(a.v)); }
+
+enum { PH_IDLE = 0, PH_SOLVE = 1, PH_CAND = 2, PH_ASM = 3, PH_INIT = 4 };
+// LM state of a robot (head of its work block)
+struct Lm {
+    double radius, dec, x_cost, x_norm, gmax, mcc, init_cost, step_norm;
+    int iter, invalid, succ, last_ok, term, reuse, done, phase, ns, N, nl, status;
+};
+
+__device__ __forceinline__ char* region(char* store, const Lay& L, int b) { return store + (size_t)b * L.robot_bytes; }
+__device__ __forceinline__ char* workblk(char* store, const Lay& L, int b) { return store + L.work_off + (size_t)b * L.work_robot_bytes; }
+__device__ __forceinline__ bool robot_on(const unsigned char* a, int b) { return !a || a[b] != 0; }
+
+__device__ __forceinline__ void store_tf(const Iso<CR>& T, double* tf) {
+    for (int k = 0; k < 9; ++k) tf[k] = T.R.m[k].v;
+    tf[9] = T.t.x.v; tf[10] = T.t.y.v; tf[11] = T.t.z.v;
+}
+__device__ __forceinline__ Iso<CR> load_tf(const double* tf) { return cast_iso<CR>(tf, tf + 9); }
+__device__ __forceinline__ Iso<CR> tf_of_pose(const double* ps) { return make_tf(V3<CR>(ps[0], ps[1], ps[2]), V3<CR>(ps[3], ps[4], ps[5])); }
+// log_SE3: p = t, q = log_SO3(R)
+__device__ __forceinline__ void pose_of_tf(const Iso<CR>& T, double* ps) {
+    const V3<CR> q = log_SO3(T.R);
+    ps[0] = T.t.x.v; ps[1] = T.t.y.v; ps[2] = T.t.z.v; ps[3] = q.x.v; ps[4] = q.y.v; ps[5] = q.z.v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// std::max as the host loop folds it: a NaN operand never replaces the running maximum
+__device__ __forceinline__ double max_skip_nan(double m, double v) { return (m < v) ? v : m; }
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max_skip_nan(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------------------- bookkeeping
+__global__ __launch_bounds__(256) void k_fpg_reset(char* store, Lay L, const unsigned char* __restrict__ mask) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B || !robot_on(mask, b)) return;
+    char* R = region(store, L, b);
+    int* hdr = (int*)R;
+    for (int k = 0; k < 8; ++k) hdr[k] = 0;
+    *(double*)(R + HB_TLAST) = -1e300;
+    double* mod = (double*)(R + HB_MOD);
+    for (int k = 0; k < 12; ++k) mod[k] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
+    for (int k = 0; k < 4; ++k) ((double*)(R + HB_SUMMARY))[k] = 0.0;
+}
+
+__global__ __launch_bounds__(64) void k_fpg_add_keyframes(char* store, Lay L, const unsigned char* __restrict__ key, const double* __restrict__ pose,
+                                                          const double* __restrict__ stamp, const unsigned char* __restrict__ mask,
+                                                          unsigned char* __restrict__ added) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B || !robot_on(mask, b)) return;
+    if (!key[b]) {
+        if (added) added[b] = 0;
+        return;
+    }
+    char* R = region(store, L, b);
+    int* hdr = (int*)R;
+    const int n = hdr[H_NKF];
+    if (n >= L.K) {
+        hdr[H_FULL] = 1;
+        if (added) added[b] = 0;
+        return;
+    }
+    const Iso<CR> T = tf_of_pose(pose + (size_t)b * 6);
+    double* tfs = (double*)(R + L.r_tf);
+    store_tf(T, tfs + (size_t)n * 12);
+    pose_of_tf(mul(load_tf((const double*)(R + HB_MOD)), T), (double*)(R + L.r_pose) + (size_t)n * 6);
+    if (n > 0) store_tf(mul(inverse(load_tf(tfs + (size_t)(n - 1) * 12)), T), (double*)(R + L.r_seq) + (size_t)n * 12);
+    ((double*)(R + L.r_stamp))[n] = stamp[b];
+    hdr[H_NKF] = n + 1;
+    if (added) added[b] = 1;
+}
+
+__global__ __launch_bounds__(64) void k_fpg_add_loops(char* store, Lay L, const unsigned char* __restrict__ found, const int* __restrict__ edge,
+                                                      const double* __restrict__ tf12, const unsigned char* __restrict__ mask) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B || !robot_on(mask, b) || !found[b]) return;
+    char* R = region(store, L, b);
+    int* hdr = (int*)R;
+    const int n = hdr[H_NKF], i1 = edge[(size_t)b * 3], i2 = edge[(size_t)b * 3 + 1];
+    if (i1 < 0 || i1 >= n || i2 < 0 || i2 >= n || i1 == i2) { hdr[H_BAD] = 1; return; }
+    const int nl = hdr[H_NLOOP];
+    if (nl >= L.ML) { hdr[H_LFULL] = 1; return; }
+    int* lidx = (int*)(R + L.r_lidx);
+    lidx[2 * nl] = i1; lidx[2 * nl + 1] = i2;
+    double* ltf = (double*)(R + L.r_ltf) + (size_t)nl * 12;
+    for (int k = 0; k < 12; ++k) ltf[k] = tf12[(size_t)b * 12 + k];
+    hdr[H_NLOOP] = nl + 1;
+    hdr[H_PEND] = 1;
+}
+
+// one work-group: due flags and their count (a block sum of integers)
+__global__ __launch_bounds__(256) void k_fpg_due(char* store, Lay L, double period, const unsigned char* __restrict__ key, const double* __restrict__ stamp,
+                                                 const unsigned char* __restrict__ mask, unsigned char* __restrict__ due, int* n_due) {
+    __shared__ int red[256];
+    int cnt = 0;
+    for (int b = threadIdx.x; b < L.B; b += 256) {
+        if (!robot_on(mask, b)) continue;
+        const char* R = region(store, L, b);
+        const int* hdr = (const int*)R;
+        const bool d = key[b] != 0 && hdr[H_PEND] != 0 && stamp[b] - *(const double*)(R + HB_TLAST) > period;
+        due[b] = d ? 1 : 0;
+        cnt += d ? 1 : 0;
+    }
+    red[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0 && n_due) *n_due = red[0];
+}
+
+__global__ __launch_bounds__(64) void k_fpg_correct(char* store, Lay L, const double* __restrict__ pose_in, double* __restrict__ pose_out,
+                                                    const unsigned char* __restrict__ mask) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= L.B || !robot_on(mask, b)) return;
+    const char* R = region(store, L, b);
+    pose_of_tf(mul(load_tf((const double*)(R + HB_MOD)), tf_of_pose(pose_in + (size_t)b * 6)), pose_out + (size_t)b * 6);
+}
+
+// ------------------------------------------------------------------------------------------------------------- solve
+struct Wk {   // a robot's work block
+    Lm* lm; double *x, *cand, *y, *scale, *dgn, *Ye, *Yg, *Dd, *gd, *Os, *Lb, *Sred, *rec, *Hr, *rhs; int *sep, *sepidx;
+};
+__device__ __forceinline__ Wk work_of(char* store, const Lay& L, int b) {
+    char* W = workblk(store, L, b);
+    Wk w;
+    w.lm = (Lm*)W;
+    w.x = (double*)(W + L.w_x); w.cand = (double*)(W + L.w_cand); w.y = (double*)(W + L.w_y); w.scale = (double*)(W + L.w_scale);
+    w.dgn = (double*)(W + L.w_dgn); w.Ye = (double*)(W + L.w_Ye); w.Yg = (double*)(W + L.w_Yg); w.Dd = (double*)(W + L.w_Dd);
+    w.gd = (double*)(W + L.w_gd); w.Os = (double*)(W + L.w_Os); w.Lb = (double*)(W + L.w_Lb); w.Sred = (double*)(W + L.w_Sred);
+    w.rec = (double*)(W + L.w_rec); w.Hr = (double*)(W + L.w_Hr); w.rhs = (double*)(W + L.w_rhs);
+    w.sep = (int*)(W + L.w_sep); w.sepidx = (int*)(W + L.w_sepidx);
+    return w;
+}
+
+__global__ __launch_bounds__(64) void k_fpg_setup(char* store, Lay L, const unsigned char* __restrict__ sel) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const char* R = region(store, L, b);
+    const int* hdr = (const int*)R;
+    Wk w = work_of(store, L, b);
+    const int N = hdr[H_NKF], nl = hdr[H_NLOOP];
+    if (!sel[b] || N < 2) {
+        if (lane == 0) w.lm->done = 1;
+        return;
+    }
+    const double* ps = (const double*)(R + L.r_pose);
+    for (int i = lane; i < 6 * N; i += 64) { const double v = ps[i]; w.x[i] = v; w.cand[i] = v; w.y[i] = 0.0; }
+    const int* lidx = (const int*)(R + L.r_lidx);
+    int base = 0;
+    for (int f0 = 0; f0 < N; f0 += 64) {
+        const int f = f0 + lane;
+        bool flag = f < N && (f == 0 || f == N - 1 || f % PG_STRIDE == 0);
+        if (f < N && !flag)
+            for (int l = 0; l < nl; ++l) flag = flag || lidx[2 * l] == f || lidx[2 * l + 1] == f;
+        const unsigned long long m = __ballot(flag);
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        if (f < N) w.sepidx[f] = flag ? base + rank : -1;
+        if (flag) w.sep[base + rank] = f;
+        base += __popcll(m);
+    }
+    if (lane == 0) {
+        Lm s;
+        s.radius = kInitRadius; s.dec = 2.0; s.x_cost = 0.0; s.x_norm = 0.0; s.gmax = 0.0; s.mcc = 0.0; s.init_cost = 0.0; s.step_norm = 0.0;
+        s.iter = 0; s.invalid = 0; s.succ = 0; s.last_ok = 1; s.term = 0; s.reuse = 0; s.done = 0; s.phase = PH_INIT; s.ns = base; s.N = N; s.nl = nl;
+        s.status = 0;
+        *w.lm = s;
+    }
+}
+
+// Y of edge slot e [6][13] = [J | r], of key frame f [2][7]; which = 0: at x for robots in PH_INIT, 1: at the candidate for PH_CAND
+__global__ __launch_bounds__(64) void k_fpg_linearize(char* store, Lay L, Noise noise, DevParams P, int which) {
+    __shared__ double Y[4][6 * 13];
+    const int lane = threadIdx.x & 63, grp = lane >> 4, d = lane & 15;
+    const long long edge_slots = (long long)L.B * L.NE;
+    const long long edge_blocks = (edge_slots + 3) / 4;
+    const int want = which ? PH_CAND : PH_INIT;
+    if ((long long)blockIdx.x < edge_blocks) {
+        const long long slot = (long long)blockIdx.x * 4 + grp;
+        const int b = slot < edge_slots ? (int)(slot / L.NE) : 0, e = (int)(slot % L.NE);
+        Wk w = work_of(store, L, b);
+        const char* R = region(store, L, b);
+        bool on = slot < edge_slots && !w.lm->done && w.lm->phase == want;
+        int i = 0, j = 0;
+        const double* tf = nullptr;
+        double weight = 1.0;
+        if (on) {
+            const int N = w.lm->N, nl = w.lm->nl;
+            if (e < L.K - 1) {
+                on = e < N - 1;
+                i = e; j = e + 1;
+                tf = (const double*)(R + L.r_seq) + (size_t)(e + 1) * 12;
+            } else {
+                const int l = e - (L.K - 1);
+                on = l < nl;
+                if (on) { i = ((const int*)(R + L.r_lidx))[2 * l]; j = ((const int*)(R + L.r_lidx))[2 * l + 1]; }
+                tf = (const double*)(R + L.r_ltf) + (size_t)l * 12;
+                weight = noise.loop_edge_k;
+            }
+        }
+        const double* x = which ? w.cand : w.x;
+        const double* xi = x + (size_t)i * 6;
+        const double* xj = x + (size_t)j * 6;
+        if (on && d < 13) {
+            LJ pi[3], qi[3], pj[3], qj[3], res[6];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                pi[k] = LJ(xi[k], d == k ? 1.0 : 0.0);
+                qi[k] = LJ(xi[3 + k], d == 3 + k ? 1.0 : 0.0);
+                pj[k] = LJ(xj[k], d == 6 + k ? 1.0 : 0.0);
+                qj[k] = LJ(xj[3 + k], d == 9 + k ? 1.0 : 0.0);
+            }
+            edge_res<LJ>(tf, weight, noise.J, pi, qi, pj, qj, res);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) Y[grp][r * 13 + d] = d < 12 ? res[r].d : res[r].v;
+        }
+        __syncthreads();
+        if (on && d < 12) {   // local parameterisation: J_theta <- J_theta * dPlus/ddelta  (lane = (row r, pose which))
+            const int r = d % 6, side = d / 6;
+            double Pq[9];
+            if (plus_jac((side ? xj : xi) + 3, Pq)) {
+                double* row = &Y[grp][r * 13 + 6 * side + 3];
+                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
+                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
+                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
+                row[0] = t0; row[1] = t1; row[2] = t2;
+            }
+        }
+        __syncthreads();
+        if (on && d < 13)
+#pragma unroll
+            for (int r = 0; r < 6; ++r) w.Ye[(size_t)e * 78 + r * 13 + d] = Y[grp][r * 13 + d];
+    } else {
+        // ground factors: 8 key frames per wave, 6 dual directions + value
+        const int sub = lane >> 3, dir = lane & 7;
+        const long long slot = ((long long)blockIdx.x - edge_blocks) * 8 + sub;
+        const long long slots = (long long)L.B * L.K;
+        const int b = slot < slots ? (int)(slot / L.K) : 0, f = (int)(slot % L.K);
+        Wk w = work_of(store, L, b);
+        const bool on = slot < slots && !w.lm->done && w.lm->phase == want && f < w.lm->N;
+        const double* x = which ? w.cand : w.x;
+        double* Yl = &Y[0][0] + sub * 16;
+        if (on && dir < 7) {
+            const double* s_ = x + (size_t)f * 6;
+            LJ p[3], q[3], res[2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { p[k] = LJ(s_[k], dir == k ? 1.0 : 0.0); q[k] = LJ(s_[3 + k], dir == 3 + k ? 1.0 : 0.0); }
+            pg_ground_res<LJ>(P, p, q, res);
+            Yl[dir] = (dir < 6 ? res[0].d : res[0].v) * noise.ground_on_p;
+            Yl[7 + dir] = (dir < 6 ? res[1].d : res[1].v) * noise.ground_on_q;
+        }
+        __syncthreads();
+        if (on && dir < 2) {
+            double Pq[9];
+            if (plus_jac(x + (size_t)f * 6 + 3, Pq)) {
+                double* row = Yl + dir * 7 + 3;
+                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
+                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
+                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
+                row[0] = t0; row[1] = t1; row[2] = t2;
+            }
+        }
+        __syncthreads();
+        if (on && dir < 7) {
+            w.Yg[(size_t)f * 14 + dir] = Yl[dir];
+            w.Yg[(size_t)f * 14 + 7 + dir] = Yl[7 + dir];
+        }
+    }
+}
+
+// wave per (robot, key frame), for robots in PH_INIT or PH_ASM.  Key frame 0 is the constant one: identity block, zero gradient.
+__global__ __launch_bounds__(64) void k_fpg_assemble(char* store, Lay L) {
+    const int b = blockIdx.x / L.K, i = blockIdx.x % L.K, lane = threadIdx.x & 63;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done || (w.lm->phase != PH_INIT && w.lm->phase != PH_ASM)) return;
+    const int N = w.lm->N, nl = w.lm->nl;
+    if (i >= N) return;
+    const int* lidx = (const int*)(region(store, L, b) + L.r_lidx);
+    const double *Ye = w.Ye, *Yg = w.Yg;
+    const int r = lane / 6, c = lane % 6;
+    double acc = 0.0;
+    const bool is_const = i == 0;
+    if (!is_const) {
+        if (lane < 36) acc = Yg[(size_t)i * 14 + r] * Yg[(size_t)i * 14 + c] + Yg[(size_t)i * 14 + 7 + r] * Yg[(size_t)i * 14 + 7 + c];
+        else if (lane < 42) acc = Yg[(size_t)i * 14 + (lane - 36)] * Yg[(size_t)i * 14 + 6] + Yg[(size_t)i * 14 + 7 + (lane - 36)] * Yg[(size_t)i * 14 + 13];
+    }
+    // incident edges in edge order: sequential i-1 (side 1), sequential i (side 0), then the loops that name i
+    const int n_inc = 2 + nl;
+    for (int t = 0; t < n_inc; ++t) {
+        int e, side, j;
+        if (t == 0) { if (i == 0) continue; e = i - 1; side = 1; j = i - 1; }
+        else if (t == 1) { if (i >= N - 1) continue; e = i; side = 0; j = i + 1; }
+        else {
+            const int l = t - 2, i1 = lidx[2 * l], i2 = lidx[2 * l + 1];
+            if (i1 == i) { side = 0; j = i2; } else if (i2 == i) { side = 1; j = i1; } else continue;
+            e = L.K - 1 + l;
+        }
+        const double* Y = Ye + (size_t)e * 78;
+        if (!is_const) {
+            double sm = 0.0;
+            if (lane < 36) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) sm += Y[k * 13 + 6 * side + r] * Y[k * 13 + 6 * side + c];
+            } else if (lane < 42) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) sm += Y[k * 13 + 6 * side + (lane - 36)] * Y[k * 13 + 12];
+            }
+            acc += sm;
+        }
+        if (side == 0 && lane < 36) {   // H[index1, index2](r, c) = sum_k J1[k][r] J2[k][c]; zero against the constant key frame
+            double o = 0.0;
+            if (!is_const && j != 0) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) o += Y[k * 13 + r] * Y[k * 13 + 6 + c];
+            }
+            if (t == 1) w.Os[(size_t)i * 36 + lane] = o;
+            else w.Lb[(size_t)(t - 2) * 36 + lane] = o;
+        }
+    }
+    if (i == N - 1 && lane < 36) w.Os[(size_t)i * 36 + lane] = 0.0;
+    if (is_const && lane < 36) acc = r == c ? 1.0 : 0.0;
+    if (lane < 36) w.Dd[(size_t)i * 36 + lane] = acc;
+    else if (lane < 42) w.gd[i * 6 + (lane - 36)] = acc;
+}
+
+// 1/2 sum r^2 of the robot's blocks in Ye / Yg (the constant key frame's ground block is not part of the cost), by one wave
+__device__ __forceinline__ double cost_of(const Lay& L, const Wk& w, int N, int nl, int lane) {
+    double s = 0.0;
+    for (int e = lane; e < N - 1; e += 64)
+#pragma unroll
+        for (int r = 0; r < 6; ++r) { const double v = w.Ye[(size_t)e * 78 + r * 13 + 12]; s += v * v; }
+    for (int l = lane; l < nl; l += 64)
+#pragma unroll
+        for (int r = 0; r < 6; ++r) { const double v = w.Ye[(size_t)(L.K - 1 + l) * 78 + r * 13 + 12]; s += v * v; }
+    for (int f = 1 + lane; f < N; f += 64) { const double a = w.Yg[(size_t)f * 14 + 6], c = w.Yg[(size_t)f * 14 + 13]; s += a * a; s += c * c; }
+    return 0.5 * wave_sum(s);
+}
+
+// Plus of the so3 parameterisation (factor_common.h:41-53): the rotation vectors add, then wrap
+__device__ __forceinline__ void plus6(const double* x, const double* d, double* out) {
+    for (int k = 0; k < 3; ++k) out[k] = x[k] + d[k];
+    const V3<double> r = normalize_so3(V3<double>(x[3] + d[3], x[4] + d[4], x[5] + d[5]));
+    out[3] = r.x; out[4] = r.y; out[5] = r.z;
+}
+
+// the robot is done: poses, summary and keyframe_manager's commit after a solve (mirror :178-188)
+__device__ __forceinline__ void finish(char* store, const Lay& L, int b, const Wk& w, int term, const double* stamp, liw_summary* summary, int lane) {
+    char* R = region(store, L, b);
+    const int N = w.lm->N;
+    double* ps = (double*)(R + L.r_pose);
+    for (int i = lane; i < 6 * N; i += 64) ps[i] = w.x[i];
+    if (lane == 0) {
+        liw_summary sm;
+        sm.iterations = w.lm->iter; sm.successful_steps = w.lm->succ; sm.termination = term; sm.initial_cost = w.lm->init_cost; sm.final_cost = w.lm->x_cost;
+        *(liw_summary*)(R + HB_SUMMARY) = sm;
+        summary[b] = sm;
+        const Iso<CR> cur = tf_of_pose(w.x + (size_t)(N - 1) * 6);
+        const Iso<CR> last = load_tf((const double*)(R + L.r_tf) + (size_t)(N - 1) * 12);
+        store_tf(mul(cur, inverse(last)), (double*)(R + HB_MOD));
+        int* hdr = (int*)R;
+        hdr[H_PEND] = 0;
+        hdr[H_SOLVES] += 1;
+        *(double*)(R + HB_TLAST) = stamp[b];
+        w.lm->term = term;
+        w.lm->done = 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_fpg_head(char* store, Lay L, int max_iters, const double* __restrict__ stamp, liw_summary* summary) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done) return;
+    Lm s = *w.lm;
+    const int N = s.N, n = 6 * N;
+    if (s.phase == PH_INIT) {
+        s.x_cost = cost_of(L, w, N, s.nl, lane);
+        s.init_cost = s.x_cost;
+        for (int i = lane; i < n; i += 64) w.scale[i] = i < 6 ? 1.0 : 1.0 / (1.0 + sqrt(w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7]));
+    }
+    if (s.phase == PH_INIT || s.phase == PH_ASM) {
+        double sq = 0.0, m = 0.0;
+        for (int i = 6 + lane; i < n; i += 64) sq += w.x[i] * w.x[i];
+        s.x_norm = sqrt(wave_sum(sq));
+        for (int f = 1 + lane; f < N; f += 64) {   // max |x - Plus(x, -g)|
+            double ng[6], xp[6];
+            for (int k = 0; k < 6; ++k) ng[k] = -w.gd[f * 6 + k];
+            plus6(w.x + (size_t)f * 6, ng, xp);
+            for (int k = 0; k < 6; ++k) m = max_skip_nan(m, fabs(w.x[f * 6 + k] - xp[k]));
+        }
+        s.gmax = wave_max(m);
+    }
+    int term = 0;
+    if (lm_cap_reached(s.iter, max_iters, s.phase == PH_INIT)) term = 4;
+    else term = lm_gradient_term(s.iter == 0, s.last_ok != 0, s.gmax, s.radius > kMinRadius);
+    if (term) {
+        if (lane == 0) *w.lm = s;
+        finish(store, L, b, w, term, stamp, summary, lane);
+        return;
+    }
+    ++s.iter;
+    if (!s.reuse)
+        for (int i = lane; i < n; i += 64) {
+            const double sc = w.scale[i];
+            double v = w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7] * sc * sc;   // clamped as std::min(std::max(v, lo), hi) does: a NaN stays
+            v = (v < kMinDiag) ? kMinDiag : v;
+            v = (kMaxDiag < v) ? kMaxDiag : v;
+            w.dgn[i] = i < 6 ? 0.0 : v;
+        }
+    s.reuse = 1;
+    s.phase = PH_SOLVE;
+    s.status = 0;
+    if (lane == 0) *w.lm = s;
+}
+
+__global__ __launch_bounds__(64) void k_fpg_seg_elim(char* store, Lay L) {
+    const int nsg = L.NS - 1;
+    const int b = blockIdx.x / nsg, sg = blockIdx.x % nsg, lane = threadIdx.x & 63;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done || w.lm->phase != PH_SOLVE || sg >= w.lm->ns - 1) return;
+    const int a = w.sep[sg], bb = w.sep[sg + 1];
+    const bool ok = pg_seg_elim_wave(a, bb, lane, w.Dd, w.gd, w.Os, w.scale, w.dgn, w.lm->radius, w.Sred + (size_t)sg * PG_SEG, w.rec);
+    if (!ok && lane == 0) atomicOr(&w.lm->status, 1);
+}
+
+__device__ __forceinline__ size_t tri(int r, int c) { return (size_t)r * (r + 1) / 2 + c; }   // packed lower triangle, c <= r
+
+// work-group per robot: the separators' system A y = g_s (as k_pg_reduced + k_pg_reduced_loops build it), Cholesky, both solves, scatter
+__global__ __launch_bounds__(256) void k_fpg_reduced(char* store, Lay L, int lds_doubles) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done || w.lm->phase != PH_SOLVE) return;
+    const int ns = w.lm->ns, nr = 6 * ns, nl = w.lm->nl;
+    const int tri_n = nr * (nr + 1) / 2;
+    double* A = tri_n <= lds_doubles ? lds : w.Hr;   // the same instructions either way
+    double* rhs = w.rhs;
+    const double radius = w.lm->radius;
+    const double *Dd = w.Dd, *gd = w.gd, *Os = w.Os, *scale = w.scale, *dgn = w.dgn, *Sred = w.Sred;
+    const int* sep = w.sep;
+    for (int e = tid; e < tri_n; e += 256) A[e] = 0.0;
+    __syncthreads();
+    for (int t = wave; t < ns; t += 4) {
+        const int f = sep[t], r = lane / 6, c = lane % 6;
+        const double* sf = scale + (size_t)f * 6;
+        const bool is_const = f == 0;
+        const bool left = t > 0 && sep[t] - sep[t - 1] > 1, right = t + 1 < ns && sep[t + 1] - sep[t] > 1;   // segments with interior frames
+        if (lane < 36) {
+            double v = is_const ? (r == c ? 1.0 : 0.0) : Dd[(size_t)f * 36 + lane] * sf[r] * sf[c] + (r == c ? dgn[(size_t)f * 6 + c] / radius : 0.0);
+            if (!is_const) {
+                if (right) v += Sred[(size_t)t * PG_SEG + lane];
+                if (left) v += Sred[(size_t)(t - 1) * PG_SEG + 72 + lane];
+            }
+            if (r >= c) A[tri(t * 6 + r, t * 6 + c)] = v;
+            if (t > 0) {   // block (t, t-1): direct edge when the separators are chain neighbours, else the segment's fill
+                const int fa = sep[t - 1];
+                const double o = left ? Sred[(size_t)(t - 1) * PG_SEG + 36 + lane] : Os[(size_t)fa * 36 + c * 6 + r] * scale[(size_t)fa * 6 + c] * sf[r];
+                A[tri(t * 6 + r, (t - 1) * 6 + c)] = (is_const || fa == 0) ? 0.0 : o;
+            }
+        } else if (lane < 42) {
+            const int k = lane - 36;
+            double v = is_const ? 0.0 : gd[(size_t)f * 6 + k] * sf[k];
+            if (!is_const) {
+                if (right) v += Sred[(size_t)t * PG_SEG + 108 + k];
+                if (left) v += Sred[(size_t)(t - 1) * PG_SEG + 114 + k];
+            }
+            rhs[t * 6 + k] = v;
+        }
+    }
+    __syncthreads();
+    if (wave == 0 && lane < 36) {   // loop edges, in edge order by one wave (several edges may share a block)
+        const int* lidx = (const int*)(region(store, L, b) + L.r_lidx);
+        const int r = lane / 6, c = lane % 6;
+        for (int e = 0; e < nl; ++e) {
+            const int i1 = lidx[2 * e], i2 = lidx[2 * e + 1];
+            if (i1 == 0 || i2 == 0) continue;
+            const int t1 = w.sepidx[i1], t2 = w.sepidx[i2];
+            const double v = w.Lb[(size_t)e * 36 + lane] * scale[(size_t)i1 * 6 + r] * scale[(size_t)i2 * 6 + c];   // H[i1, i2](r, c)
+            if (t1 > t2) A[tri(t1 * 6 + r, t2 * 6 + c)] += v;
+            else A[tri(t2 * 6 + c, t1 * 6 + r)] += v;
+        }
+    }
+    __syncthreads();
+    // right-looking Cholesky, a column per step; every thread reads the same pivot
+    bool ok = true;
+    for (int k = 0; k < nr; ++k) {
+        const double piv = A[tri(k, k)];
+        if (!(piv > 0.0) || !isfinite(piv)) ok = false;
+        const double inv = 1.0 / sqrt(piv);
+        __syncthreads();
+        for (int i = k + tid; i < nr; i += 256) A[tri(i, k)] *= inv;   // i = k: sqrt(piv)
+        __syncthreads();
+        const int m = nr - k - 1;
+        for (int e = tid; e < m * m; e += 256) {
+            const int i = k + 1 + e / m, j = k + 1 + e % m;
+            if (j <= i) A[tri(i, j)] -= A[tri(i, k)] * A[tri(j, k)];
+        }
+        __syncthreads();
+    }
+    for (int k = 0; k < nr; ++k) {          // L y = b
+        const double xk = rhs[k] / A[tri(k, k)];
+        __syncthreads();
+        if (tid == 0) rhs[k] = xk;
+        for (int i = k + 1 + tid; i < nr; i += 256) rhs[i] -= A[tri(i, k)] * xk;
+        __syncthreads();
+    }
+    for (int k = nr - 1; k >= 0; --k) {     // L^T x = y
+        const double xk = rhs[k] / A[tri(k, k)];
+        __syncthreads();
+        if (tid == 0) rhs[k] = xk;
+        for (int i = tid; i < k; i += 256) rhs[i] -= A[tri(k, i)] * xk;
+        __syncthreads();
+    }
+    for (int e = tid; e < nr; e += 256) w.y[(size_t)sep[e / 6] * 6 + e % 6] = rhs[e];
+    if (!ok && tid == 0) atomicOr(&w.lm->status, 1);
+}
+
+__global__ __launch_bounds__(64) void k_fpg_backsub(char* store, Lay L) {
+    const int nsg = L.NS - 1;
+    const int b = blockIdx.x / nsg, sg = blockIdx.x % nsg, lane = threadIdx.x & 63;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done || w.lm->phase != PH_SOLVE || sg >= w.lm->ns - 1) return;
+    pg_seg_backsub_wave(w.sep[sg], w.sep[sg + 1], lane, w.rec, w.y);
+}
+
+__global__ __launch_bounds__(64) void k_fpg_decide1(char* store, Lay L, const double* __restrict__ stamp, liw_summary* summary) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done || w.lm->phase != PH_SOLVE) return;
+    Lm s = *w.lm;
+    const int N = s.N, n = 6 * N;
+    bool fin = true;
+    for (int i = lane; i < n; i += 64) fin = fin && isfinite(w.y[i]);
+    const bool solved = s.status == 0 && __ballot(!fin) == 0ull;
+    // model cost change with (A + D^2) y = g_s, step = -y:  (y'g_s + y'D^2 y) / 2
+    double mcc = 0.0;
+    if (solved) {
+        double ytg = 0.0, dsum = 0.0;
+        for (int i = 6 + lane; i < n; i += 64) {
+            const double yi = w.y[i];
+            ytg += yi * (w.gd[i] * w.scale[i]);
+            dsum += w.dgn[i] / s.radius * yi * yi;
+        }
+        mcc = 0.5 * (wave_sum(ytg) + wave_sum(dsum));
+    }
+    if (!lm_step_valid(solved, mcc)) {
+        if (lm_gives_up(s.invalid++)) {
+            --s.iter;
+            if (lane == 0) *w.lm = s;
+            finish(store, L, b, w, 6, stamp, summary, lane);
+            return;
+        }
+        lm_step_rejected(s.radius, s.dec, s.reuse);
+        s.last_ok = 0;
+        s.phase = PH_IDLE;
+        if (lane == 0) *w.lm = s;
+        return;
+    }
+    s.invalid = 0;
+    s.mcc = mcc;
+    double sq = 0.0;
+    for (int f = 1 + lane; f < N; f += 64) {
+        double dl[6], xc[6];
+        for (int k = 0; k < 6; ++k) dl[k] = -w.y[f * 6 + k] * w.scale[f * 6 + k];
+        plus6(w.x + (size_t)f * 6, dl, xc);
+        for (int k = 0; k < 6; ++k) {
+            w.cand[f * 6 + k] = xc[k];
+            const double df = w.x[f * 6 + k] - xc[k];
+            sq += df * df;
+        }
+    }
+    s.step_norm = sqrt(wave_sum(sq));
+    s.phase = PH_CAND;
+    if (lane == 0) *w.lm = s;
+}
+
+__global__ __launch_bounds__(64) void k_fpg_decide2(char* store, Lay L, const double* __restrict__ stamp, liw_summary* summary) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    Wk w = work_of(store, L, b);
+    if (w.lm->done || w.lm->phase != PH_CAND) return;
+    Lm s = *w.lm;
+    const int N = s.N, n = 6 * N;
+    double cc = cost_of(L, w, N, s.nl, lane);
+    if (!isfinite(cc)) cc = kFailedEvalCost;
+    const int term = lm_candidate_term(s.step_norm, s.x_norm, s.x_cost, cc);
+    if (term) {
+        finish(store, L, b, w, term, stamp, summary, lane);
+        return;
+    }
+    const double rho = (s.x_cost - cc) / s.mcc;
+    if (lm_accepts(rho)) {
+        for (int i = lane; i < n; i += 64) w.x[i] = w.cand[i];
+        s.x_cost = cc;
+        lm_step_accepted(rho, s.radius, s.dec, s.reuse);
+        ++s.succ;
+        s.last_ok = 1;
+        s.phase = PH_ASM;
+    } else {
+        lm_step_rejected(s.radius, s.dec, s.reuse);
+        s.last_ok = 0;
+        s.phase = PH_IDLE;
+    }
+    if (lane == 0) *w.lm = s;
+}
+
+// robots still iterating (a sum of integers by one work-group)
+__global__ __launch_bounds__(256) void k_fpg_count(char* store, Lay L) {
+    __shared__ int red[256];
+    int cnt = 0;
+    for (int b = threadIdx.x; b < L.B; b += 256) cnt += ((const Lm*)workblk(store, L, b))->done ? 0 : 1;
+    red[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) *(int*)(store + L.g_count) = red[0];
+}
+
+// ------------------------------------------------------------------------------------------------------------- launches
+static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+
+int launch_reset(char* store, const Lay& L, const unsigned char* mask, hipStream_t s) {
+    hipLaunchKernelGGL(k_fpg_reset, dim3((L.B + 255) / 256), dim3(256), 0, s, store, L, mask);
+    return launched();
+}
+int launch_add_keyframes(char* store, const Lay& L, const unsigned char* key, const double* pose, const double* stamp, const unsigned char* mask,
+                         unsigned char* added, hipStream_t s) {
+    hipLaunchKernelGGL(k_fpg_add_keyframes, dim3((L.B + 63) / 64), dim3(64), 0, s, store, L, key, pose, stamp, mask, added);
+    return launched();
+}
+int launch_add_loops(char* store, const Lay& L, const unsigned char* found, const int* edge, const double* tf12, const unsigned char* mask, hipStream_t s) {
+    hipLaunchKernelGGL(k_fpg_add_loops, dim3((L.B + 63) / 64), dim3(64), 0, s, store, L, found, edge, tf12, mask);
+    return launched();
+}
+int launch_due(char* store, const Lay& L, double period, const unsigned char* key, const double* stamp, const unsigned char* mask, unsigned char* due,
+               int* n_due, hipStream_t s) {
+    hipLaunchKernelGGL(k_fpg_due, dim3(1), dim3(256), 0, s, store, L, period, key, stamp, mask, due, n_due);
+    return launched();
+}
+int launch_correct(char* store, const Lay& L, const double* pose_in, double* pose_out, const unsigned char* mask, hipStream_t s) {
+    hipLaunchKernelGGL(k_fpg_correct, dim3((L.B + 63) / 64), dim3(64), 0, s, store, L, pose_in, pose_out, mask);
+    return launched();
+}
+
+int launch_solve(char* store, const Lay& L, const Noise& noise, const DevParams& P, const unsigned char* sel, const double* stamp, int max_iters,
+                 int check_every, int lds_cap_doubles, liw_summary* summary, hipStream_t s) {
+    const int K = max_iters > 0 ? max_iters : 50;
+    const unsigned B = (unsigned)L.B;
+    const unsigned lin_blocks = (unsigned)(((long long)L.B * L.NE + 3) / 4 + ((long long)L.B * L.K + 7) / 8);
+    const unsigned asm_blocks = B * (unsigned)L.K, seg_blocks = B * (unsigned)(L.NS > 1 ? L.NS - 1 : 0);
+    // LDS for the separator systems: what the largest one of this store needs, 64 KB at the most (two work-groups per CU); a robot
+    // whose own triangle is larger than that runs from its work area
+    const int nr = 6 * L.NS, tri_max = nr * (nr + 1) / 2;
+    const int lds_doubles = tri_max <= lds_cap_doubles ? tri_max : lds_cap_doubles;
+    hipLaunchKernelGGL(k_fpg_setup, dim3(B), dim3(64), 0, s, store, L, sel);
+    hipLaunchKernelGGL(k_fpg_linearize, dim3(lin_blocks), dim3(64), 0, s, store, L, noise, P, 0);
+    hipLaunchKernelGGL(k_fpg_assemble, dim3(asm_blocks), dim3(64), 0, s, store, L);
+    for (int it = 0; it < K; ++it) {
+        hipLaunchKernelGGL(k_fpg_head, dim3(B), dim3(64), 0, s, store, L, K, stamp, summary);
+        if (seg_blocks) hipLaunchKernelGGL(k_fpg_seg_elim, dim3(seg_blocks), dim3(64), 0, s, store, L);
+        hipLaunchKernelGGL(k_fpg_reduced, dim3(B), dim3(256), sizeof(double) * (size_t)lds_doubles, s, store, L, lds_doubles);
+        if (seg_blocks) hipLaunchKernelGGL(k_fpg_backsub, dim3(seg_blocks), dim3(64), 0, s, store, L);
+        hipLaunchKernelGGL(k_fpg_decide1, dim3(B), dim3(64), 0, s, store, L, stamp, summary);
+        hipLaunchKernelGGL(k_fpg_linearize, dim3(lin_blocks), dim3(64), 0, s, store, L, noise, P, 1);
+        hipLaunchKernelGGL(k_fpg_decide2, dim3(B), dim3(64), 0, s, store, L, stamp, summary);
+        hipLaunchKernelGGL(k_fpg_assemble, dim3(asm_blocks), dim3(64), 0, s, store, L);
+        if (launched()) return -1;
+        if (check_every > 0 && (it + 1) % check_every == 0 && it + 1 < K) {
+            int left = 0;
+            hipLaunchKernelGGL(k_fpg_count, dim3(1), dim3(256), 0, s, store, L);
+            if (hipMemcpyAsync(&left, store + L.g_count, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+                return -1;
+            if (left == 0) return 0;
+        }
+    }
+    hipLaunchKernelGGL(k_fpg_head, dim3(B), dim3(64), 0, s, store, L, K, stamp, summary);   // the iteration cap (termination 4) of who is left
+    return launched();
+}
+
+}  // namespace liw_fpg_dev

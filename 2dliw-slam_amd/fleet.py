@@ -7,8 +7,9 @@ read-back of a frame.  `FleetTracker` tracks robots that were initialised elsewh
 pack_init -> INIT solve -> rebuild, or a known state) and handed to start(); `FleetTrajectory` is the whole trajectory from the first
 scan on: the per-robot INITIALIZING state machine (the is_static gate, each robot's own window, the INIT solve of the robots whose
 window is full, the restart of a failed window) in the same step as the tracking frame.  The key frames a step returns (key, pose, acc,
-n_acc) are what loop_batch.FleetLoopDetector.push takes: the fleet's key-frame store and laser loop detector.  The pose-graph solve,
-the map, non-laser key frames and the sensor-inited latch stay with the caller.  There is no CPU fallback."""
+n_acc) are what loop_batch.FleetLoopDetector.push takes: the fleet's key-frame store and laser loop detector; its result and the
+step's go to posegraph_batch.FleetBackEnd.push, the pose-graph back-end of the fleet (queue, edges, solve, map-frame correction).
+The map per robot, non-laser key frames and the sensor-inited latch stay with the caller.  There is no CPU fallback."""
 import numpy as np
 
 from .laser_batch import REF, BatchFrontEnd, track_params_struct
@@ -173,8 +174,8 @@ class FleetTrajectory(FleetTracker):
     block, has_match 1 with the pose record of an empty match, and its prior rows (none).  They are put back from a snapshot after
     the marginalisation, as the rows of a skipped robot are.
 
-    Out of scope: the pose-graph solve, the map and non-laser key frames (the key frames themselves and their loop edges are
-    loop_batch.FleetLoopDetector's), keep_window_size > 1, the imu_inited / wheel_odom_inited latch (the caller starts stepping once it
+    Out of scope: the map per robot and non-laser key frames (the key frames themselves and their loop edges are
+    loop_batch.FleetLoopDetector's, the pose-graph solve around them posegraph_batch.FleetBackEnd's), keep_window_size > 1, the imu_inited / wheel_odom_inited latch (the caller starts stepping once it
     has intervals), a C++ mirror of this driver."""
 
     def __init__(self, prm, laser_prm, track_prm, init_prm, dims, device="cuda:0", cap=256, max_corners=64, acc_cap=1024, init_iters=0):

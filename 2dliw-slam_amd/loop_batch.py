@@ -2,7 +2,8 @@
 the key / pose / acc / n_acc tensors `FleetTracker.step` / `FleetTrajectory.step` return, appends the key frames of the robots
 whose key is set to a per-robot store with their sub-map features, and runs laser_loop_detect for each of them, on torch's
 current stream and without a host loop over robots.  `loop.LoopDetector` (one robot, host glue) is its parity reference.  There is
-no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device."""
+no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device.  What `push` returns goes on to
+posegraph_batch.FleetBackEnd.push, the fleet's pose-graph back-end; the map per robot and non-laser key frames stay with the caller."""
 import ctypes as C
 
 import numpy as np
@@ -189,9 +190,10 @@ class FleetLoopDetector:
 
     def push(self, step_out, mask=None):
         """add + detect for the key frames of a FleetTracker.step / FleetTrajectory.step result.  A robot that is full gets no
-        detection for the key frame that was not stored."""
+        detection for the key frame that was not stored.  The result also carries `added`, which posegraph_batch.FleetBackEnd.push
+        takes as its key so that both stores hold the same key frames."""
         added = self.add_keyframes(step_out["key"], step_out["pose"], step_out["acc"], step_out["n_acc"], mask=mask)
-        return self.detect(added, mask=mask)
+        return dict(self.detect(added, mask=mask), added=added)
 
     # ---- inspection (synchronous)
     def _sync(self):
