@@ -70,6 +70,7 @@
 #include "../../include/liw_laser_batch.h"
 #include "liw_dual.hpp"
 #include "liw_crmath.hpp"
+#include "liw_host_common.hpp"
 
 void liw_normalize_rotation_host(double* R9);   // liw_capi.hip (params.cpp:44-54 round trip)
 
@@ -1788,13 +1789,10 @@ __global__ void __launch_bounds__(256) k_lfe_crmath(int op, int n, const double*
 
 using namespace lfe;
 
-struct liw_lfe_ctx {
+struct liw_lfe_ctx : liw_fleet_ctx_base {
     liw_laser_params prm;
     Lay L;
     DP P;
-    int device = 0;
-    bool have_device = false;
-    std::string err;
     float2* d_cs = nullptr;
     int* d_rows = nullptr;   // B ints between the two launches of liw_lfe_init_begin
     int n_rays = 0;
@@ -1803,16 +1801,6 @@ struct liw_lfe_ctx {
 };
 
 namespace {
-int fail(liw_lfe_ctx* c, int code, const char* what) {
-    if (c) c->err = what;
-    return code;
-}
-#define LFE_DEV(c)                                                                                                   \
-    do {                                                                                                             \
-        if (!(c)) return LIW_EINVAL;                                                                                 \
-        if (!(c)->have_device) return fail((c), LIW_ENODEV, "no usable gfx950 device (no CPU fallback)");             \
-        (void)hipSetDevice((c)->device);                                                                             \
-    } while (0)
 int launched(liw_lfe_ctx* c) {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LIW_OK : fail(c, LIW_EHIP, hipGetErrorString(e));
@@ -1906,16 +1894,7 @@ liw_lfe_ctx* liw_lfe_create(const liw_laser_params* prm, const liw_lfe_dims* dim
     P.h = (int)(prm->h_laser_each_scan / prm->laser_resolution + 1);
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.Til_R[i * 3 + j] = prm->T_imu_to_laser[i * 4 + j]; P.Til_t[i] = prm->T_imu_to_laser[i * 4 + 3]; }
     if (prm->normalize_extrinsics) liw_normalize_rotation_host(P.Til_R);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) {
-        hipDeviceProp_t props;
-        if (hipGetDeviceProperties(&props, device) == hipSuccess) {
-            if (std::strstr(props.gcnArchName, "gfx950") != nullptr) c->have_device = true;
-            else c->err = std::string("device is ") + props.gcnArchName + ", this library is built for gfx950 only";
-        }
-    }
-    (void)hipGetLastError();
-    if (!c->have_device && c->err.empty()) c->err = "no HIP device";
+    c->have_device = liw_probe_gfx950(device, &c->err);
     return c;
 }
 
@@ -1929,7 +1908,7 @@ void liw_lfe_destroy(liw_lfe_ctx* c) {
 const char* liw_lfe_last_error(liw_lfe_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
 
 int liw_lfe_set_geometry(liw_lfe_ctx* c, int n_rays, float angle_min, float angle_increment, float time_increment) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (n_rays <= 0 || !(angle_increment > 0)) return fail(c, LIW_EINVAL, "liw_lfe_set_geometry: n_rays > 0 and angle_increment > 0");
     // exactly the float arithmetic of liw_laser_to_points (common.cpp:22-24): float angle, cosf / sinf of the host libm
     std::vector<float2> cs(n_rays);
@@ -1948,14 +1927,14 @@ int liw_lfe_set_geometry(liw_lfe_ctx* c, int n_rays, float angle_min, float angl
 }
 
 int liw_lfe_store_reset(liw_lfe_ctx* c, void* store, const unsigned char* mask, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store) return fail(c, LIW_EINVAL, "liw_lfe_store_reset: store");
     hipLaunchKernelGGL(k_lfe_reset, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, mask);
     return launched(c);
 }
 
 int liw_lfe_ranges_to_points(liw_lfe_ctx* c, void* store, const float* ranges, const double* stamps, double* pts, double* times, int* n_pts, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!c->d_cs) return fail(c, LIW_ESTATE, "liw_lfe_ranges_to_points: no geometry (liw_lfe_set_geometry)");
     if (!ranges || !stamps || !pts || !times || !n_pts) return fail(c, LIW_EINVAL, "liw_lfe_ranges_to_points: null array");
     hipLaunchKernelGGL(k_lfe_ranges, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, ranges, c->n_rays,
@@ -1965,7 +1944,7 @@ int liw_lfe_ranges_to_points(liw_lfe_ctx* c, void* store, const float* ranges, c
 
 int liw_lfe_deskew(liw_lfe_ctx* c, double* pts, const double* times, const int* n_pts, const double* stamps, const double* linear, const double* angular,
                    void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!pts || !times || !n_pts || !stamps || !linear || !angular) return fail(c, LIW_EINVAL, "liw_lfe_deskew: null array");
     hipLaunchKernelGGL(k_lfe_deskew, dim3(blocks((size_t)c->L.B * c->L.max_points, 256)), dim3(256), 0, (hipStream_t)stream, c->L, pts, times, n_pts,
                        stamps, linear, angular);
@@ -1973,14 +1952,14 @@ int liw_lfe_deskew(liw_lfe_ctx* c, double* pts, const double* times, const int* 
 }
 
 int liw_lfe_spawn(liw_lfe_ctx* c, void* store, int slot, const double* pts, const int* n_pts, const double* times, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !pts || !n_pts || slot < 0 || slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_spawn: bad argument");
     return spawn_launch(c, store, slot, pts, n_pts, times, 0, nullptr, nullptr, stream);
 }
 
 int liw_lfe_spawn_corners(liw_lfe_ctx* c, void* store, int slot, const double* pts, const int* n_pts, const double* times, int max_corners,
                           double* corners, int* n_corners, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !pts || !n_pts || slot < 0 || slot >= c->L.slots || max_corners < 1 || !corners || !n_corners)
         return fail(c, LIW_EINVAL, "liw_lfe_spawn_corners: bad argument");
     return spawn_launch(c, store, slot, pts, n_pts, times, max_corners, corners, n_corners, stream);
@@ -1988,7 +1967,7 @@ int liw_lfe_spawn_corners(liw_lfe_ctx* c, void* store, int slot, const double* p
 
 int liw_lfe_corners_to_world(liw_lfe_ctx* c, void* store, int max_corners, const double* corners, const int* n_corners, const double* pose,
                              const unsigned char* mask, const unsigned char* clear, int acc_cap, double* acc, int* n_acc, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (max_corners < 1 || !corners || !n_corners || !pose || acc_cap < 1 || !acc || !n_acc) return fail(c, LIW_EINVAL, "liw_lfe_corners_to_world: bad argument");
     hipLaunchKernelGGL(k_lfe_corners_world, dim3(blocks(c->L.B, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, store, c->L, c->P, max_corners, corners,
                        n_corners, pose, mask, clear, acc_cap, acc, n_acc);
@@ -1997,7 +1976,7 @@ int liw_lfe_corners_to_world(liw_lfe_ctx* c, void* store, int max_corners, const
 
 int liw_lfe_match(liw_lfe_ctx* c, void* store, int slot1, int slot2, const double* pose1, const double* pose2, int kk, int cap, int* count, double* recs,
                   int* idx1, int* idx2, double* match_pose, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !pose2 || !count || !recs || !match_pose || cap < 1 || kk < 0 || slot2 < 0 || slot2 >= c->L.slots ||
         !(slot1 == LIW_LFE_REF || (slot1 >= 0 && slot1 < c->L.slots)) || (slot1 != LIW_LFE_REF && !pose1))
         return fail(c, LIW_EINVAL, "liw_lfe_match: bad argument");
@@ -2007,13 +1986,13 @@ int liw_lfe_match(liw_lfe_ctx* c, void* store, int slot1, int slot2, const doubl
 }
 
 int liw_lfe_add_scan(liw_lfe_ctx* c, void* store, int src_slot, const double* pose, const unsigned char* mask, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !pose || src_slot < 0 || src_slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_add_scan: bad argument");
     return add_scan_launch(c, store, src_slot, 1, false, pose, 6LL, 0LL, mask, nullptr, stream);
 }
 
 int liw_lfe_add_scan_flags(liw_lfe_ctx* c, void* store, int src_slot, const double* pose, const unsigned char* mask, unsigned char* flags, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !pose || !flags || src_slot < 0 || src_slot >= c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_add_scan_flags: bad argument");
     return add_scan_launch(c, store, src_slot, 1, false, pose, 6LL, 0LL, mask, flags, stream);
 }
@@ -2026,7 +2005,7 @@ int liw_lfe_add_scan_path(liw_lfe_ctx* c) {
 
 int liw_lfe_pack_track(liw_lfe_ctx* c, int n, int frame, int cap, const int* count, const double* recs, const double* match_pose, int L_cap,
                        int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (n < 1 || frame < 0 || frame >= n || cap < 1 || L_cap < 0 || !count || !recs || !match_pose || !laser_off || !laser_frame || !laser_pts ||
         !match_pose_out || !has_match)
         return fail(c, LIW_EINVAL, "liw_lfe_pack_track: bad argument");
@@ -2047,7 +2026,7 @@ int liw_lfe_pack_track(liw_lfe_ctx* c, int n, int frame, int cap, const int* cou
 int liw_lfe_match_front(liw_lfe_ctx* c, void* store, int front_slot, int first_slot, int F, const double* pose_front, const double* poses,
                         long long robot_stride, long long frame_stride, int kk, int cap, int* count, double* recs, int* idx1, int* idx2,
                         double* match_pose, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !pose_front || !poses || !count || !recs || !match_pose || cap < 1 || kk < 0 || F < 1 || first_slot < 0 ||
         (long long)first_slot + F > c->L.slots || front_slot < 0 || front_slot >= c->L.slots)
         return fail(c, LIW_EINVAL, "liw_lfe_match_front: bad argument");
@@ -2062,7 +2041,7 @@ int liw_lfe_match_front(liw_lfe_ctx* c, void* store, int front_slot, int first_s
 int liw_lfe_pack_init(liw_lfe_ctx* c, int n, int cap, const int* count, const double* recs, const double* match_pose, const double* pose_front,
                       int L_cap, int* laser_off, int* laser_frame, double* laser_pts, double* match_pose_out, unsigned char* has_match,
                       unsigned char* init_ok, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (n < 2 || cap < 1 || L_cap < 0 || !count || !recs || !match_pose || !pose_front || !laser_off || !laser_frame || !laser_pts ||
         !match_pose_out || !has_match)
         return fail(c, LIW_EINVAL, "liw_lfe_pack_init: bad argument");
@@ -2084,7 +2063,7 @@ int liw_lfe_pack_init(liw_lfe_ctx* c, int n, int cap, const int* count, const do
 
 int liw_lfe_rebuild(liw_lfe_ctx* c, void* store, int first_slot, int F, const double* poses, long long robot_stride, long long frame_stride,
                     const unsigned char* mask, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !poses || F < 1 || first_slot < 0 || (long long)first_slot + F > c->L.slots) return fail(c, LIW_EINVAL, "liw_lfe_rebuild: bad argument");
     return add_scan_launch(c, store, first_slot, F, true, poses, robot_stride, frame_stride, mask, nullptr, stream);
 }
@@ -2108,7 +2087,7 @@ TP track_tp(const liw_lfe_track_params* tp) {   // the extrinsic as liw_lie_from
 
 int liw_lfe_track_init(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* track, const double* x, long long robot_stride, const double* angular_local,
                        const unsigned char* mask, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!tp || !track || !x || robot_stride < 1) return fail(c, LIW_EINVAL, "liw_lfe_track_init: bad argument");
     hipLaunchKernelGGL(k_lfe_track_init, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, c->L.B, track, x, robot_stride, angular_local, mask);
     return launched(c);
@@ -2117,7 +2096,7 @@ int liw_lfe_track_init(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* tra
 int liw_lfe_track_begin(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* track, double* x, const double* imu_X, const double* imu_Dt,
                         const double* wheel_T, const double* stamps, const unsigned char* mask, double* linear, double* angular, double* pose_new,
                         unsigned char* skip, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!tp || !track || !x || !imu_X || !imu_Dt || !wheel_T || !stamps || !linear || !angular || !pose_new || !skip)
         return fail(c, LIW_EINVAL, "liw_lfe_track_begin: null argument");
     hipLaunchKernelGGL(k_lfe_track_begin, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, c->L.B, c->P, track_tp(tp), track, x, imu_X, imu_Dt,
@@ -2127,7 +2106,7 @@ int liw_lfe_track_begin(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* tr
 
 int liw_lfe_track_end(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* track, const void* store, int slot, const double* x, const int* count,
                       const unsigned char* mask, unsigned char* key, double* pose, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!tp || !track || !store || !x || !count || !key || !pose || slot < 0 || slot >= c->L.slots)
         return fail(c, LIW_EINVAL, "liw_lfe_track_end: bad argument");
     hipLaunchKernelGGL(k_lfe_track_end, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, store, c->L, c->P, track_tp(tp), track, slot, x, count,
@@ -2136,7 +2115,7 @@ int liw_lfe_track_end(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* trac
 }
 
 int liw_lfe_track_get(liw_lfe_ctx* c, const void* track, int robot, double* tf12, double* angular3, double* stamp, int* counters) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!track || robot < 0 || robot >= c->L.B) return fail(c, LIW_EINVAL, "liw_lfe_track_get: bad argument");
     Trk t;
     if (hipMemcpy(&t, (const char*)track + (size_t)robot * kTrkBytes, sizeof t, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, LIW_EHIP, "hipMemcpy");
@@ -2168,14 +2147,14 @@ IP init_ip(const liw_lfe_track_params* tp, const liw_lfe_init_params* ip) {
 }  // namespace
 
 int liw_lfe_init_reset(liw_lfe_ctx* c, const liw_lfe_track_params* tp, void* init, const unsigned char* mask, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!tp || !init) return fail(c, LIW_EINVAL, "liw_lfe_init_reset: bad argument");
     hipLaunchKernelGGL(k_lfe_init_reset, dim3(blocks(c->L.B, 256)), dim3(256), 0, (hipStream_t)stream, c->L.B, init_ip(tp, nullptr), init, mask);
     return launched(c);
 }
 
 int liw_lfe_init_get(liw_lfe_ctx* c, const void* init, int robot, int* status, int* n_frames, double* state15, double* angular3, int* counters) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!init || robot < 0 || robot >= c->L.B) return fail(c, LIW_EINVAL, "liw_lfe_init_get: bad argument");
     Ini r;
     if (hipMemcpy(&r, (const char*)init + (size_t)robot * kIniBytes, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, LIW_EHIP, "hipMemcpy");
@@ -2194,7 +2173,7 @@ int liw_lfe_init_begin(liw_lfe_ctx* c, const liw_lfe_track_params* tp, const liw
                        const double* imu_J, const double* imu_sqrtP, const double* imu_Dt, const double* wheel_T, const double* wheel_sqrtP,
                        const unsigned char* mask, double* x_init, double* w_imu_X, double* w_imu_J, double* w_imu_sqrtP, double* w_imu_Dt,
                        double* w_wheel_T, double* w_wheel_sqrtP, unsigned char* drop, int* slot_of, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!tp || !ip || !init || !imu_X || !imu_J || !imu_sqrtP || !imu_Dt || !wheel_T || !wheel_sqrtP || !x_init || !w_imu_X || !w_imu_J ||
         !w_imu_sqrtP || !w_imu_Dt || !w_wheel_T || !w_wheel_sqrtP || !drop || !slot_of)
         return fail(c, LIW_EINVAL, "liw_lfe_init_begin: null argument");
@@ -2211,7 +2190,7 @@ int liw_lfe_init_begin(liw_lfe_ctx* c, const liw_lfe_track_params* tp, const liw
 }
 
 int liw_lfe_slot_copy(liw_lfe_ctx* c, void* store, const int* dst_slot, const unsigned char* mask, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!store || !dst_slot) return fail(c, LIW_EINVAL, "liw_lfe_slot_copy: null argument");
     if (((size_t)store & 15) != 0) return fail(c, LIW_EINVAL, "liw_lfe_slot_copy: the store must be 16-byte aligned");
     hipLaunchKernelGGL(k_lfe_slot_copy, dim3(c->L.B), dim3(256), 0, (hipStream_t)stream, store, c->L, dst_slot, mask);
@@ -2220,7 +2199,7 @@ int liw_lfe_slot_copy(liw_lfe_ctx* c, void* store, const int* dst_slot, const un
 
 int liw_lfe_init_select(liw_lfe_ctx* c, const liw_lfe_init_params* ip, const void* init, unsigned char* ready, int* sel, int* n_sel, int* R_host,
                         void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!ip || !init || !ready || !sel || !n_sel || ip->slide_window_size < 2) return fail(c, LIW_EINVAL, "liw_lfe_init_select: bad argument");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_lfe_init_select, dim3(1), dim3(1024), 0, s, c->L.B, ip->slide_window_size, init, ready, sel, n_sel);
@@ -2232,7 +2211,7 @@ int liw_lfe_init_select(liw_lfe_ctx* c, const liw_lfe_init_params* ip, const voi
 int liw_lfe_pack_init_sel(liw_lfe_ctx* c, int R, const int* sel, int n, int cap, const int* count, const double* recs, const double* match_pose,
                           const double* pose_front, long long front_stride, int L_cap, int* laser_off, int* laser_frame, double* laser_pts,
                           double* match_pose_out, unsigned char* has_match, unsigned char* init_ok, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (R < 1 || R > c->L.B || !sel || n < 2 || cap < 1 || L_cap < 0 || front_stride < 6 || !count || !recs || !match_pose || !pose_front || !laser_off ||
         !laser_frame || !laser_pts || !match_pose_out || !has_match)
         return fail(c, LIW_EINVAL, "liw_lfe_pack_init_sel: bad argument");
@@ -2254,7 +2233,7 @@ int liw_lfe_pack_init_sel(liw_lfe_ctx* c, int R, const int* sel, int n, int cap,
 
 int liw_lfe_init_commit(liw_lfe_ctx* c, const liw_lfe_track_params* tp, const liw_lfe_init_params* ip, void* init, void* track, int R, const int* sel,
                         const unsigned char* init_ok, const double* x_sol, double* x_init, double* x_track, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (!tp || !ip || !init || !track || R < 1 || R > c->L.B || !sel || !init_ok || !x_sol || !x_init || !x_track || ip->slide_window_size < 2)
         return fail(c, LIW_EINVAL, "liw_lfe_init_commit: bad argument");
     hipLaunchKernelGGL(k_lfe_init_commit, dim3(blocks(R, 256)), dim3(256), 0, (hipStream_t)stream, R, init_ip(tp, ip), init, track, sel, init_ok, x_sol, x_init,
@@ -2263,7 +2242,7 @@ int liw_lfe_init_commit(liw_lfe_ctx* c, const liw_lfe_track_params* tp, const li
 }
 
 int liw_lfe_crmath_eval(liw_lfe_ctx* c, int op, int n, const double* a, const double* b, double* out, void* stream) {
-    LFE_DEV(c);
+    LIW_FLEET_DEV(c);
     if (op < 0 || op > 2 || n < 0 || !a || !out || (op == 2 && !b)) return fail(c, LIW_EINVAL, "liw_lfe_crmath_eval: bad argument");
     if (n == 0) return LIW_OK;
     hipLaunchKernelGGL(k_lfe_crmath, dim3(blocks((size_t)n, 256)), dim3(256), 0, (hipStream_t)stream, op, n, a, b, out);

@@ -1,4 +1,5 @@
-// k_loop.hpp — interface between the loop detector's host code (liw_loop.cpp) and its kernels (k_loop.hip).
+// k_loop.hpp — interface between the loop detector's host code (liw_loop.cpp) and its kernels (k_loop.hip); the device bodies that
+// k_loop.hip shares with the fleet's k_loop_batch.hip are in k_loop_dev.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -24,28 +25,16 @@ struct Geom {                    // store strides and the matching constants
 
 constexpr double kPi = 3.14159265358979323846;
 
-// ---- row routines shared by k_loop.hip and k_loop_batch.hip (both include this header under fp contract(off))
-// match_des's bin of a pair: wrap the angle difference to [-pi, pi), truncate toward zero, shift by nAngle / 2.  Clamped to
-// the histogram (finite inputs never leave it: |bin - orign| <= int(pi / a_res) < orign).
-__device__ __forceinline__ int angle_bin(double a1, double a2, double a_res, int orign, int nb) {
-    double d = a1 - a2;
-    if (d >= kPi) d -= kPi * 2;
-    else if (d < -kPi) d += kPi * 2;
-    const double q = d / a_res;
-    int b = (q == q) ? (int)q : 0;
-    b += orign;
-    return b < 0 ? 0 : (b >= nb ? nb - 1 : b);
+// The draws of the query rows (include/liw_loop.h): one function for the host's make_cand and the fleet's k_floop_gates.
+__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
 }
-
-// first index in keys[0, n) with keys[e] >= v (keys ascending)
-__device__ __forceinline__ int lower_bound_u32(const uint32_t* keys, int n, uint32_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+// draw d of query key frame q against candidate key frame c: a row of the query's n1
+__host__ __device__ inline int draw_row(uint64_t seed, int q, int c, int d, int n1) {
+    return (int)(splitmix64(seed ^ ((uint64_t)q << 40) ^ ((uint64_t)c << 8) ^ (uint64_t)d) % (uint64_t)n1);
 }
 
 // one wave per point of slot `slot`: rows of (dij << 12 | j) keys, aij and quick_des; inv[slot] = 1 on a dij overflow

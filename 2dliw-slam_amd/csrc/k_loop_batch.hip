@@ -6,15 +6,16 @@
 //                     kept point within 5 d_res and blends only within d_res / 2; every point in front of the first hit is farther
 //                     than 5 d_res, so per corner the lanes test the kept points (in LDS) 64 at a time, a ballot finds the
 //                     first hit, and its lane blends if it is also within d_res / 2; no hit appends.  Serial over corners.
-//   k_floop_describe  one wave per (robot, point): k_loop_describe's body (dij, aij, bitonic sort of dij << 12 | j, quick_des).
+//   k_floop_describe  one wave per (robot, point): describe_point of k_loop_dev.hpp, the body k_loop_describe runs (dij, aij, bitonic
+//                     sort of dij << 12 | j, quick_des), at the fleet's point stride of 3 doubles.
 // liw_floop_detect:
 //   k_floop_gates     one wave per robot, a lane per candidate i = 0, s, ...: the null / points / origin-distance gates, the five
 //                     draws (splitmix64, a 64-bit modulo), the rank among the robot's launched candidates by ballot prefix.
 //   k_floop_scan      one work-group: exclusive scan of the per-robot counts -> the pair list's bases, the pair total, max n2.
 //   k_floop_pairs     a lane per (robot, candidate): the compact pair list in robot-then-candidate order.
-//   k_floop_match     k_loop_match's scheme (16 rows per work-group, the drawn query row staged once) on a fixed grid that
-//                     strides over (pair, draw, 16-row) items.
-//   k_floop_select    one wave per pair: k_loop_select's body.
+//   k_floop_match     match_rows of k_loop_dev.hpp, the body k_loop_match runs (16 rows per work-group, the drawn query row staged
+//                     once), on a fixed grid that strides over (pair, draw, 16-row) items.
+//   k_floop_select    a wave strides over pairs: select_best of k_loop_dev.hpp, the body k_loop_select runs.
 //   k_floop_icp       a lane per pair above the threshold: the planar closed-form ICP over the list in list order, the
 //                     T_imu_to_wheel conjugation, the tf gate through log_SO3, all with liw_dual.hpp and liw_crmath.hpp.
 //   k_floop_choose    one wave per robot: the lowest passing candidate, the stats.
@@ -27,15 +28,16 @@
 
 #include "../../include/liw_loop_batch.h"
 #include "k_loop_batch.hpp"
+#include "k_loop_dev.hpp"
 #include "liw_crmath.hpp"
 #include "liw_dual.hpp"
 
 namespace liw_floop_dev {
 
-using liw_loop_dev::angle_bin;
-using liw_loop_dev::kPi;
+using liw_loop_dev::describe_point;
 using liw_loop_dev::kRowsPerBlock;
-using liw_loop_dev::lower_bound_u32;
+using liw_loop_dev::match_rows;
+using liw_loop_dev::select_best;
 
 // A double whose sin / cos / atan2 are the correctly rounded ones of liw_crmath.hpp (as the tracking glue's): make_tf of a key
 // frame's pose is then the host's for all but the arguments where the host libm itself is not correctly rounded.
@@ -60,8 +62,6 @@ __host__ __device__ inline CR dfloor(const CR& a) { return CR(floor(a.v)); }
 using IsoD = liw::Iso<double>;
 
 __device__ __forceinline__ char* robot_region(char* store, const Lay& L, int b) { return store + (size_t)b * L.robot_bytes; }
-// feature slot of key frame k: a candidate slot when k % s == 0, else the one query slot (which holds the newest such k only)
-__device__ __forceinline__ int feature_slot(const Lay& L, int k) { return k % L.step == 0 ? k / L.step : L.NC; }
 __device__ __forceinline__ bool robot_on(const unsigned char* a, int b) { return !a || a[b] != 0; }
 
 __device__ __forceinline__ IsoD load_iso(const double* T) { return liw::cast_iso<double>(T, T + 9); }
@@ -70,13 +70,6 @@ __device__ __forceinline__ IsoD identity_iso() {
     for (int k = 0; k < 9; ++k) r.R.m[k] = (k % 4 == 0) ? 1.0 : 0.0;
     r.t = liw::V3<double>(0.0, 0.0, 0.0);
     return r;
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 __global__ __launch_bounds__(256) void k_floop_reset(char* store, Lay L, const unsigned char* __restrict__ mask) {
@@ -197,54 +190,11 @@ __global__ __launch_bounds__(64) void k_floop_describe(char* store, Lay L, Geom 
     const int kf = ((const int*)R)[0] - 1;
     const int fs = feature_slot(L, kf);
     const double* pts = (const double*)(R + L.r_pts) + (size_t)fs * L.P * 3;
-    const int m = n - 1;
-    int N2 = 1;
-    while (N2 < m) N2 <<= 1;
-    double* a_j = (double*)smem;                    // [n]  aij by j
-    uint64_t* q = (uint64_t*)(a_j + n);             // [W]
-    uint32_t* kk = (uint32_t*)(q + g.W);            // [N2]
     bool bad = false;
     for (int i = i0; i < n; i += gx) {
-        for (int w = lane; w < g.W; w += 64) q[w] = 0;
-        __syncthreads();
-        const double xi = pts[3 * i], yi = pts[3 * i + 1];
-        for (int j = lane; j < n; j += 64) {
-            if (j == i) { a_j[j] = 0.0; continue; }
-            const double vx = pts[3 * j] - xi, vy = pts[3 * j + 1] - yi;
-            const double nrm = sqrt(vx * vx + vy * vy);
-            const double c = acos(vx / nrm);
-            a_j[j] = vy > 0 ? c : kPi * 2 - c;
-            const double r = nrm / d_res + 0.5;
-            uint32_t dij;
-            if (!(r < 1048575.0)) { bad = true; dij = 0xFFFFFu; }
-            else dij = (uint32_t)(int)r;
-            kk[j < i ? j : j - 1] = dij << 12 | (uint32_t)j;
-            if ((int)(dij >> 6) < g.W) atomicOr((unsigned long long*)&q[dij >> 6], 1ull << (dij & 63));
-        }
-        for (int e = m + lane; e < N2; e += 64) kk[e] = 0xFFFFFFFFu;
-        __syncthreads();
-        for (int k = 2; k <= N2; k <<= 1) {
-            for (int jj = k >> 1; jj > 0; jj >>= 1) {
-                for (int t = lane; t < N2; t += 64) {
-                    const int u = t ^ jj;
-                    if (u > t) {
-                        const uint32_t a = kk[t], c = kk[u];
-                        if ((a > c) == ((t & k) == 0)) { kk[t] = c; kk[u] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
         const size_t row = (size_t)fs * L.P + i;
-        uint32_t* ko = (uint32_t*)(R + L.r_keys) + row * L.P;
-        double* ao = (double*)(R + L.r_aij) + row * L.P;
-        for (int e = lane; e < m; e += 64) {
-            const uint32_t kv = kk[e];
-            ko[e] = kv;
-            ao[e] = a_j[kv & 0xFFFu];
-        }
-        uint64_t* qo = (uint64_t*)(R + L.r_quick) + row * L.W;
-        for (int w = lane; w < g.W; w += 64) qo[w] = q[w];
+        bad |= describe_point<3>(pts, n, i, g, d_res, smem, (uint32_t*)(R + L.r_keys) + row * L.P, (double*)(R + L.r_aij) + row * L.P,
+                                 (uint64_t*)(R + L.r_quick) + row * L.W);
         __syncthreads();
     }
     if (bad) ((int*)(R + L.r_state))[kf] = LIW_LOOP_DIJ_OVERFLOW;   // every writer stores the same value
@@ -298,7 +248,7 @@ __global__ __launch_bounds__(64) void k_floop_gates(char* store, Lay L, Prm p, c
                 if (ok) {
                     int r0 = -1, r1 = -1, r2 = -1, r3 = -1, r4 = -1;
                     for (int d = 0; d < kDraws; ++d) {
-                        int row = (int)(splitmix64(p.seed ^ ((uint64_t)q << 40) ^ ((uint64_t)i << 8) ^ (uint64_t)d) % (uint64_t)n1);
+                        int row = liw_loop_dev::draw_row(p.seed, q, i, d, n1);
                         if (row == r0 || row == r1 || row == r2 || row == r3) row = -1;
                         if (d == 0) r0 = row; else if (d == 1) r1 = row; else if (d == 2) r2 = row; else if (d == 3) r3 = row; else r4 = row;
                         tasks += row >= 0 ? n2 : 0;
@@ -379,8 +329,6 @@ __global__ __launch_bounds__(256) void k_floop_match(char* store, Lay L, Geom g)
     const int* hdr = (const int*)(store + L.f_hdr);
     const int npairs = hdr[0], rb = (hdr[1] + kRowsPerBlock - 1) / kRowsPerBlock;
     const long long items = (long long)npairs * kDraws * rb;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int MW = (g.nb + 31) >> 5;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int pi = (int)(item / (kDraws * rb)), rem = (int)(item - (long long)pi * kDraws * rb);
         const int d = rem / rb, r0 = (rem - d * rb) * kRowsPerBlock;
@@ -389,150 +337,30 @@ __global__ __launch_bounds__(256) void k_floop_match(char* store, Lay L, Geom g)
         if (r0 >= n2) continue;
         int2* out = (int2*)(store + L.f_tres) + ((size_t)pi * kDraws + d) * L.P;
         if (row1 < 0) {   // a repeated draw: no task
-            for (int r = r0 + tid; r < n2 && r < r0 + kRowsPerBlock; r += blockDim.x) out[r] = make_int2(0, 0);
+            for (int r = r0 + threadIdx.x; r < n2 && r < r0 + kRowsPerBlock; r += blockDim.x) out[r] = make_int2(0, 0);
             continue;
         }
         const char* R = store + (size_t)c->robot * L.robot_bytes;
         const uint32_t* keys = (const uint32_t*)(R + L.r_keys);
         const double* aij = (const double*)(R + L.r_aij);
         const uint64_t* quick = (const uint64_t*)(R + L.r_quick);
-        const int m1 = n1 - 1, m2 = n2 - 1;
-        double* qa = (double*)smem;                       // [m1] aij of the drawn query row
-        uint32_t* qk = (uint32_t*)(qa + m1);              // [m1] its keys
-        char* wbase = (char*)(qk + m1) + (size_t)wave * ((size_t)g.nb * 8 + (size_t)MW * 64 * 4);
-        int* cnt = (int*)wbase;                           // [nb]  distinct m per bin
-        uint32_t* reach = (uint32_t*)(cnt + g.nb);        // [nb]  max of m << 12 | (4095 - k)
-        uint32_t* mask = reach + g.nb;                    // [MW][64] bins the current m of each lane has hit
         const size_t qrow = (size_t)feature_slot(L, c->query) * L.P + row1;
         const size_t cslot = (size_t)feature_slot(L, c->cand) * L.P;
-        for (int e = tid; e < m1; e += blockDim.x) {
-            qk[e] = keys[qrow * L.P + e];
-            qa[e] = aij[qrow * L.P + e];
-        }
-        const uint64_t* q1 = quick + qrow * L.W;
-        __syncthreads();
-        for (int it = 0; it < kRowsPerBlock / 4; ++it) {
-            const int r = r0 + it * 4 + wave;
-            const bool active = r < n2;                   // wave-uniform
-            for (int bb = lane; bb < g.nb; bb += 64) { cnt[bb] = 0; reach[bb] = 0; }
-            __syncthreads();
-            bool pass = false;
-            const size_t crow = cslot + (active ? r : 0);
-            if (active) {
-                const uint64_t* q2 = quick + crow * L.W;
-                int pc = 0;
-                for (int w = lane; w < g.W; w += 64) pc += __popcll(q1[w] & q2[w]);
-                for (int o = 32; o > 0; o >>= 1) pc += __shfl_xor(pc, o, 64);
-                pass = pc >= g.thr;
-                if (pass) {
-                    const uint32_t* ck = keys + crow * L.P;
-                    const double* ca = aij + crow * L.P;
-                    for (int m = lane; m < m1; m += 64) {
-                        const uint32_t dij = qk[m] >> 12;
-                        const int lo = lower_bound_u32(ck, m2, dij << 12), hi = lower_bound_u32(ck, m2, (dij + 1) << 12);
-                        if (lo >= hi) continue;
-                        for (int w = 0; w < MW; ++w) mask[w * 64 + lane] = 0;
-                        const double a1 = qa[m];
-                        for (int k = lo; k < hi; ++k) {
-                            const int bn = angle_bin(a1, ca[k], g.a_res, g.orign, g.nb);
-                            const uint32_t bit = 1u << (bn & 31);
-                            uint32_t* mw = &mask[(bn >> 5) * 64 + lane];
-                            if (*mw & bit) continue;   // this m is already in bin bn: the has-used check
-                            *mw |= bit;
-                            atomicAdd(&cnt[bn], 1);
-                            atomicMax(&reach[bn], (uint32_t)m << 12 | (uint32_t)(4095 - k));
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (active) {
-                uint64_t best = 0;
-                for (int bb = lane; bb < g.nb; bb += 64) {
-                    const int nc = cnt[bb];
-                    if (nc <= 0) continue;
-                    const uint32_t rv = reach[bb];
-                    const uint32_t rt = (rv & ~0xFFFu) | (4095u - (rv & 0xFFFu));
-                    const uint64_t v = (uint64_t)nc << 40 | (uint64_t)(0xFFFFFFu - rt) << 16 | (uint64_t)bb;
-                    best = v > best ? v : best;
-                }
-                for (int o = 32; o > 0; o >>= 1) {
-                    const uint64_t x = __shfl_xor(best, o, 64);
-                    best = x > best ? x : best;
-                }
-                if (lane == 0) {
-                    const int nc = (int)(best >> 40);
-                    out[r] = make_int2(nc ? nc + 1 : 0, (nc ? (int)(best & 0xFFFF) : 0) | (pass ? 1 << 16 : 0));
-                }
-            }
-            __syncthreads();
-        }
+        match_rows(n1, n2, r0, keys + qrow * L.P, aij + qrow * L.P, quick + qrow * L.W, keys + cslot * L.P, aij + cslot * L.P, quick + cslot * L.W, g,
+                   smem, out);
     }
 }
 
 __global__ __launch_bounds__(64) void k_floop_select(char* store, Lay L, Geom g) {
     const int npairs = ((const int*)(store + L.f_hdr))[0];
-    const int lane = threadIdx.x;
     for (int pi = blockIdx.x; pi < npairs; pi += gridDim.x) {
-        const Pair* c = (const Pair*)(store + L.f_pairs) + pi;
-        const int n1 = c->n1, n2 = c->n2;
-        const int2* tr = (const int2*)(store + L.f_tres) + (size_t)pi * kDraws * L.P;
-        uint64_t best = 0;
-        int npass = 0;
-        const int ntask = kDraws * n2;
-        for (int t = lane; t < ntask; t += 64) {
-            const int d = t / n2, r = t - d * n2;
-            if (c->rows[d] < 0) continue;
-            const int2 v = tr[(size_t)d * L.P + r];
-            npass += (v.y >> 16) & 1;
-            if (v.x > 0) {
-                const uint64_t kv = (uint64_t)v.x << 32 | (uint64_t)(0xFFFFFFFFu - (uint32_t)t);
-                best = kv > best ? kv : best;
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint64_t x = __shfl_xor(best, o, 64);
-            best = x > best ? x : best;
-            npass += __shfl_xor(npass, o, 64);
-        }
-        const int size = (int)(best >> 32);
-        int* sm = (int*)(store + L.f_summary) + (size_t)pi * 8;
-        if (size == 0) {
-            if (lane == 0) { sm[0] = 0; sm[1] = -1; sm[2] = -1; sm[3] = -1; sm[4] = npass; sm[5] = 0; }
-            continue;
-        }
-        const int t = (int)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFu));
-        const int d = t / n2, r = t - d * n2;
-        const int bin = tr[(size_t)d * L.P + r].y & 0xFFFF;
-        int len = 0;
-        if (size > g.thr) {
-            const char* R = store + (size_t)c->robot * L.robot_bytes;
-            const int row1 = c->rows[d];
-            const size_t qrow = (size_t)feature_slot(L, c->query) * L.P + row1, crow = (size_t)feature_slot(L, c->cand) * L.P + r;
-            const uint32_t* qk = (const uint32_t*)(R + L.r_keys) + qrow * L.P;
-            const double* qa = (const double*)(R + L.r_aij) + qrow * L.P;
-            const uint32_t* ck = (const uint32_t*)(R + L.r_keys) + crow * L.P;
-            const double* ca = (const double*)(R + L.r_aij) + crow * L.P;
-            int* Ls = (int*)(store + L.f_lists) + (size_t)pi * L.P * 2;
-            if (lane == 0) { Ls[0] = row1; Ls[1] = r; }
-            len = 1;
-            const int m1 = n1 - 1, m2 = n2 - 1;
-            for (int m0 = 0; m0 < m1; m0 += 64) {
-                const int m = m0 + lane;
-                int kk = -1;
-                if (m < m1) {
-                    const uint32_t dij = qk[m] >> 12;
-                    const int lo = lower_bound_u32(ck, m2, dij << 12), hi = lower_bound_u32(ck, m2, (dij + 1) << 12);
-                    for (int k = lo; k < hi; ++k)
-                        if (angle_bin(qa[m], ca[k], g.a_res, g.orign, g.nb) == bin) { kk = k; break; }
-                }
-                const unsigned long long hit = __ballot(kk >= 0);
-                const int pos = len + __popcll(hit & ((1ull << lane) - 1ull));
-                if (kk >= 0 && pos < L.P) { Ls[pos * 2] = (int)(qk[m] & 0xFFFu); Ls[pos * 2 + 1] = (int)(ck[kk] & 0xFFFu); }
-                len += __popcll(hit);
-            }
-        }
-        if (lane == 0) { sm[0] = size; sm[1] = d; sm[2] = r; sm[3] = bin; sm[4] = npass; sm[5] = len; }
+        const Pair* c = (const Pair*)(store + L.f_pairs) + pi;   // read through the pointer, as Cand in k_loop.hip
+        const char* R = store + (size_t)c->robot * L.robot_bytes;
+        const size_t qs = (size_t)feature_slot(L, c->query) * L.P * L.P, cs = (size_t)feature_slot(L, c->cand) * L.P * L.P;
+        const uint32_t* keys = (const uint32_t*)(R + L.r_keys);
+        const double* aij = (const double*)(R + L.r_aij);
+        select_best(c->rows, c->n1, c->n2, (const int2*)(store + L.f_tres) + (size_t)pi * kDraws * L.P, keys + qs, aij + qs, keys + cs, aij + cs, g,
+                    (int*)(store + L.f_summary) + (size_t)pi * 8, (int*)(store + L.f_lists) + (size_t)pi * L.P * 2);
     }
 }
 

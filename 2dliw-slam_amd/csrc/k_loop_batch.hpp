@@ -17,6 +17,9 @@ struct Lay {                     // the store: byte offsets inside a robot regio
     size_t f_hdr, f_work, f_cnt, f_base, f_cmax, f_pre, f_pairs, f_tres, f_summary, f_lists, f_res, bytes;
 };
 
+// feature slot of key frame k: a candidate slot when k % s == 0, else the one query slot (which holds the newest such k only)
+__host__ __device__ inline int feature_slot(const Lay& L, int k) { return k % L.step == 0 ? k / L.step : L.NC; }
+
 struct Prm {
     Geom g;
     double d_res, max_dis, max_tf_p, max_tf_q;

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "liw_host_common.hpp"
 #include "liw_kernels.hpp"
 
 using namespace liw;
@@ -230,7 +231,6 @@ int liw_get_extrinsics(const liw_ctx* c, double* A, double* Bm) {
 }
 
 // ------------------------------------------------------------------------------------------ workspace
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct FullLayout {
     size_t PL[2], PI[2], PW[2], PG[2], CS[2], x_cand, group_off, lm, solve_ws, info, history, active, imu_pk, imu_pk_bad, bytes;
 };

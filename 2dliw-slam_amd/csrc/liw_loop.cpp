@@ -18,6 +18,7 @@
 #include "../../include/liw_lie.h"
 #include "../../include/liw_loop.h"
 #include "k_loop.hpp"
+#include "liw_host_common.hpp"
 
 struct liw_ctx;
 hipStream_t liw_ctx_stream(liw_ctx* c);
@@ -35,8 +36,6 @@ constexpr double kPi = 3.14159265358979323846;
 struct Layout {
     size_t keys, aij, quick, inv, pts, cands, tres, summary, lists, bytes;
 };
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int check_params(const liw_loop_params* p, int* W, int* nAngle) {
     if (!p || !(p->a_res > 0) || !(p->d_res > 0) || !std::isfinite(p->a_res) || !std::isfinite(p->d_res)) return LIW_EINVAL;
@@ -65,13 +64,6 @@ int layout(const liw_loop_params* p, const liw_loop_dims* d, Layout* L) {
     L->lists = o; o = al256(o + K * P * 8);
     L->bytes = o;
     return LIW_OK;
-}
-
-uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 struct KF {
@@ -128,9 +120,9 @@ Cand make_cand(const liw_loop* h, int q, int c) {
     Cand x{};
     x.slot = c;
     x.n2 = (int)h->kfs[c].points.size() / 3;
-    const uint64_t n1 = h->kfs[q].points.size() / 3;
+    const int n1 = (int)h->kfs[q].points.size() / 3;
     for (int d = 0; d < kDraws; ++d) {
-        const int row = (int)(splitmix64(h->p.seed ^ ((uint64_t)q << 40) ^ ((uint64_t)c << 8) ^ (uint64_t)d) % n1);
+        const int row = liw_loop_dev::draw_row(h->p.seed, q, c, d, n1);
         bool rep = false;
         for (int e = 0; e < d; ++e) rep |= x.rows[e] == row;
         x.rows[d] = rep ? -1 : row;

@@ -11,13 +11,12 @@
 #include "../../include/liw_lie.h"
 #include "../../include/liw_loop_batch.h"
 #include "k_loop_batch.hpp"
+#include "liw_host_common.hpp"
 
 namespace {
 
 using liw_floop_dev::Lay;
 using liw_floop_dev::Prm;
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 bool make_lay(const liw_loop_params* p, const liw_floop_dims* d, Lay* L, int* nAngle) {
     int W = 0, na = 0;
@@ -59,30 +58,12 @@ bool make_lay(const liw_loop_params* p, const liw_floop_dims* d, Lay* L, int* nA
 
 }  // namespace
 
-struct liw_floop_ctx {
+struct liw_floop_ctx : liw_fleet_ctx_base {
     Lay L{};
     Prm P{};
-    int device = 0;
-    bool have_device = false;
-    std::string err;
 };
 
 namespace {
-
-int fail(liw_floop_ctx* c, int code, const char* what) { c->err = what; return code; }
-
-#define FLOOP_DEV(c)                                                                              \
-    do {                                                                                          \
-        if (!(c)) return LIW_EINVAL;                                                              \
-        if (!(c)->have_device) return fail((c), LIW_ENODEV, "no usable gfx950 device (no CPU fallback)"); \
-        (void)hipSetDevice((c)->device);                                                          \
-    } while (0)
-
-bool bad_store(const void* store) { return !store || ((uintptr_t)store & 7) != 0; }
-
-template <class T> bool pull(const void* store, size_t off, T* dst, size_t n) {
-    return hipMemcpy(dst, (const char*)store + off, sizeof(T) * n, hipMemcpyDeviceToHost) == hipSuccess;
-}
 
 // header {K, full} of a robot; < 0 on error
 int robot_header(liw_floop_ctx* c, const void* store, int robot, int* hdr) {
@@ -130,16 +111,7 @@ liw_floop_ctx* liw_floop_create(const liw_loop_params* params, const liw_floop_d
     P.min_interval = params->min_interval;
     P.seed = params->seed;
     liw_lie_from_matrix16(T_imu_to_wheel16, normalize_extrinsics, P.Tiw);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) {
-        hipDeviceProp_t props;
-        if (hipGetDeviceProperties(&props, device) == hipSuccess) {
-            if (std::strstr(props.gcnArchName, "gfx950") != nullptr) c->have_device = true;
-            else c->err = std::string("device is ") + props.gcnArchName + ", this library is built for gfx950 only";
-        }
-    }
-    (void)hipGetLastError();
-    if (!c->have_device && c->err.empty()) c->err = "no HIP device";
+    c->have_device = liw_probe_gfx950(device, &c->err);
     return c;
 }
 
@@ -147,7 +119,7 @@ void liw_floop_destroy(liw_floop_ctx* c) { delete c; }
 const char* liw_floop_last_error(liw_floop_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
 
 int liw_floop_reset(liw_floop_ctx* c, void* store, const unsigned char* mask, void* stream) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store)) return fail(c, LIW_EINVAL, "liw_floop_reset: store");
     if (liw_floop_dev::launch_reset((char*)store, c->L, mask, (hipStream_t)stream)) return fail(c, LIW_EHIP, "liw_floop_reset: kernel launch failed");
     return LIW_OK;
@@ -155,7 +127,7 @@ int liw_floop_reset(liw_floop_ctx* c, void* store, const unsigned char* mask, vo
 
 int liw_floop_add_keyframes(liw_floop_ctx* c, void* store, const unsigned char* key, const double* pose, const double* corners, int corner_stride,
                             const int* n_corners, const unsigned char* mask, unsigned char* added, void* stream) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !key || !pose || !corners || !n_corners || corner_stride < 1)
         return fail(c, LIW_EINVAL, "liw_floop_add_keyframes: bad argument");
     if (liw_floop_dev::launch_add((char*)store, c->L, c->P, key, pose, corners, corner_stride, n_corners, mask, added, (hipStream_t)stream))
@@ -165,7 +137,7 @@ int liw_floop_add_keyframes(liw_floop_ctx* c, void* store, const unsigned char* 
 
 int liw_floop_detect(liw_floop_ctx* c, void* store, const unsigned char* key, const unsigned char* mask, unsigned char* found, int* edge, double* tf12,
                      long long* stats, void* stream) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !key || !found || !edge || !tf12 || !stats) return fail(c, LIW_EINVAL, "liw_floop_detect: bad argument");
     if (liw_floop_dev::launch_detect((char*)store, c->L, c->P, key, mask, found, edge, tf12, stats, (hipStream_t)stream))
         return fail(c, LIW_EHIP, "liw_floop_detect: kernel launch failed");
@@ -173,21 +145,21 @@ int liw_floop_detect(liw_floop_ctx* c, void* store, const unsigned char* key, co
 }
 
 int liw_floop_num_keyframes(liw_floop_ctx* c, const void* store, int robot) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[2];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     return hdr[0];
 }
 
 int liw_floop_full(liw_floop_ctx* c, const void* store, int robot) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[2];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     return hdr[1] != 0;
 }
 
 int liw_floop_status(liw_floop_ctx* c, const void* store, int robot, int k, int* n_points, double* origin12, double* tf12) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[2];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     if (k < 0 || k >= hdr[0]) return fail(c, LIW_EINVAL, "liw_floop_status: no such key frame");
@@ -209,12 +181,12 @@ int liw_floop_status(liw_floop_ctx* c, const void* store, int robot, int k, int*
 // feature slot of key frame k of a robot with K key frames, -1 if its feature is not held
 static int held_slot(const Lay& L, int k, int K) {
     if (k < 0 || k >= K) return -1;
-    if (k % L.step == 0) return k / L.step;
-    return k == K - 1 ? L.NC : -1;
+    const int fs = liw_floop_dev::feature_slot(L, k);
+    return fs < L.NC || k == K - 1 ? fs : -1;
 }
 
 int liw_floop_get_points(liw_floop_ctx* c, const void* store, int robot, int k, int cap, double* points) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[2];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     const int fs = held_slot(c->L, k, hdr[0]);
@@ -224,13 +196,13 @@ int liw_floop_get_points(liw_floop_ctx* c, const void* store, int robot, int k, 
     if (st < 0) return st;
     if (st != LIW_LOOP_VALID && st != LIW_LOOP_DIJ_OVERFLOW) return fail(c, LIW_EINVAL, "liw_floop_get_points: no points");
     const int m = std::min(n, cap);
-    if (m > 0 && !pull(store, (size_t)robot * c->L.robot_bytes + c->L.r_pts + (size_t)fs * c->L.P * 24, points, (size_t)m * 3))
+    if (!pull(store, (size_t)robot * c->L.robot_bytes + c->L.r_pts + (size_t)fs * c->L.P * 24, points, (size_t)m * 3))
         return fail(c, LIW_EHIP, "liw_floop_get_points: hipMemcpy");
     return n;
 }
 
 int liw_floop_get_row(liw_floop_ctx* c, const void* store, int robot, int k, int i, int cap, int* dij, int* j, double* aij, unsigned long long* quick_des) {
-    FLOOP_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[2];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     const Lay& L = c->L;
@@ -245,7 +217,7 @@ int liw_floop_get_row(liw_floop_ctx* c, const void* store, int robot, int k, int
     std::vector<uint32_t> kv((size_t)std::max(m, 1));
     std::vector<double> av((size_t)std::max(m, 1));
     std::vector<unsigned long long> qv((size_t)L.W);
-    if (m > 0 && (!pull(store, base + L.r_keys + row * L.P * 4, kv.data(), m) || !pull(store, base + L.r_aij + row * L.P * 8, av.data(), m)))
+    if (!pull(store, base + L.r_keys + row * L.P * 4, kv.data(), m) || !pull(store, base + L.r_aij + row * L.P * 8, av.data(), m))
         return fail(c, LIW_EHIP, "liw_floop_get_row: hipMemcpy");
     if (!pull(store, base + L.r_quick + row * L.W * 8, qv.data(), L.W)) return fail(c, LIW_EHIP, "liw_floop_get_row: hipMemcpy");
     for (int e = 0; e < m; ++e) {

@@ -18,6 +18,7 @@
 #include "../../include/liw_lie.h"
 #include "../../include/liw_map.h"
 #include "k_map.hpp"
+#include "liw_host_common.hpp"
 
 struct liw_ctx;
 hipStream_t liw_ctx_stream(liw_ctx* c);
@@ -36,7 +37,6 @@ struct Layout {
     size_t pts, sub, tf, partial, bounds, counters, bits, grid, bytes;
 };
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int layout(const liw_map_params* p, const liw_map_dims* d, Layout* L) {
     if (!p || !(p->resolution > 0) || !std::isfinite(p->resolution)) return LIW_EINVAL;

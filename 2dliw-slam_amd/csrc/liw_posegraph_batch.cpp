@@ -13,6 +13,7 @@
 #include "../../include/liw_posegraph_batch.h"
 #include "k_posegraph_batch.hpp"
 #include "k_posegraph_dev.hpp"
+#include "liw_host_common.hpp"
 
 void liw_fill_devparams(const liw_params* prm, liw::DevParams* dp);   // liw_capi.hip
 
@@ -20,8 +21,6 @@ namespace {
 
 using liw_fpg_dev::Lay;
 using namespace liw_fpg_dev;
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 bool make_lay(const liw_fpg_dims* d, Lay* L) {
     if (!d || d->B < 1 || d->max_keyframes < 1 || d->max_loops < 0) return false;
@@ -66,36 +65,15 @@ bool make_lay(const liw_fpg_dims* d, Lay* L) {
 
 }  // namespace
 
-struct liw_fpg_ctx {
+struct liw_fpg_ctx : liw_fleet_ctx_base {
     Lay L{};
     Noise noise{};
     liw::DevParams P{};
     double period = 0.0;
     int lds_cap = kLdsDoubles;
-    int device = 0;
-    bool have_device = false;
-    std::string err;
 };
 
 namespace {
-
-int fail(liw_fpg_ctx* c, int code, const char* what) { c->err = what; return code; }
-
-#define FPG_DEV(c)                                                                                \
-    do {                                                                                          \
-        if (!(c)) return LIW_EINVAL;                                                              \
-        if (!(c)->have_device) return fail((c), LIW_ENODEV, "no usable gfx950 device (no CPU fallback)"); \
-        (void)hipSetDevice((c)->device);                                                          \
-    } while (0)
-
-bool bad_store(const void* store) { return !store || ((uintptr_t)store & 7) != 0; }
-
-template <class T> bool pull(const void* store, size_t off, T* dst, size_t n) {
-    return n == 0 || hipMemcpy(dst, (const char*)store + off, sizeof(T) * n, hipMemcpyDeviceToHost) == hipSuccess;
-}
-template <class T> bool push(void* store, size_t off, const T* src, size_t n) {
-    return n == 0 || hipMemcpy((char*)store + off, src, sizeof(T) * n, hipMemcpyHostToDevice) == hipSuccess;
-}
 
 // the eight header words of a robot; < 0 on error
 int robot_header(liw_fpg_ctx* c, const void* store, int robot, int* hdr) {
@@ -143,16 +121,7 @@ liw_fpg_ctx* liw_fpg_create(const liw_params* params, const liw_pg_params* pg, c
     n.ground_on_p = pg->use_ground_p_factor ? 1.0 : 0.0;
     n.ground_on_q = pg->use_ground_q_factor ? 1.0 : 0.0;
     n.loop_edge_k = pg->loop_edge_k;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) {
-        hipDeviceProp_t props;
-        if (hipGetDeviceProperties(&props, device) == hipSuccess) {
-            if (std::strstr(props.gcnArchName, "gfx950") != nullptr) c->have_device = true;
-            else c->err = std::string("device is ") + props.gcnArchName + ", this library is built for gfx950 only";
-        }
-    }
-    (void)hipGetLastError();
-    if (!c->have_device && c->err.empty()) c->err = "no HIP device";
+    c->have_device = liw_probe_gfx950(device, &c->err);
     return c;
 }
 
@@ -167,7 +136,7 @@ int liw_fpg_set_lds_doubles(liw_fpg_ctx* c, int doubles) {
 }
 
 int liw_fpg_reset(liw_fpg_ctx* c, void* store, const unsigned char* mask, void* stream) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store)) return fail(c, LIW_EINVAL, "liw_fpg_reset: store");
     if (launch_reset((char*)store, c->L, mask, (hipStream_t)stream)) return fail(c, LIW_EHIP, "liw_fpg_reset: kernel launch failed");
     return LIW_OK;
@@ -175,7 +144,7 @@ int liw_fpg_reset(liw_fpg_ctx* c, void* store, const unsigned char* mask, void* 
 
 int liw_fpg_add_keyframes(liw_fpg_ctx* c, void* store, const unsigned char* key, const double* pose, const double* stamp, const unsigned char* mask,
                           unsigned char* added, void* stream) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !key || !pose || !stamp) return fail(c, LIW_EINVAL, "liw_fpg_add_keyframes: bad argument");
     if (launch_add_keyframes((char*)store, c->L, key, pose, stamp, mask, added, (hipStream_t)stream))
         return fail(c, LIW_EHIP, "liw_fpg_add_keyframes: kernel launch failed");
@@ -184,7 +153,7 @@ int liw_fpg_add_keyframes(liw_fpg_ctx* c, void* store, const unsigned char* key,
 
 int liw_fpg_add_loops(liw_fpg_ctx* c, void* store, const unsigned char* found, const int* edge, const double* tf12, const unsigned char* mask,
                       void* stream) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !found || !edge || !tf12) return fail(c, LIW_EINVAL, "liw_fpg_add_loops: bad argument");
     if (launch_add_loops((char*)store, c->L, found, edge, tf12, mask, (hipStream_t)stream)) return fail(c, LIW_EHIP, "liw_fpg_add_loops: kernel launch failed");
     return LIW_OK;
@@ -192,7 +161,7 @@ int liw_fpg_add_loops(liw_fpg_ctx* c, void* store, const unsigned char* found, c
 
 int liw_fpg_due(liw_fpg_ctx* c, void* store, const unsigned char* key, const double* stamp, const unsigned char* mask, unsigned char* due, int* n_due,
                 void* stream) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !key || !stamp || !due) return fail(c, LIW_EINVAL, "liw_fpg_due: bad argument");
     if (launch_due((char*)store, c->L, c->period, key, stamp, mask, due, n_due, (hipStream_t)stream)) return fail(c, LIW_EHIP, "liw_fpg_due: kernel launch failed");
     return LIW_OK;
@@ -200,7 +169,7 @@ int liw_fpg_due(liw_fpg_ctx* c, void* store, const unsigned char* key, const dou
 
 int liw_fpg_solve(liw_fpg_ctx* c, void* store, const unsigned char* sel, const double* stamp, int max_iters, int check_every, liw_summary* summary,
                   void* stream) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !sel || !stamp || !summary) return fail(c, LIW_EINVAL, "liw_fpg_solve: bad argument");
     if (launch_solve((char*)store, c->L, c->noise, c->P, sel, stamp, max_iters, check_every, c->lds_cap, summary, (hipStream_t)stream))
         return fail(c, LIW_EHIP, "liw_fpg_solve: kernel launch or read-back failed");
@@ -208,21 +177,21 @@ int liw_fpg_solve(liw_fpg_ctx* c, void* store, const unsigned char* sel, const d
 }
 
 int liw_fpg_correct(liw_fpg_ctx* c, void* store, const double* pose_in, double* pose_out, const unsigned char* mask, void* stream) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     if (bad_store(store) || !pose_in || !pose_out) return fail(c, LIW_EINVAL, "liw_fpg_correct: bad argument");
     if (launch_correct((char*)store, c->L, pose_in, pose_out, mask, (hipStream_t)stream)) return fail(c, LIW_EHIP, "liw_fpg_correct: kernel launch failed");
     return LIW_OK;
 }
 
 int liw_fpg_num_keyframes(liw_fpg_ctx* c, const void* store, int robot) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     return hdr[H_NKF];
 }
 
 int liw_fpg_flags(liw_fpg_ctx* c, const void* store, int robot, int* flags6, double* last_solve_time) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (!flags6) return fail(c, LIW_EINVAL, "liw_fpg_flags: null flags");
     if (int r = robot_header(c, store, robot, hdr)) return r;
@@ -232,7 +201,7 @@ int liw_fpg_flags(liw_fpg_ctx* c, const void* store, int robot, int* flags6, dou
 }
 
 int liw_fpg_get_keyframes(liw_fpg_ctx* c, const void* store, int robot, int cap, double* poses, double* stamps, double* tf12) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     if (cap < 0) return fail(c, LIW_EINVAL, "liw_fpg_get_keyframes: cap");
@@ -244,7 +213,7 @@ int liw_fpg_get_keyframes(liw_fpg_ctx* c, const void* store, int robot, int cap,
 }
 
 int liw_fpg_get_seq_edges(liw_fpg_ctx* c, const void* store, int robot, int cap, double* tf12) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     if (cap < 0) return fail(c, LIW_EINVAL, "liw_fpg_get_seq_edges: cap");
@@ -255,7 +224,7 @@ int liw_fpg_get_seq_edges(liw_fpg_ctx* c, const void* store, int robot, int cap,
 }
 
 int liw_fpg_get_loop_edges(liw_fpg_ctx* c, const void* store, int robot, int cap, int* idx, double* tf12) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (int r = robot_header(c, store, robot, hdr)) return r;
     if (cap < 0) return fail(c, LIW_EINVAL, "liw_fpg_get_loop_edges: cap");
@@ -266,7 +235,7 @@ int liw_fpg_get_loop_edges(liw_fpg_ctx* c, const void* store, int robot, int cap
 }
 
 int liw_fpg_get_modify_delta_tf(liw_fpg_ctx* c, const void* store, int robot, double* tf12) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (!tf12) return fail(c, LIW_EINVAL, "liw_fpg_get_modify_delta_tf: null output");
     if (int r = robot_header(c, store, robot, hdr)) return r;
@@ -275,7 +244,7 @@ int liw_fpg_get_modify_delta_tf(liw_fpg_ctx* c, const void* store, int robot, do
 }
 
 int liw_fpg_get_summary(liw_fpg_ctx* c, const void* store, int robot, liw_summary* summary) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     int hdr[8];
     if (!summary) return fail(c, LIW_EINVAL, "liw_fpg_get_summary: null output");
     if (int r = robot_header(c, store, robot, hdr)) return r;
@@ -285,7 +254,7 @@ int liw_fpg_get_summary(liw_fpg_ctx* c, const void* store, int robot, liw_summar
 
 int liw_fpg_load_graph(liw_fpg_ctx* c, void* store, int robot, int N, const double* poses, const double* stamps, const double* seq_tf12, int n_loop,
                        const int* loop_idx, const double* loop_tf12) {
-    FPG_DEV(c);
+    LIW_FLEET_DEV(c);
     const Lay& L = c->L;
     if (bad_store(store) || robot < 0 || robot >= L.B || N < 1 || N > L.K || !poses || (N > 1 && !seq_tf12) || n_loop < 0 || n_loop > L.ML ||
         (n_loop && (!loop_idx || !loop_tf12)))

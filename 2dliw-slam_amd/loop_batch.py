@@ -8,6 +8,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._fleet import FleetStore, _pd, _pi
 from .loop import LoopParamsC, params_struct, sizes, tf12_to_mat
 
 # every symbol include/liw_loop_batch.h declares (checked by tests/test_loop_batch_abi.py)
@@ -79,20 +80,14 @@ def store_bytes(params, dims):
     return n.value
 
 
-def _pd(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _pi(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int))
-
-
-class FleetLoopDetector:
+class FleetLoopDetector(FleetStore):
     """prm: solver parameters (synth.office_params layout; T_imu_to_wheel and normalize_extrinsics are used); loop_params: dict as
     loop.office_loop_params; dims: dict(B, max_keyframes, max_points, max_kf_corners).  Owns the store (a torch uint8 tensor, with
     `guard` bytes of 0xA5 on either side for tests) and the outputs added [B] uint8, found [B] uint8, edge [B, 3] int32, tf12 [B, 12], stats [B, 6]
     int64: views valid until the next call.  Every call runs on torch's current stream; add_keyframes, detect and push neither
     synchronise nor read back."""
+
+    _destroy, _last_error = "liw_floop_destroy", "liw_floop_last_error"
 
     def __init__(self, prm, loop_params, dims, device="cuda:0", guard=0):
         import torch
@@ -109,57 +104,12 @@ class FleetLoopDetector:
                                                      C.c_int(int(bool(prm.get("normalize_extrinsics", True)))), C.c_int(index)))
         if not self.h:
             raise LiwError(-22, "liw_floop_create: bad params or dims")
-        self.guard = int(guard)
-        if self.guard % 8:
-            raise ValueError("guard must be a multiple of 8 (the store is 8-byte aligned)")
-        self._buf = torch.zeros(self.lay["bytes"] + 2 * self.guard, dtype=torch.uint8, device=self.dev)   # zeroed: the bytes are reproducible
-        if self.guard:
-            self._buf[:self.guard] = 0xA5
-            self._buf[self.guard + self.lay["bytes"]:] = 0xA5
-        self.store = self._buf[self.guard:self.guard + self.lay["bytes"]]
+        self._alloc_store(guard)
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.dev)
         B = self.B
         self.found, self.edge, self.tf12, self.stats = z(B, dt=torch.uint8), z(B, 3, dt=torch.int32), z(B, 12, dt=torch.float64), z(B, 6, dt=torch.int64)
         self.added = z(B, dt=torch.uint8)
         self.reset()
-
-    def close(self):
-        if self.h:
-            self.L.liw_floop_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, r):
-        if r < 0:
-            raise self.LiwError(r, self.L.liw_floop_last_error(self.h).decode())
-        return r
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def _t(self, a, dt, shape=None):
-        torch = self.torch
-        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
-        t = t.to(device=self.dev, dtype=dt).contiguous()
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
-        return t
-
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _mask(self, mask):
-        return None if mask is None else self._t(mask, self.torch.uint8, (self.B,))
-
-    def robot_regions(self):
-        """[B, robot_bytes] uint8 view of the store's robot regions (the scratch area behind them is not part of it)"""
-        return self.store[:self.B * self.lay["robot_bytes"]].view(self.B, self.lay["robot_bytes"])
 
     def reset(self, mask=None):
         m = self._mask(mask)
@@ -196,9 +146,6 @@ class FleetLoopDetector:
         return dict(self.detect(added, mask=mask), added=added)
 
     # ---- inspection (synchronous)
-    def _sync(self):
-        self.torch.cuda.synchronize(self.dev)
-
     def num_keyframes(self, robot):
         self._sync()
         return self._chk(self.L.liw_floop_num_keyframes(self.h, self._ptr(self.store), C.c_int(robot)))

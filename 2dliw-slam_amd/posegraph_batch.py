@@ -7,6 +7,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._fleet import FleetStore, _pd, _pi
 from .posegraph import PgParamsC, pg_struct
 
 # every symbol include/liw_posegraph_batch.h declares (checked by tests/test_posegraph_batch_abi.py)
@@ -86,14 +87,6 @@ def store_bytes(dims):
     return n.value
 
 
-def _pd(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _pi(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
-
-
 def summary_rows(raw):
     """[B, 32] uint8 host array of liw_summary rows -> list of dicts as PoseGraph.solve returns"""
     raw = np.ascontiguousarray(raw)
@@ -102,7 +95,7 @@ def summary_rows(raw):
             for i, d in zip(ints, dbl)]
 
 
-class FleetBackEnd:
+class FleetBackEnd(FleetStore):
     """prm: solver parameters (synth.office_params layout; the extrinsics and ground sigmas are used); pg: dict as
     posegraph.office_pg_params; dims: dict(B, max_keyframes, max_loops); solve_period: seconds of key-frame time between two solves of
     a robot; max_iters (<= 0: 50) and check_every are the defaults of solve().  Owns the store (a torch uint8 tensor, with `guard`
@@ -111,6 +104,8 @@ class FleetBackEnd:
     current stream.  Behind a FleetLoopDetector give both the same max_keyframes: push() stores a key frame exactly when the loop
     detector stored it, so the edge indices of its loops are the indices of this queue.
     What stays with the caller: the occupancy map per robot, non-laser key frames, a C++ mirror of this class."""
+
+    _destroy, _last_error = "liw_fpg_destroy", "liw_fpg_last_error"
 
     def __init__(self, prm, pg, dims, solve_period=10.0, device="cuda:0", guard=0, max_iters=0, check_every=4):
         import torch
@@ -127,57 +122,12 @@ class FleetBackEnd:
                                                    C.c_int(index)))
         if not self.h:
             raise LiwError(-22, "liw_fpg_create: bad params or dims")
-        self.guard = int(guard)
-        if self.guard % 8:
-            raise ValueError("guard must be a multiple of 8 (the store is 8-byte aligned)")
-        self._buf = torch.zeros(self.lay["bytes"] + 2 * self.guard, dtype=torch.uint8, device=self.dev)   # zeroed: the bytes are reproducible
-        if self.guard:
-            self._buf[:self.guard] = 0xA5
-            self._buf[self.guard + self.lay["bytes"]:] = 0xA5
-        self.store = self._buf[self.guard:self.guard + self.lay["bytes"]]
+        self._alloc_store(guard)
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.dev)
         B = self.B
         self.added, self.due_flags, self.n_due = z(B, dt=torch.uint8), z(B, dt=torch.uint8), z(1, dt=torch.int32)
         self.summary, self.corrected = z(B, SUMMARY_BYTES, dt=torch.uint8), z(B, 6, dt=torch.float64)
         self.reset()
-
-    def close(self):
-        if self.h:
-            self.L.liw_fpg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, r):
-        if r < 0:
-            raise self.LiwError(r, self.L.liw_fpg_last_error(self.h).decode())
-        return r
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def _t(self, a, dt, shape=None):
-        torch = self.torch
-        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
-        t = t.to(device=self.dev, dtype=dt).contiguous()
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
-        return t
-
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _mask(self, mask):
-        return None if mask is None else self._t(mask, self.torch.uint8, (self.B,))
-
-    def robot_regions(self):
-        """[B, robot_bytes] uint8 view of the store's robot regions (the solver's work area behind them is not part of it)"""
-        return self.store[:self.B * self.lay["robot_bytes"]].view(self.B, self.lay["robot_bytes"])
 
     def modify_delta_tf(self):
         """[B, 12] float64 strided view of every robot's modify_delta_tf in the store (no copy: it shows what later solves write)"""
@@ -257,9 +207,6 @@ class FleetBackEnd:
         return dict(added=added, due=due, n_due=n, summary=self.summary, modify_delta_tf=self.modify_delta_tf())
 
     # ---- inspection (synchronous)
-    def _sync(self):
-        self.torch.cuda.synchronize(self.dev)
-
     def summaries(self):
         self._sync()
         return summary_rows(self.summary.cpu().numpy())

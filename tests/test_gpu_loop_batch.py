@@ -138,6 +138,26 @@ def test_features_bit_identical(liw, synth):
     fl.close()
 
 
+@pytest.mark.parametrize("n", tgl.DESCRIBE_EDGE_N)
+def test_features_bit_identical_at_sort_and_lane_edges(liw, synth, n):
+    """Sub-maps of n points, where the shared descriptor body's sort padding and lane strides change (tgl.DESCRIBE_EDGE_N), for two
+    robots against the single detector: every byte of keys, aij and quick_des.  With max_points = 130 the describe grid has 128
+    blocks per robot, so at n = 129 one wave also runs a second point in the same LDS."""
+    import torch
+    C_, _ = tgl.describe_edge_case(n)
+    B, P = 2, tgl.DESCRIBE_EDGE_CAP
+    p = tgl._params()
+    fl, det = _fleet(liw, synth, p, B, 2, P, P, guard=GUARD), _single(liw, synth, p, 2, P)
+    inp = _upload(torch, B, P, [(np.zeros(6), C_)] * B)
+    assert fl.add_keyframes(inp["key"], inp["pose"], inp["acc"], inp["n_acc"]).tolist() == [1] * B
+    assert det.add_keyframe(cases.make_tf(np.zeros(6)), C_) == 0
+    for b in range(B):
+        assert _same_feature(liw, fl, b, det, 0) == n
+    buf = fl._buf
+    assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[-GUARD:] == 0xA5).all())
+    fl.close()
+
+
 # --------------------------------------------------------------------------------------------------------------------- 2
 def _frame_items(robots, t):
     seqs = cases.sequences()
