@@ -99,6 +99,13 @@ int liw_fpg_layout(const liw_fpg_dims* dims, liw_fpg_layout_info* out) {
     return LIW_OK;
 }
 
+int liw_fpg_pose_offset(const liw_fpg_dims* dims, size_t* off) {
+    Lay L{};
+    if (!off || !make_lay(dims, &L)) return LIW_EINVAL;
+    *off = L.r_pose;
+    return LIW_OK;
+}
+
 int liw_fpg_store_bytes(const liw_fpg_dims* dims, size_t* bytes) {
     Lay L{};
     if (!bytes || !make_lay(dims, &L)) return LIW_EINVAL;

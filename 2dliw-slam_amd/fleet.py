@@ -9,7 +9,8 @@ scan on: the per-robot INITIALIZING state machine (the is_static gate, each robo
 window is full, the restart of a failed window) in the same step as the tracking frame.  The key frames a step returns (key, pose, acc,
 n_acc) are what loop_batch.FleetLoopDetector.push takes: the fleet's key-frame store and laser loop detector; its result and the
 step's go to posegraph_batch.FleetBackEnd.push, the pose-graph back-end of the fleet (queue, edges, solve, map-frame correction).
-The map per robot, non-laser key frames and the sensor-inited latch stay with the caller.  There is no CPU fallback."""
+The occupancy map per robot is map_batch.FleetMapper's: it stores scan_points() of the key frames and renders from the back-end's poses.
+Non-laser key frames and the sensor-inited latch stay with the caller.  There is no CPU fallback."""
 import numpy as np
 
 from .laser_batch import REF, BatchFrontEnd, track_params_struct
@@ -87,6 +88,11 @@ class FleetTracker:
         self.n_acc.zero_()
         self.key.zero_()
         self.frames = 0
+
+    def scan_points(self):
+        """(pts [B, max_points, 3], n [B] int32): views of the de-skewed laser-frame points of the last step's scans, valid until the
+        next step: what map_batch.FleetMapper.add_keyframes stores for the robots whose key frame was kept"""
+        return self._pts[0], self._pts[2]
 
     def bias(self):
         """[B, 6] view of the newest frame's ba, bw: what the next interval's pre-integration is reset with"""
@@ -174,8 +180,8 @@ class FleetTrajectory(FleetTracker):
     block, has_match 1 with the pose record of an empty match, and its prior rows (none).  They are put back from a snapshot after
     the marginalisation, as the rows of a skipped robot are.
 
-    Out of scope: the map per robot and non-laser key frames (the key frames themselves and their loop edges are
-    loop_batch.FleetLoopDetector's, the pose-graph solve around them posegraph_batch.FleetBackEnd's), keep_window_size > 1, the imu_inited / wheel_odom_inited latch (the caller starts stepping once it
+    The key frames and their loop edges are loop_batch.FleetLoopDetector's, the pose-graph solve around them
+    posegraph_batch.FleetBackEnd's, the occupancy map per robot map_batch.FleetMapper's.  Out of scope: non-laser key frames, keep_window_size > 1, the imu_inited / wheel_odom_inited latch (the caller starts stepping once it
     has intervals), a C++ mirror of this driver."""
 
     def __init__(self, prm, laser_prm, track_prm, init_prm, dims, device="cuda:0", cap=256, max_corners=64, acc_cap=1024, init_iters=0):

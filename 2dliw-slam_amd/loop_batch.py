@@ -3,7 +3,7 @@ the key / pose / acc / n_acc tensors `FleetTracker.step` / `FleetTrajectory.step
 whose key is set to a per-robot store with their sub-map features, and runs laser_loop_detect for each of them, on torch's
 current stream and without a host loop over robots.  `loop.LoopDetector` (one robot, host glue) is its parity reference.  There is
 no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device.  What `push` returns goes on to
-posegraph_batch.FleetBackEnd.push, the fleet's pose-graph back-end; the map per robot and non-laser key frames stay with the caller."""
+posegraph_batch.FleetBackEnd.push, the fleet's pose-graph back-end, and the occupancy map per robot is map_batch.FleetMapper's; non-laser key frames stay with the caller."""
 import ctypes as C
 
 import numpy as np

@@ -14,7 +14,7 @@ from .posegraph import PgParamsC, pg_struct
 FPG_EXPORTS = ["liw_fpg_store_bytes", "liw_fpg_layout", "liw_fpg_create", "liw_fpg_destroy", "liw_fpg_last_error", "liw_fpg_reset",
                "liw_fpg_add_keyframes", "liw_fpg_add_loops", "liw_fpg_due", "liw_fpg_solve", "liw_fpg_correct", "liw_fpg_num_keyframes",
                "liw_fpg_flags", "liw_fpg_get_keyframes", "liw_fpg_get_seq_edges", "liw_fpg_get_loop_edges", "liw_fpg_get_modify_delta_tf",
-               "liw_fpg_get_summary", "liw_fpg_load_graph", "liw_fpg_set_lds_doubles"]
+               "liw_fpg_get_summary", "liw_fpg_load_graph", "liw_fpg_set_lds_doubles", "liw_fpg_pose_offset"]
 
 FLAGS = ("loops", "full", "loops_full", "bad_edge", "pending", "solves")
 SUMMARY_BYTES = 32   # sizeof(liw_summary)
@@ -43,6 +43,7 @@ def _lib():
         dd = C.POINTER(FpgDimsC)
         L.liw_fpg_store_bytes.argtypes = [dd, C.POINTER(C.c_size_t)]
         L.liw_fpg_layout.argtypes = [dd, C.POINTER(FpgLayoutC)]
+        L.liw_fpg_pose_offset.argtypes = [dd, C.POINTER(C.c_size_t)]
         L.liw_fpg_create.restype = vp
         L.liw_fpg_create.argtypes = [C.POINTER(ParamsC), C.POINTER(PgParamsC), dd, C.c_double, ci]
         L.liw_fpg_destroy.argtypes = [vp]
@@ -103,7 +104,8 @@ class FleetBackEnd(FleetStore):
     (liw_summary rows; summaries() decodes them), corrected [B, 6]: views valid until the next call.  Every call runs on torch's
     current stream.  Behind a FleetLoopDetector give both the same max_keyframes: push() stores a key frame exactly when the loop
     detector stored it, so the edge indices of its loops are the indices of this queue.
-    What stays with the caller: the occupancy map per robot, non-laser key frames, a C++ mirror of this class."""
+    The occupancy map per robot is map_batch.FleetMapper's, which reads poses() in place.  What stays with the caller: non-laser key
+    frames, a C++ mirror of this class."""
 
     _destroy, _last_error = "liw_fpg_destroy", "liw_fpg_last_error"
 
@@ -133,6 +135,19 @@ class FleetBackEnd(FleetStore):
         """[B, 12] float64 strided view of every robot's modify_delta_tf in the store (no copy: it shows what later solves write)"""
         rb = self.lay["robot_bytes"]
         return self.store[:self.B * rb].view(self.torch.float64).view(self.B, rb // 8)[:, 5:17]
+
+    def pose_offset(self):
+        """byte offset of the corrected poses within a robot region (liw_fpg_pose_offset)"""
+        off = C.c_size_t(0)
+        self._chk(self.L.liw_fpg_pose_offset(C.byref(dims_struct(self.dims)), C.byref(off)))
+        return off.value
+
+    def poses(self):
+        """[B, max_keyframes, 6] float64 strided view of every robot's corrected poses (p, rotation vector) in the store (no copy: it
+        shows what later solves write); robot b holds num_keyframes(b) of them.  map_batch.FleetMapper.render takes it as it is."""
+        rb, K = self.lay["robot_bytes"], self.dims["max_keyframes"]
+        o = self.pose_offset() // 8
+        return self.store[:self.B * rb].view(self.torch.float64).view(self.B, rb // 8)[:, o:o + 6 * K].unflatten(1, (K, 6))
 
     def set_lds_doubles(self, doubles):
         """test hook: separator systems of more than `doubles` entries run from the work area (0: all of them; default 8192)"""

@@ -75,6 +75,10 @@ typedef struct liw_fpg_ctx liw_fpg_ctx;
 int liw_fpg_store_bytes(const liw_fpg_dims* dims, size_t* bytes);
 /* the same with the sizes of the parts.  Host-only. */
 int liw_fpg_layout(const liw_fpg_dims* dims, liw_fpg_layout_info* out);
+/* byte offset of the corrected-pose part (pose, 48 K) within a robot region, so that a consumer reads the poses in place: robot b's
+ * key frame k is at store + b * robot_bytes + *off + 48 k (liw_fmap_render of liw_map_batch.h: poses = store + *off, robot_stride =
+ * robot_bytes / 8).  LIW_EINVAL for bad dims or a null pointer.  Host-only. */
+int liw_fpg_pose_offset(const liw_fpg_dims* dims, size_t* off);
 
 /* a ctx bound to the solver parameters (extrinsics and ground sigmas are read), the pose-graph parameters, dims and solve_period
  * (seconds of key-frame time between two solves of a robot); device = HIP device ordinal.  NULL only on a bad argument. */

@@ -1,0 +1,123 @@
+"""Fleet map timing on the MI355X (include/liw_map_batch.h): FleetMapper.render_tf for B robots, each holding --keyframes sub-maps of
+--rays rays cast in one of 16 distinct rooms (tiled over the fleet), against the only way to do it without it: a host loop of
+GridMap.render_tf calls, one handle per robot.
+
+The host loop is linear in the robots by construction (serial calls with two synchronising read-backs each), so it is measured on
+at most --baseline-robots robots and scaled to B; the JSON says which.  Wall times around torch.cuda.synchronize(), the median of
+--reps after one warm-up render.  Per B two rows: every robot selected, and one robot in 16 (the work-groups of the others exit at
+once).  The rows are printed as JSON lines and written to --out (profiles/fleet_map_bench.json).
+  python tools/bench_map_batch.py --fleet 1,64,1024 [--keyframes 200] [--rays 360] [--reps 5]
+Under rocprofv3 --kernel-trace --stats: --fleet 1024 --no-baseline --reps 1 --out ''."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def scenes(n_rooms, K, n_rays, seed=5):
+    """per room: T_w_l [K, 12] along the circle (three laps, small noise and tilt) and K scans padded to [K, n_rays, 3] with counts [K]"""
+    import map_batch_cases as mc
+    rng = np.random.default_rng(seed)
+    tfs, pts, cnt = np.zeros((n_rooms, K, 12)), np.zeros((n_rooms, K, n_rays, 3)), np.zeros((n_rooms, K), np.int32)
+    for r, room in enumerate(mc.rooms(n_rooms)):
+        for k in range(K):
+            a = 2 * np.pi * 3 * k / K + 0.3 * r
+            x, y, yaw = 5.0 * np.cos(a) + rng.normal(0, 0.02), 5.0 + 5.0 * np.sin(a) + rng.normal(0, 0.02), a + np.pi / 2 + rng.normal(0, 0.01)
+            s = mc.scan(room, x, y, yaw, n_rays, rng)
+            cnt[r, k] = len(s)
+            pts[r, k, :len(s)] = s
+            tfs[r, k] = mc.tf12(x, y, yaw, rng.normal(0, 0.01), rng.normal(0, 0.005), rng.normal(0, 0.005))
+    return tfs, pts, cnt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fleet", default="1,64,1024")
+    ap.add_argument("--keyframes", type=int, default=200)
+    ap.add_argument("--rays", type=int, default=360)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rooms", type=int, default=16)
+    ap.add_argument("--baseline-robots", type=int, default=64)
+    ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_map_bench.json"))
+    a = ap.parse_args()
+    import torch
+    liw = importlib.import_module("2dliw-slam_amd")
+    synth = importlib.import_module("2dliw-slam_amd.synth")
+    prm = synth.office_params()
+    K, R = a.keyframes, a.rays
+    tfs, pts, cnt = scenes(a.rooms, K, R)
+    cells, steps = 1 << 17, 1024           # a 16 m room at 5 cm is 321 x 321 cells; rays stay below 25.5 m
+    d_tfs, d_pts, d_cnt = torch.as_tensor(tfs).cuda(), torch.as_tensor(pts).cuda(), torch.as_tensor(cnt).cuda()
+    rows = []
+    for B in [int(v) for v in a.fleet.split(",")]:
+        room_of = torch.arange(B, device="cuda") % a.rooms
+        fm = liw.FleetMapper(prm, dict(resolution=0.05), dict(B=B, max_submaps=K, max_points=K * R, max_cells=cells, max_steps=steps))
+        key = torch.ones(B, dtype=torch.uint8, device="cuda")
+        for k in range(K):
+            fm.add_keyframes(key, d_pts[room_of, k], d_cnt[room_of, k])
+        T = d_tfs[room_of].contiguous()
+        t_host = None
+        if not a.no_baseline:
+            nb = min(B, a.baseline_robots)
+            maps = []
+            for b in range(nb):
+                m = liw.gridmap.GridMap(prm, dict(resolution=0.05), dict(max_submaps=K, max_points=K * R, max_cells=cells))
+                for k in range(K):
+                    m.add_submap(pts[b % a.rooms, k, :cnt[b % a.rooms, k]])
+                maps.append(m)
+        for every in (1, 16):
+            sel = (torch.arange(B, device="cuda") % every == 0).to(torch.uint8)
+            n_sel = int(sel.sum().item())
+            ts = []
+            for rep in range(a.reps + 1):          # the first one warms up
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fm.render_tf(T, sel=sel)
+                torch.cuda.synchronize()
+                if rep:
+                    ts.append(time.perf_counter() - t0)
+            t_fleet = float(np.median(ts))
+            st = fm.status.cpu().numpy()[sel.cpu().numpy() != 0]
+            info = fm.info_of(0)
+            row = dict(bench="fleet_map", B=B, selected=n_sel, keyframes=K, rays=R, rooms=min(a.rooms, B), status_ok=bool((st == 0).all()),
+                       grid="%d x %d" % (info["width"], info["height"]), rays_cast=info["rays"], samples=info["samples"],
+                       robot_MB=round(fm.lay["robot_bytes"] / 1e6, 3), store_MB=round(fm.lay["bytes"] / 1e6, 1),
+                       fleet_ms_per_render=round(t_fleet * 1e3, 3), fleet_us_per_robot=round(t_fleet * 1e6 / n_sel, 2))
+            if not a.no_baseline:
+                use = [b for b in range(nb) if b % every == 0]
+                for b in use[:1]:
+                    maps[b].render_tf(tfs[b % a.rooms])
+                tb = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    for b in use:
+                        maps[b].render_tf(tfs[b % a.rooms])
+                    tb.append(time.perf_counter() - t0)
+                t_host = float(np.median(tb)) * n_sel / len(use)
+                same = bool(np.array_equal(maps[0].grid(), fm.grid(0)))
+                row.update(host_loop_ms_per_render=round(t_host * 1e3, 3), host_loop_robots_measured=len(use), host_loop_scaled=bool(len(use) < n_sel),
+                           speedup=round(t_host / t_fleet, 2), robot0_equals_single_map=same)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+        fm.close()
+        del fm, T
+        if not a.no_baseline:
+            del maps
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            for row in rows:
+                f.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
