@@ -377,6 +377,8 @@ void launch_marg_schur(const MargArgs& a, hipStream_t s);
 struct PreintNoise { double q_na[3], q_nw[3], q_nba[3], q_nbw[3], wheel_cov[3]; };
 void launch_preint_imu(int M, const int* sample_off, const double* samples, const double* t_start, const double* t_end, const double* bias6,
                        const PreintNoise& N, double* X, double* J, double* Pscratch, double* sqrtP, double* Dt, hipStream_t s);
+// sqrt_inverse_P [M][225] of the covariances P [M][225] alone; mask [M] uint8 (nullptr = all): rows of masked-out entries stay unwritten
+void launch_preint_imu_sqrt(int M, const double* P, double* sqrtP, const unsigned char* mask, hipStream_t s);
 void launch_preint_wheel(int M, const int* sample_off, const double* samples, const double* t_start, const double* t_end,
                          const PreintNoise& N, double* T12, double* sq9, double* Dt, hipStream_t s);
 

@@ -10,7 +10,9 @@ window is full, the restart of a failed window) in the same step as the tracking
 n_acc) are what loop_batch.FleetLoopDetector.push takes: the fleet's key-frame store and laser loop detector; its result and the
 step's go to posegraph_batch.FleetBackEnd.push, the pose-graph back-end of the fleet (queue, edges, solve, map-frame correction).
 The occupancy map per robot is map_batch.FleetMapper's: it stores scan_points() of the key frames and renders from the back-end's poses.
-Non-laser key frames and the sensor-inited latch stay with the caller.  There is no CPU fallback."""
+The intervals a step takes come from preint_batch.FleetPreint, the front door of a frame: persistent per-robot IMU / wheel accumulators
+fed raw messages, with the sensor-inited latch and the merge of the intervals of skipped and dropped scans (FleetPreint.step drives
+either class).  Non-laser key frames stay with the caller.  There is no CPU fallback."""
 import numpy as np
 
 from .laser_batch import REF, BatchFrontEnd, track_params_struct
@@ -127,8 +129,9 @@ class FleetTracker:
     def step(self, ranges, stamps, interval):
         """one tracking frame of every robot.  ranges [B, n_rays] float32 (geometry: fe.set_geometry), stamps [B], interval: the six
         device tensors imu_X [B, 15], imu_J [B, 225], imu_sqrtP [B, 225], imu_Dt [B], wheel_T [B, 12], wheel_sqrtP [B, 9] of the
-        interval that ends at the scan (BatchPreint makes them).  A robot whose imu_Dt is below min_delta_t is skipped: apart from its
-        skip counter it is left byte for byte as it was (the caller merges that interval into the next one).
+        interval that ends at the scan (FleetPreint.push makes them from the messages; BatchPreint from the closed intervals of a log).  A
+        robot whose imu_Dt is below min_delta_t is skipped: apart from its skip counter it is left byte for byte as it was (its interval
+        merges into the next one: FleetPreint.step does not commit it; a caller with intervals of its own has to merge them).
         -> dict(skip, key [B] uint8, flags [B] uint8 of ADD_* bits, pose [B, 6], Ltot, acc [B, acc_cap, 3], n_acc [B]): views of
         the tracker's buffers, valid until the next step; pose of a skipped robot is the one of its last accepted frame."""
         torch, fe, B = self.torch, self.fe, self.B
@@ -181,8 +184,9 @@ class FleetTrajectory(FleetTracker):
     the marginalisation, as the rows of a skipped robot are.
 
     The key frames and their loop edges are loop_batch.FleetLoopDetector's, the pose-graph solve around them
-    posegraph_batch.FleetBackEnd's, the occupancy map per robot map_batch.FleetMapper's.  Out of scope: non-laser key frames, keep_window_size > 1, the imu_inited / wheel_odom_inited latch (the caller starts stepping once it
-    has intervals), a C++ mirror of this driver."""
+    posegraph_batch.FleetBackEnd's, the occupancy map per robot map_batch.FleetMapper's.  The imu_inited / wheel_odom_inited latch is preint_batch.FleetPreint's: its step() hands a robot whose
+    latch is off the identity increment, which the gates here drop.  Out of scope: non-laser key frames, keep_window_size > 1, a C++
+    mirror of this driver."""
 
     def __init__(self, prm, laser_prm, track_prm, init_prm, dims, device="cuda:0", cap=256, max_corners=64, acc_cap=1024, init_iters=0):
         super().__init__(prm, laser_prm, track_prm, dims, device=device, cap=cap, max_corners=max_corners, acc_cap=acc_cap)
@@ -246,8 +250,8 @@ class FleetTrajectory(FleetTracker):
 
     def step(self, ranges, stamps, interval):
         """one frame of every robot, whatever its state; arguments as FleetTracker.step.  An INITIALIZING robot whose wheel increment
-        is below both motion thresholds is dropped: apart from its counter it is left byte for byte as it was (the caller merges the
-        interval into the next one), as a TRACKING robot below min_delta_t is skipped.  A robot committed in this frame tracks from
+        is below both motion thresholds is dropped: apart from its counter it is left byte for byte as it was (its interval merges into
+        the next one, as FleetPreint.step does by not committing it), as a TRACKING robot below min_delta_t is skipped.  A robot committed in this frame tracks from
         the next one.
         -> FleetTracker.step's dict (skip, key, flags 0 for robots that are not TRACKING) plus status [B] int32 after the frame,
         drop [B] uint8, ready [B] uint8 (the window was full and went into the INIT solve), init_ok [B] uint8 (it was committed)."""
