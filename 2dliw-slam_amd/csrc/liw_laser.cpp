@@ -183,6 +183,7 @@ struct liw_scan_impl {
         if (max_dis > line_max_dis) return false;
         if (len < line_min_len) return false;
         const int id = (int)pool.size();
+        const size_t registered = lines.size();
         pool.push_back(Line{p1, p2, abc, len});
         if (add_concers) {
             for (int i = i1; i <= i2; ++i) {
@@ -221,7 +222,7 @@ struct liw_scan_impl {
                 if (cell.ids.empty() || cell.ids.back() != id) { cell.ids.push_back(id); register_line(id); }
             }
         }
-        return true;
+        return lines.size() > registered;   // an accepted line that touches no valid cell is in no list (scan::lines grows in a cell only)
     }
     // scan::add_line(p1, p2, add_concers) (:213-222)
     bool add_segment(const Vec& p1, const Vec& p2, bool add_concers, double line_max_dis, double line_min_len) {

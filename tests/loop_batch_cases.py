@@ -9,6 +9,7 @@ import importlib
 import numpy as np
 
 import loop_reference as ref
+import second_config as sc
 import test_gpu_loop as tgl
 
 FRAMES = 40            # fleet frames; robot r gets its 30 key frames in frames OFFSET[r] .. OFFSET[r] + 29
@@ -22,6 +23,19 @@ ROBOTS = [
     (1, 6, {}, dict(spin0=0.8), 0),                                                             # candidate 0 rejected by the tf gate
     (1, 8, {}, dict(drift=(-0.15, 0.1, -0.04)), 5),
     (1, 21, {}, dict(drift=(0.05, 0.05, -0.02)), 2),
+    (1, 22, {}, dict(revisit=False), 9),
+]
+# the sequences at the second sets (second_config.LOOP_SETS "fine" and "coarse", detectors created from skewed_params): robot 2 comes
+# back 0.9 m beside its first leg, so origin distances lie between max_tf_p and max_dis on candidates that give edges; robots 3 and
+# 6 drift by half a metre, so |dp| of the tf gate lies between max_tf_q and max_tf_p on accepted edges
+ROBOTS_SECOND = [
+    (3, 5, {}, dict(drift=(0.2, -0.1, 0.05)), 0),
+    (3, 7, {}, dict(revisit=False), 3),
+    (3, 10, {}, dict(drift=(0.2, 0.0, 0.02), offset=(0.9, -0.03, 0.03)), 7),
+    (3, 11, {}, dict(drift=(0.45, -0.2, 0.05)), 10),
+    (1, 6, {}, dict(spin0=0.8), 0),
+    (1, 8, {}, dict(drift=(-0.15, 0.1, -0.04)), 5),
+    (1, 21, {}, dict(drift=(0.45, -0.2, 0.05)), 2),
     (1, 22, {}, dict(revisit=False), 9),
 ]
 SETS = {3: [0, 1, 2, 3], 1: [4, 5, 6, 7]}     # robots by parameter set (submap_count): one fleet detector per set
@@ -53,16 +67,24 @@ def make_tf(pose):
     return _lie()[1](pose)
 
 
-def params(submap_count, **kw):
-    return tgl._params(submap_count=submap_count, **kw)
+def robots(cfg="office"):
+    return ROBOTS if cfg == "office" else ROBOTS_SECOND
 
 
-def T_imu_to_wheel():
-    """the extrinsic as the detectors load it (liw_get_extrinsics of a ctx made from the office parameters)"""
+def params(submap_count, cfg="office", **kw):
+    return tgl._set_params(cfg, submap_count=submap_count, **kw)
+
+
+def prm(cfg="office"):
+    """the parameters the detectors of a set are created from"""
+    return tgl._set_prm(importlib.import_module("2dliw-slam_amd.synth"), cfg)
+
+
+def T_imu_to_wheel(cfg="office"):
+    """the extrinsic as the detectors load it (liw_get_extrinsics of a ctx made from the set's parameters)"""
     liw = importlib.import_module("2dliw-slam_amd")
-    synth = importlib.import_module("2dliw-slam_amd.synth")
     L = liw.lib()
-    ps = liw.params_struct(synth.office_params())
+    ps = liw.params_struct(prm(cfg))
     ctx = C.c_void_p(L.liw_create(C.byref(ps)))
     M = np.zeros(16)
     L.liw_get_extrinsics(ctx, M.ctypes.data_as(C.POINTER(C.c_double)), None)
@@ -71,12 +93,12 @@ def T_imu_to_wheel():
 
 
 @functools.lru_cache(maxsize=None)
-def sequences():
+def sequences(cfg="office"):
     """per robot: list of KEYFRAMES (pose6, T = make_tf(pose6), corners [n][3])"""
     pose_of, mk = _lie()
-    Tiw = T_imu_to_wheel()
+    Tiw = T_imu_to_wheel(cfg)
     out = []
-    for S, seed, lkw, skw, _ in ROBOTS:
+    for S, seed, lkw, skw, _ in robots(cfg):
         rng = np.random.default_rng(seed)
         skw = dict(skw)
         if "drift" in skw:
@@ -126,14 +148,16 @@ class GateRecorder(ref.Detector):
 
 
 @functools.lru_cache(maxsize=None)
-def restatement():
-    """per robot: dict(edges [KEYFRAMES] (None or the edge after key frame k), gates, n_points, later_passes)"""
-    Tiw = T_imu_to_wheel()
+def restatement(cfg="office", T_iw=None):
+    """per robot: dict(edges [KEYFRAMES] (None or the edge after key frame k), gates, n_points, later_passes, per_candidate: the gate
+    values grouped by evaluated candidate).  T_iw (a tuple of 16) replaces the extrinsic of the restatement alone: the CPU guards
+    show with it that a wrong T_imu_to_wheel in the tf gate's conjugation moves the edges."""
+    Tiw = T_imu_to_wheel(cfg) if T_iw is None else np.array(T_iw).reshape(4, 4)
     out = []
-    for r, (S, *_rest) in enumerate(ROBOTS):
-        rd = GateRecorder(params(S), MAX_POINTS[S], Tiw)
+    for r, (S, *_rest) in enumerate(robots(cfg)):
+        rd = GateRecorder(params(S, cfg), MAX_POINTS[S], Tiw)
         edges = []
-        for pose, T, Cn in sequences()[r]:
+        for pose, T, Cn in sequences(cfg)[r]:
             rd.add_keyframe(T, Cn, True)
             edges.append(rd.detect())
         later = False
@@ -142,7 +166,18 @@ def restatement():
             s = S // 3 + 1
             later = any(rd.try_candidate(e["index1"], c) is not None for c in range(e["index2"] + s, e["index1"] - rd.p["min_interval"], s))
             del rd.gates[n0:]
-        out.append(dict(edges=edges, gates=list(rd.gates), n_points=[len(f.points) for f in rd.features], later_passes=later))
+        out.append(dict(edges=edges, gates=list(rd.gates), n_points=[len(f.points) for f in rd.features], later_passes=later,
+                        per_candidate=per_candidate(rd.gates), min_margin=min(rd.margins) if rd.margins else np.inf))
+    return out
+
+
+def per_candidate(gates):
+    """the recorded gates grouped by evaluated candidate: every candidate starts with its "dis" record -> list of dicts kind -> value"""
+    out = []
+    for k, v, _ in gates:
+        if k == "dis" or not out:
+            out.append({})
+        out[-1][k] = v
     return out
 
 

@@ -7,7 +7,11 @@ in every scalar, has three distinct components per vector, generic extrinsic rot
 quaternion round trip of the parameter loader (reference src/utilies/params.cpp:44-54) does work.
 
 A helper module, not a conftest: it holds the configuration, the inputs the two test modules share and the mutated restatements with
-which the CPU guards show that these inputs would expose each class of mistake.  Everything here is numpy."""
+which the CPU guards show that these inputs would expose each class of mistake.  Everything here is numpy.
+
+Its second half holds the sets of the FRONT half — laser_params (a 138 x 83 grid, no two scalars equal, ref_n_accumulation = 5),
+loop_params (a_res != d_res, max_dis != max_tf_p) — and the laser scene that tests/test_second_config_frontend.py (CPU guards) and
+tests/test_gpu_laser_second_config.py share; the loop detector and map tests take skewed_params for their extrinsics."""
 import os
 import sys
 
@@ -196,3 +200,181 @@ def factor_move(ref, alt, kind):
     """largest |alt - ref| / max(1, |ref|_inf) over the residuals and Jacobians of one factor type: the measure of the per-factor bar"""
     rel = lambda a, b: float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1.0, np.abs(np.asarray(b)).max()))
     return max(max(rel(a[0], b[0]), rel(a[1], b[1])) for a, b in zip(alt[kind], ref[kind]))
+
+
+# ---------------------------------------------------------------- the front half: laser front-end, loop detector, map
+LASER = dict(w_laser_each_scan=11.0, h_laser_each_scan=6.6, laser_resolution=0.08, line_continuous_threshold=0.14, line_min_len=0.11,
+             line_max_dis=0.021, line_max_tolerance_angle=170.0, ref_motion_filter_p=0.03, ref_motion_filter_q=0.017, ref_n_accumulation=5)
+LASER_W, LASER_H = 138, 83      # (int)(11.0 / 0.08 + 1), (int)(6.6 / 0.08 + 1): 137.5 and 82.5 before the + 1, no rounding decides
+LASER_THRESHOLDS = ("line_max_dis", "line_min_len", "line_continuous_threshold", "line_max_tolerance_angle", "ref_motion_filter_p",
+                    "ref_motion_filter_q", "laser_resolution")
+N_RAYS = 1080
+ANG_MIN = np.float32(-2.0 * np.pi * 0.75 / 2)
+ANG_INC = np.float32(2.0 * np.pi * 0.75 / (N_RAYS - 1))
+T_INC = np.float32(1.0 / (40.0 * N_RAYS))
+ROOMS, POSES_PER_ROOM, FRAMES = (1, 2, 3, 4, 5, 6), 4, 16
+F_SMALL_P, F_SMALL_Q = 6, 11   # frames of the manager sequence whose motion lies between the two motion-filter thresholds
+MATCH_GUESS = np.array([0.01, -0.01, 0.0, 0.0, 0.0, 0.004])   # do_match: the guess of the second pose is slightly off, as in tracking
+
+LOOP_SETS = dict(
+    office=dict(a_res=0.03, d_res=0.03, min_match_threshold=5, min_interval=10, max_dis=1.0, max_tf_p=1.0, max_tf_q=0.5),
+    fine=dict(a_res=0.025, d_res=0.02, min_match_threshold=7, min_interval=12, max_dis=1.4, max_tf_p=0.8, max_tf_q=0.35),
+    coarse=dict(a_res=0.07, d_res=0.11, min_match_threshold=7, min_interval=12, max_dis=1.4, max_tf_p=0.8, max_tf_q=0.35),
+    edge=dict(a_res=2.0 * np.pi / 253.0, d_res=0.02, min_match_threshold=7, min_interval=12, max_dis=1.4, max_tf_p=0.8, max_tf_q=0.35))
+
+
+def laser_params(liw, prm):
+    """The second laser set over liw.laser.office_laser_params(prm), prm = skewed_params(synth): w = 138 and h = 83 cells (one even, one
+    odd, 11 m x 6.6 m against rooms of about 9 m x 7 m: narrower than the rooms in one direction, wider in the other), every scalar
+    different from every other one, an odd ref_n_accumulation (spawn at count 2, swap at count 5: a 2 / 3 cycle)."""
+    return dict(liw.laser.office_laser_params(prm), **LASER)
+
+
+def loop_params(name="fine", **kw):
+    """A loop-detector set of LOOP_SETS: `fine` (W = 79 descriptor words, 253 angle bins: two lane passes), `coarse` (W = 15, 91 bins),
+    `edge` (a_res = 2 pi / 253, the smallest that check_params accepts: 2 pi / a_res + 2 is 255.0 in double arithmetic, so
+    nAngle + 1 = 256 = kMaxBins bins, the largest LDS histogram; anything finer, 2 pi / 253.5 included, is LIW_EINVAL) or `office`."""
+    p = dict(LOOP_SETS[name], submap_count=1, seed=12345)
+    p.update(kw)
+    return p
+
+
+def held_extrinsic(liw, prm, key="T_imu_to_laser"):
+    """the 4x4 extrinsic as the library holds it: liw_lie_from_matrix16 with the parameters' normalize_extrinsics (the loader's
+    quaternion round trip), exactly"""
+    import ctypes as C
+    pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    M, T12 = np.ascontiguousarray(np.asarray(prm[key], dtype=np.float64).reshape(16)), np.zeros(12)
+    liw.lib().liw_lie_from_matrix16(pd(M), C.c_int(int(bool(prm.get("normalize_extrinsics", True)))), pd(T12))
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = T12[:9].reshape(3, 3), T12[9:]
+    return T
+
+
+def transposed_laser_rotation(liw, lp):
+    """lp with ONE mistake: the laser rotation as held, transposed (normalize_extrinsics off, so it arrives as given)"""
+    T = held_extrinsic(liw, lp)
+    return dict(lp, T_imu_to_laser=_matrix16(T[:3, :3].T, T[:3, 3]), normalize_extrinsics=False)
+
+
+def laser_mutations(liw, lp):
+    """name -> laser parameters with ONE mistake, each of which a kernel could make without an office-set test noticing"""
+    off = liw.laser.office_laser_params()
+    out = {"w and h exchanged": dict(lp, w_laser_each_scan=lp["h_laser_each_scan"], h_laser_each_scan=lp["w_laser_each_scan"]),
+           "motion filters exchanged": dict(lp, ref_motion_filter_p=lp["ref_motion_filter_q"], ref_motion_filter_q=lp["ref_motion_filter_p"]),
+           "ref_n_accumulation = 4": dict(lp, ref_n_accumulation=4),
+           "laser rotation transposed": transposed_laser_rotation(liw, lp)}
+    for k in ("line_min_len", "line_max_dis", "line_continuous_threshold", "line_max_tolerance_angle"):
+        out["office " + k] = dict(lp, **{k: off[k]})
+    return out
+
+
+def pose_T(synth, pose):
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = synth.exp_so3(np.asarray(pose[3:6], dtype=np.float64)), pose[:3]
+    return T
+
+
+def cast_scan(segs, T_w_l, seed, noise=0.004, max_range=30.0):
+    """liw.laser.cast_scan's ranges for N_RAYS rays, all rays at once (the same formulas; the noise is drawn per hit in ray order)"""
+    rng = np.random.default_rng(seed)
+    o, yaw = T_w_l[:2, 3], np.arctan2(T_w_l[1, 0], T_w_l[0, 0])
+    a = yaw + float(ANG_MIN) + np.arange(N_RAYS) * float(ANG_INC)
+    dx, dy = np.cos(a), np.sin(a)
+    best = np.full(N_RAYS, np.inf)
+    for p, q in segs:
+        e, w = q - p, p - o
+        den = dx * e[1] - dy * e[0]
+        ok = np.abs(den) >= 1e-12
+        den = np.where(ok, den, 1.0)
+        t, u = (w[0] * e[1] - w[1] * e[0]) / den, (w[0] * dy - w[1] * dx) / den
+        ok &= (t > 0.05) & (u >= 0.0) & (u <= 1.0) & (t < best)
+        best = np.where(ok, t, best)
+    hit = best < max_range
+    ranges = np.full(N_RAYS, np.inf, dtype=np.float32)
+    ranges[hit] = (best[hit] + rng.normal(0.0, noise, int(hit.sum()))).astype(np.float32)
+    return ranges
+
+
+WALK_SEED = 4301   # chosen so that no decision of the oracle sits within 1e-6 of a threshold (tests/test_second_config_frontend.py)
+MIN_LINES, MIN_BACK_MATCHES = 5, 2   # floors of the GPU laser tests: lines per scan, matches with the scan before
+
+
+def _walk(liw, synth, room, Til, rng, seed):
+    """a planar walk of the LASER in the room; the IMU poses are T_w_l T_il^-1, as a robot's are, so that the relative laser motion
+    T_il^-1 (T_1^-1 T_2) T_il of add_scan and do_match stays near the scan plane and generic 3D rotation vectors reach make_tf.
+    The rotation of T_il here is the rotation nearest to the one the library holds, which is 0.2 % off orthonormal at this set (the
+    loader's round trip does not undo LASER_SKEW): transformed lines leave the plane z = 0 by millimetres, below line_max_dis."""
+    planar = np.zeros((FRAMES, 6))
+    planar[0] = np.concatenate([rng.uniform(-1.0, 1.0, 2), [0.0, 0.0, 0.0], rng.uniform(-np.pi, np.pi, 1)])
+    for k in range(1, FRAMES):
+        step, turn = rng.uniform(0.05, 0.12), rng.uniform(-0.04, 0.04)
+        if k == F_SMALL_P:
+            step, turn = 0.024, 0.001
+        if k == F_SMALL_Q:
+            step, turn = 0.001, 0.024
+        d = rng.uniform(-np.pi, np.pi)
+        planar[k] = planar[k - 1] + np.array([step * np.cos(d), step * np.sin(d), 0.0, 0.0, 0.0, turn])
+    U, _, Vt = np.linalg.svd(Til[:3, :3])
+    T_li = np.eye(4)
+    T_li[:3, :3] = (U @ Vt).T
+    T_li[:3, 3] = -T_li[:3, :3] @ Til[:3, 3]
+    poses, pts = np.zeros((FRAMES, 6)), []
+    for k in range(FRAMES):
+        T_wl = pose_T(synth, planar[k])
+        T_wi = T_wl @ T_li
+        poses[k] = np.concatenate([T_wi[:3, 3], synth.log_so3(T_wi[:3, :3])])
+        pts.append(liw.laser.laser_to_points(cast_scan(room, T_wl, seed=seed + k), ANG_MIN, ANG_INC, T_INC, 0.0)[0])
+    return poses, pts
+
+
+def _meets_floors(liw, lp, poses, pts):
+    scans = [liw.laser.Scan.spawn(lp, p) for p in pts]
+    if min(s.lines().shape[0] for s in scans) < MIN_LINES:
+        return False
+    return all(len(liw.laser.do_match(lp, scans[k - 1], scans[k], poses[k - 1, :3], poses[k - 1, 3:], poses[k, :3], poses[k, 3:], kk)) >= MIN_BACK_MATCHES
+               for k in range(1, FRAMES) for kk in (0, 1))
+
+
+_scene = {}
+
+
+def laser_scene(liw, synth):
+    """The inputs of the laser tests at the second set, computed once: B = 24 robots (the six rooms of
+    tests/test_laser_frontend.py x four poses), each walking FRAMES = 16 frames (_walk).  Steps are up to 0.12 m and 0.04 rad; in
+    frame F_SMALL_P the laser moves 0.024 m (between the two motion-filter thresholds) and 0.001 rad, in frame F_SMALL_Q 0.001 m and
+    0.024 rad (the IMU 0.007 m, through the lever arm): the filter drops the first and keeps the second, and does the converse with
+    its thresholds exchanged.
+    -> dict(prm, lp, Til, poses [B, F, 6], points [B][F] arrays [m, 3] in the laser frame, low_edge: a hand-placed scan)"""
+    if _scene:
+        return _scene
+    prm = skewed_params(synth)
+    lp = laser_params(liw, prm)
+    Til = held_extrinsic(liw, prm)
+    B = len(ROOMS) * POSES_PER_ROOM
+    poses = np.zeros((B, FRAMES, 6))
+    points, tries = [], []
+    for b in range(B):
+        room = liw.laser.room_segments(ROOMS[b // POSES_PER_ROOM])
+        for attempt in range(200):       # the first walk of the robot's seeds that meets the floors of the GPU tests
+            pw, pts = _walk(liw, synth, room, Til, np.random.default_rng(WALK_SEED + 1000 * attempt + b), 100 * b + 10000 * attempt)
+            if _meets_floors(liw, lp, pw, pts):
+                break
+        else:
+            raise AssertionError("no walk of robot %d meets the floors" % b)
+        poses[b] = pw
+        points.append(pts)
+        tries.append(attempt)
+    # a wall whose points have grid coordinates in (-1, 0) x [0, h): xy_to_index truncates them toward zero into column 0, a valid cell
+    res, w2 = LASER["laser_resolution"], LASER_W // 2
+    y = np.linspace(-1.0, 1.0, 60)
+    low = np.stack([np.full(60, (-w2 - 0.5) * res) + 0.002 * np.sin(7.0 * y), y, np.zeros(60)], 1)
+    _scene.update(prm=prm, lp=lp, Til=Til, poses=poses, points=points, low_edge=low, tries=tries)
+    return _scene
+
+
+def grid_coordinates(lp, pts):
+    """(gx, gy) = x / resolution + w / 2, y / resolution + h / 2 before the truncation of xy_to_index, and (w, h)"""
+    res = lp["laser_resolution"]
+    w, h = int(lp["w_laser_each_scan"] / res + 1), int(lp["h_laser_each_scan"] / res + 1)
+    return pts[:, 0] / res + w // 2, pts[:, 1] / res + h // 2, w, h

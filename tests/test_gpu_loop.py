@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import loop_reference as ref
+import second_config as sc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +24,19 @@ def _params(**kw):
              seed=12345)
     p.update(kw)
     return p
+
+
+SECOND_SETS = ("fine", "coarse")   # second_config.LOOP_SETS: a_res != d_res, W = 79 / 15 descriptor words, 253 / 91 angle bins
+
+
+def _set_params(cfg, **kw):
+    """_params at a set of second_config.LOOP_SETS ("office": _params itself)"""
+    return _params(**kw) if cfg == "office" else sc.loop_params(cfg, **kw)
+
+
+def _set_prm(synth, cfg):
+    """the parameters a detector of the set is created from: the second sets come with the generic T_imu_to_wheel of skewed_params"""
+    return synth.office_params() if cfg == "office" else sc.skewed_params(synth)
 
 
 def _rot(yaw):
@@ -59,8 +73,8 @@ def _seen(L, T_true, r=2.5, drift=None, noise=0.0, rng=None, spin=0.0):
     return P3
 
 
-def _pair(liw, synth, p, max_points=128, max_keyframes=256):
-    det = liw.loop.LoopDetector(synth.office_params(), p, dict(max_keyframes=max_keyframes, max_points=max_points))
+def _pair(liw, synth, p, max_points=128, max_keyframes=256, cfg="office"):
+    det = liw.loop.LoopDetector(_set_prm(synth, cfg), p, dict(max_keyframes=max_keyframes, max_points=max_points))
     return det, ref.Detector(p, max_points, det.T_imu_to_wheel)
 
 
@@ -72,9 +86,20 @@ def _feed(det, rd, frames):
 
 # ------------------------------------------------------------------------------------------------------------------ descriptors
 def test_descriptors_and_points_bit_exact(liw, synth):
+    _check_descriptors_and_points(liw, synth, "office")
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+def test_descriptors_and_points_bit_exact_second_sets(liw, synth, cfg):
+    """a_res != d_res; at the fine set W = 79 words: describe_point's `for (w = lane; w < g.W; w += 64)` loops run a second pass"""
+    _check_descriptors_and_points(liw, synth, cfg)
+
+
+def _check_descriptors_and_points(liw, synth, cfg):
     rng = np.random.default_rng(1)
-    p = _params(submap_count=3)
-    det, rd = _pair(liw, synth, p)
+    p = _set_params(cfg, submap_count=3)
+    det, rd = _pair(liw, synth, p, cfg=cfg)
+    assert (det.W, det.n_angle) == ref.sizes(p)
     L = _landmarks(rng)
     frames = []
     for k in range(8):
@@ -101,6 +126,7 @@ def test_descriptors_and_points_bit_exact(liw, synth):
             a = np.array(row["aij"])
             assert np.all(np.abs(g["aij"] - a) <= np.spacing(np.maximum(np.abs(a), 1e-300)))   # the device acos: within 1 ulp
             nrows += 1
+    print("descriptors at the %s set (W = %d): %d rows equal" % (cfg, det.W, nrows))
     assert nrows > 200
 
 
@@ -111,16 +137,19 @@ DESCRIBE_EDGE_CAP = 130   # max_points of these cases: above every n and no mult
 
 
 @functools.lru_cache(maxsize=None)
-def describe_edge_case(n):
+def describe_edge_case(n, cfg="office"):
     """-> (corners [n][3], rows of loop_reference.describe): a jittered 0.5 m lattice in shuffled order.  The corners are at least
     0.3 m = 10 d_res apart, so the de-duplication (5 d_res) keeps every one in the given order; dij stays below 300, so among the
-    up to 128 entries of a row many dij are equal and the (dij, j) order decides."""
+    up to 128 entries of a row many dij are equal and the (dij, j) order decides.  At another set the lattice is scaled by
+    d_res / 0.03, which keeps both statements."""
     rng = np.random.default_rng(7)
     g = np.arange(12) * 0.5
     X, Y = np.meshgrid(g, g)
     P = np.stack([X.ravel(), Y.ravel()], axis=1) + rng.uniform(-0.1, 0.1, (144, 2))
     C = np.concatenate([P[rng.permutation(144)[:n]], np.zeros((n, 1))], axis=1)
-    p = _params()
+    p = _set_params(cfg)
+    if cfg != "office":
+        C = np.ascontiguousarray(C * (p["d_res"] / 0.03))
     return C, ref.describe(C.tolist(), p["d_res"], ref.sizes(p)[0])
 
 
@@ -130,8 +159,20 @@ def test_descriptors_at_sort_and_lane_edges(liw, synth, n):
     A comparison of the bits of aij with the reference does not hold at any of these n, before or after the kernels shared their
     bodies (measured on an MI355X: up to 7 of a row's aij are one ulp off, the device acos against the host's; docs/WIDENING.md lists
     it as open).  tests/test_gpu_loop_batch.py compares the fleet with this detector at the same n, there with every bit of aij."""
-    C, rows = describe_edge_case(n)
-    det = liw.loop.LoopDetector(synth.office_params(), _params(), dict(max_keyframes=2, max_points=DESCRIBE_EDGE_CAP))
+    _check_describe_edge(liw, synth, n, "office")
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+@pytest.mark.parametrize("n", DESCRIBE_EDGE_N)
+def test_descriptors_at_sort_and_lane_edges_second_sets(liw, synth, n, cfg):
+    """the same sizes at a_res != d_res; at the fine set n = 66 and 129 need a second lane pass over the entries (n - 1 > 64) and
+    over the W = 79 words of quick_des at once"""
+    _check_describe_edge(liw, synth, n, cfg)
+
+
+def _check_describe_edge(liw, synth, n, cfg):
+    C, rows = describe_edge_case(n, cfg)
+    det = liw.loop.LoopDetector(_set_prm(synth, cfg), _set_params(cfg), dict(max_keyframes=2, max_points=DESCRIBE_EDGE_CAP))
     assert det.add_keyframe(_pose(0.0, 0.0, 0.0), C, True) == 0
     assert det.status(0)["state"] == liw.loop.VALID and det.get_points(0).tobytes() == C.tobytes()
     for i, row in enumerate(rows):
@@ -140,6 +181,39 @@ def test_descriptors_at_sort_and_lane_edges(liw, synth, n):
         assert [int(v) for v in g["quick"]] == row["quick"], i
         a = np.array(row["aij"])
         assert np.all(np.abs(g["aij"] - a) <= np.spacing(np.maximum(np.abs(a), 1e-300))), i   # the device acos: within 1 ulp
+
+
+@functools.lru_cache(maxsize=None)
+def describe_far_case(n_near, far):
+    """-> (parameters, corners, rows of loop_reference.describe) at the fine set (W = 79 words, bins of 64 dij = 1.28 m): n_near
+    corners of describe_edge_case's lattice and one corner `far` metres along x from the lattice"""
+    p = sc.loop_params("fine")
+    C, _ = describe_edge_case(n_near, "fine")
+    C = np.concatenate([C, [[far, 0.4, 0.0]]])
+    return p, C, ref.describe(C.tolist(), p["d_res"], ref.sizes(p)[0])
+
+
+@pytest.mark.parametrize("n_near,far", [(2, 134.0), (70, 95.0)])
+def test_descriptors_of_far_corners_at_the_fine_set(liw, synth, n_near, far):
+    """(2, 134 m): dij = 6 500 ... 6 700 >= 64 W = 5 056, so the entry is kept and sorted but its quick bit is dropped.
+    (70, 95 m): n - 1 = 70 entries and the quick words 69 ... 74 of W = 79 are both beyond the first 64-lane pass."""
+    p, C, rows = describe_far_case(n_near, far)
+    W = ref.sizes(p)[0]
+    assert W == 79
+    far_dij = [d for r in rows for d in r["dij"] if d // 64 >= 64]
+    if n_near == 2:
+        assert far_dij and min(far_dij) // 64 >= W and all(not any(r["quick"][64:]) for r in rows)
+    else:
+        assert len(C) - 1 > 64 and far_dij and max(far_dij) // 64 < W and any(any(r["quick"][64:]) for r in rows)
+    det = liw.loop.LoopDetector(_set_prm(synth, "fine"), p, dict(max_keyframes=2, max_points=DESCRIBE_EDGE_CAP))
+    assert det.add_keyframe(_pose(0.0, 0.0, 0.0), C, True) == 0
+    assert det.status(0)["state"] == liw.loop.VALID and det.get_points(0).tobytes() == C.tobytes()
+    for i, row in enumerate(rows):
+        g = det.get_row(0, i)
+        assert g["dij"].tolist() == row["dij"] and g["j"].tolist() == row["j"], i
+        assert [int(v) for v in g["quick"]] == row["quick"], i
+        a = np.array(row["aij"])
+        assert np.all(np.abs(g["aij"] - a) <= np.spacing(np.maximum(np.abs(a), 1e-300))), i
 
 
 # ------------------------------------------------------------------------------------------------------------------ match_map
@@ -152,11 +226,11 @@ def _lattice(rng, n_side, spacing, yaw, offset):
     return np.concatenate([P, np.zeros((len(P), 1))], axis=1)
 
 
-def _match_features(rng, L):
+def _match_features(rng, L, pieces=26):
     """feature point sets: pieces of one landmark field under rigid motions (real matches), rotated lattices (long equal-dij runs,
     ties), tiny sets (repeated draws, the size gates)"""
     feats = []
-    for k in range(26):
+    for k in range(pieces):
         c = rng.uniform(-4, 4, 2)
         P = L[np.linalg.norm(L - c, axis=1) < rng.uniform(1.2, 2.6)]
         T = _pose(*rng.uniform(-5, 5, 2), rng.uniform(-3, 3))
@@ -171,18 +245,46 @@ def _match_features(rng, L):
 
 @pytest.mark.parametrize("thr", [3, 5])
 def test_match_map_equals_the_serial_walk(liw, synth, thr):
+    _check_match_map(liw, synth, "office", thr)
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+@pytest.mark.parametrize("thr", [5, 7])
+def test_match_map_equals_the_serial_walk_second_sets(liw, synth, thr, cfg):
+    """a_res != d_res through angle_bin and the dij keys; tests/test_second_config_frontend.py shows on the CPU that exchanging the
+    two changes more than a tenth of these pairs"""
+    _check_match_map(liw, synth, cfg, thr)
+
+
+def test_match_map_at_the_largest_histogram(liw, synth):
+    """the edge set: nAngle + 1 = 256 = kMaxBins bins, the largest per-wave LDS histogram check_params accepts"""
+    p = sc.loop_params("edge")
+    assert ref.sizes(p)[1] + 1 == 256 and liw.loop.sizes(p) == ref.sizes(p)
+    _check_match_map(liw, synth, "edge", 5, stride=3)
+
+
+MATCH_PIECES = dict(office=26, edge=26, fine=60, coarse=60)   # the fine and coarse sets accept fewer pairs: more pieces, for > 100 accepted
+
+
+def match_case(cfg, thr):
+    """-> (parameters, feature point sets) of the match_map comparison at a set and threshold"""
     rng = np.random.default_rng(20 + thr)
-    p = _params(min_match_threshold=thr, max_dis=1e9)
-    det, rd = _pair(liw, synth, p, max_points=64)
+    p = _set_params(cfg, min_match_threshold=thr, max_dis=1e9)
     L = _landmarks(rng, extent=6.0, spacing=0.8, jitter=0.25)
-    feats = _match_features(rng, L)
+    return p, _match_features(rng, L, MATCH_PIECES[cfg])
+
+
+def _check_match_map(liw, synth, cfg, thr, stride=2):
+    p, feats = match_case(cfg, thr)
+    det, rd = _pair(liw, synth, p, max_points=64, cfg=cfg)
     _feed(det, rd, [(np.eye(4), F, True) for F in feats])
+    assert len(feats) <= 256                                    # _pair's max_keyframes
     ref.QUICK_COUNTS.clear()
     margins, sizes, compared, accepted, repeated = [], set(), 0, 0, 0
     K = len(feats)
     for q in range(K):
         for c in range(K):
-            if q == c or (q + c) % 2:      # half the ordered pairs keep the run time modest
+            if q == c or (q + c) % stride:      # half the ordered pairs keep the run time modest
                 continue
             want = ref.match_map(rd.features[q], rd.features[c], q, c, p, margins)
             got = det.match(q, c)
@@ -198,6 +300,7 @@ def test_match_map_equals_the_serial_walk(liw, synth, thr):
                 assert got["p1"].tolist() == want["p1"] and got["p2"].tolist() == want["p2"], (q, c)
                 accepted += 1
             compared += 1
+    print("match_map at the %s set, threshold %d: %d pairs compared, %d accepted, smallest bin margin %.3e" % (cfg, thr, compared, accepted, min(margins)))
     assert compared > 300 and accepted > 20 and repeated > 20
     assert thr in sizes and thr + 1 in sizes          # best sizes of exactly threshold (rejected) and threshold + 1 (accepted)
     assert thr - 1 in ref.QUICK_COUNTS and thr in ref.QUICK_COUNTS   # quick-filter counts at the edge
@@ -205,8 +308,9 @@ def test_match_map_equals_the_serial_walk(liw, synth, thr):
 
 
 # ------------------------------------------------------------------------------------------------------------------ detect
-def _loop_sequence(rng, L, T_iw, K=30, drift=None, spin0=0.0, revisit=True, r=2.5):
-    """planar base poses: frames 0..9 near the origin, 10..19 far away, 20..29 back (if revisit) in a drifting tracking world;
+def _loop_sequence(rng, L, T_iw, K=30, drift=None, spin0=0.0, revisit=True, r=2.5, offset=(0.04, -0.03, 0.03)):
+    """planar base poses: frames 0..9 near the origin, 10..19 far away, 20..29 back (if revisit), `offset` (x, y, yaw) from the
+    first leg, in a drifting tracking world;
     -> frames (tracking IMU pose = base pose * T_imu_to_wheel^-1, world-frame corners, laser) and the true IMU poses"""
     frames, truth = [], []
     for k in range(K):
@@ -216,7 +320,7 @@ def _loop_sequence(rng, L, T_iw, K=30, drift=None, spin0=0.0, revisit=True, r=2.
             B = _pose(-10.0 + 0.7 * (k - 10), 6.0, 0.5)
         else:
             j = k - 20
-            B = _pose(0.05 * j + 0.04, 0.02 * j - 0.03, 0.01 * j + 0.03)
+            B = _pose(0.05 * j + offset[0], 0.02 * j + offset[1], 0.01 * j + offset[2])
         D = drift if (drift is not None and k >= 20) else np.eye(4)
         C = _seen(L, B, r=r, drift=D, noise=0.001, rng=rng, spin=spin0 if k == 0 else 0.0)
         T = B @ ref.iso_inv(T_iw)
@@ -240,11 +344,25 @@ def _run_detect(det, rd, frames):
     return edges
 
 
+DETECT_SECOND = dict(   # sequence keywords of the detect tests at the second sets (tests/test_second_config_frontend.py: what they reach)
+    earlier=dict(drift=(0.2, 0.0, 0.02), offset=(0.9, -0.03, 0.03)),    # origin distances between max_tf_p and max_dis that give edges
+    one=dict(drift=(0.45, -0.2, 0.05)))                                 # |dp| of the tf gate between max_tf_q and max_tf_p, accepted
+
+
 def test_detect_earlier_candidate_wins(liw, synth):
+    _check_detect_earlier_candidate_wins(liw, synth, "office", dict(drift=(0.2, -0.1, 0.05)))
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+def test_detect_earlier_candidate_wins_second_sets(liw, synth, cfg):
+    _check_detect_earlier_candidate_wins(liw, synth, cfg, DETECT_SECOND["earlier"])
+
+
+def _check_detect_earlier_candidate_wins(liw, synth, cfg, skw):
     rng = np.random.default_rng(5)
-    p = _params(submap_count=3)
-    det, rd = _pair(liw, synth, p)
-    frames, truth = _loop_sequence(rng, _landmarks(rng), det.T_imu_to_wheel, drift=_pose(0.2, -0.1, 0.05))
+    p = _set_params(cfg, submap_count=3)
+    det, rd = _pair(liw, synth, p, cfg=cfg)
+    frames, truth = _loop_sequence(rng, _landmarks(rng), det.T_imu_to_wheel, **dict(skw, drift=_pose(*skw["drift"])))
     edges = _run_detect(det, rd, frames)
     assert edges and all(e["index1"] >= 20 for e in edges)
     e = edges[-1]
@@ -257,9 +375,18 @@ def test_detect_earlier_candidate_wins(liw, synth):
 
 
 def test_detect_skips_a_candidate_rejected_by_the_tf_gate(liw, synth):
+    _check_detect_skips_rejected(liw, synth, "office")
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+def test_detect_skips_a_candidate_rejected_by_the_tf_gate_second_sets(liw, synth, cfg):
+    _check_detect_skips_rejected(liw, synth, cfg)
+
+
+def _check_detect_skips_rejected(liw, synth, cfg):
     rng = np.random.default_rng(6)
-    p = _params(submap_count=1)
-    det, rd = _pair(liw, synth, p)
+    p = _set_params(cfg, submap_count=1)
+    det, rd = _pair(liw, synth, p, cfg=cfg)
     frames, _ = _loop_sequence(rng, _landmarks(rng), det.T_imu_to_wheel, spin0=0.8)
     q = None
     for k, (T, C, laser) in enumerate(frames):
@@ -279,18 +406,36 @@ def test_detect_skips_a_candidate_rejected_by_the_tf_gate(liw, synth):
 
 
 def test_detect_without_revisit_gives_no_edge(liw, synth):
+    _check_detect_without_revisit(liw, synth, "office")
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+def test_detect_without_revisit_gives_no_edge_second_sets(liw, synth, cfg):
+    _check_detect_without_revisit(liw, synth, cfg)
+
+
+def _check_detect_without_revisit(liw, synth, cfg):
     rng = np.random.default_rng(7)
-    p = _params(submap_count=3)
-    det, rd = _pair(liw, synth, p)
+    p = _set_params(cfg, submap_count=3)
+    det, rd = _pair(liw, synth, p, cfg=cfg)
     frames, _ = _loop_sequence(rng, _landmarks(rng), det.T_imu_to_wheel, revisit=False)
     assert _run_detect(det, rd, frames) == []
 
 
 def test_detect_submap_count_one(liw, synth):
+    _check_detect_submap_count_one(liw, synth, "office", (-0.15, 0.1, -0.04))
+
+
+@pytest.mark.parametrize("cfg", SECOND_SETS)
+def test_detect_submap_count_one_second_sets(liw, synth, cfg):
+    _check_detect_submap_count_one(liw, synth, cfg, DETECT_SECOND["one"]["drift"])
+
+
+def _check_detect_submap_count_one(liw, synth, cfg, drift):
     rng = np.random.default_rng(8)
-    p = _params(submap_count=1)
-    det, rd = _pair(liw, synth, p)
-    frames, _ = _loop_sequence(rng, _landmarks(rng), det.T_imu_to_wheel, drift=_pose(-0.15, 0.1, -0.04))
+    p = _set_params(cfg, submap_count=1)
+    det, rd = _pair(liw, synth, p, cfg=cfg)
+    frames, _ = _loop_sequence(rng, _landmarks(rng), det.T_imu_to_wheel, drift=_pose(*drift))
     edges = _run_detect(det, rd, frames)
     assert edges
     assert np.array_equal(det.status(25)["origin"], np.eye(4))   # the origin stays identity (the loop breaks before setting it)

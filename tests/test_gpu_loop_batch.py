@@ -14,12 +14,12 @@ GUARD = 256
 TF_BAR = 1e-9      # the bar of the single detector's own detect tests: host libm against liw_crmath, pose -> tf12
 
 
-def _fleet(liw, synth, p, B, K, P, Cc, guard=0):
-    return liw.FleetLoopDetector(synth.office_params(), p, dict(B=B, max_keyframes=K, max_points=P, max_kf_corners=Cc), guard=guard)
+def _fleet(liw, synth, p, B, K, P, Cc, guard=0, cfg="office"):
+    return liw.FleetLoopDetector(tgl._set_prm(synth, cfg), p, dict(B=B, max_keyframes=K, max_points=P, max_kf_corners=Cc), guard=guard)
 
 
-def _single(liw, synth, p, K, P):
-    return liw.loop.LoopDetector(synth.office_params(), p, dict(max_keyframes=K, max_points=P))
+def _single(liw, synth, p, K, P, cfg="office"):
+    return liw.loop.LoopDetector(tgl._set_prm(synth, cfg), p, dict(max_keyframes=K, max_points=P))
 
 
 def _upload(torch, B, stride, items):
@@ -56,12 +56,24 @@ def _same_feature(liw, fl, b, det, k):
 # --------------------------------------------------------------------------------------------------------------------- 1
 def test_features_bit_identical(liw, synth):
     """Measured on an MI355X: 1 629 descriptor rows of 53 key frames, every byte equal."""
+    _check_features_bit_identical(liw, synth, "office")
+
+
+@pytest.mark.parametrize("cfg", tgl.SECOND_SETS)
+def test_features_bit_identical_second_sets(liw, synth, cfg):
+    """k_floop_gather's near = d_res / 2 and far = 5 d_res and the shared descriptor body at a_res != d_res.  The hand-placed corners
+    of the office case are scaled by d_res / 0.03 where their distances are what the case is about."""
+    _check_features_bit_identical(liw, synth, cfg)
+
+
+def _check_features_bit_identical(liw, synth, cfg):
     import torch
     rng = np.random.default_rng(101)
     B, F, K, P, Cc, stride = 6, 14, 16, 64, 40, 48
-    p = tgl._params(submap_count=3)
-    fl = _fleet(liw, synth, p, B, K, P, Cc, guard=GUARD)
-    dets = [_single(liw, synth, p, K, P) for _ in range(B)]
+    p = tgl._set_params(cfg, submap_count=3)
+    sc_ = p["d_res"] / 0.03                 # 1.0 at the office set
+    fl = _fleet(liw, synth, p, B, K, P, Cc, guard=GUARD, cfg=cfg)
+    dets = [_single(liw, synth, p, K, P, cfg=cfg) for _ in range(B)]
     L = tgl._landmarks(rng)
     keyed = [lambda t: True, lambda t: t % 2 == 0, lambda t: t % 3 != 0, lambda t: t >= 2, lambda t: t not in (1, 5, 6), lambda t: False]
     count = [0] * B
@@ -79,7 +91,7 @@ def test_features_bit_identical(liw, synth):
             n = 22 if j in (4, 5) else (21 if j == 6 else 10)
             Cn = np.stack([np.arange(n) * 1.0 + 100.0, np.full(n, 1.0 * j), np.zeros(n)], axis=1)
         if b == 3 and j == 3:
-            Cn = np.concatenate([Cn, [[40000.0, 0.0, 0.0]]])                 # dij = 1 333 333 >= 2^20 - 1
+            Cn = np.concatenate([Cn, [[40000.0 * sc_, 0.0, 0.0]]])           # dij = 1 333 333 >= 2^20 - 1
         if b == 4 and j == 2:
             Cn = np.concatenate([Cn, np.stack([np.arange(Cc + 1 - len(Cn)) * 1.0 + 50.0, np.full(Cc + 1 - len(Cn), -30.0), np.zeros(Cc + 1 - len(Cn))], axis=1)])
             assert len(Cn) == Cc + 1                                         # one key frame over max_kf_corners
@@ -134,7 +146,7 @@ def test_features_bit_identical(liw, synth):
     buf = fl._buf
     assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[-GUARD:] == 0xA5).all())
     assert not bool(fl.full().any())
-    print("features: %d rows of %d key frames bit-identical (keys, j, aij, quick_des, points, origins)" % (rows, sum(count)))
+    print("features at the %s set: %d rows of %d key frames bit-identical (keys, j, aij, quick_des, points, origins)" % (cfg, rows, sum(count)))
     fl.close()
 
 
@@ -143,11 +155,21 @@ def test_features_bit_identical_at_sort_and_lane_edges(liw, synth, n):
     """Sub-maps of n points, where the shared descriptor body's sort padding and lane strides change (tgl.DESCRIBE_EDGE_N), for two
     robots against the single detector: every byte of keys, aij and quick_des.  With max_points = 130 the describe grid has 128
     blocks per robot, so at n = 129 one wave also runs a second point in the same LDS."""
+    _check_features_at_edges(liw, synth, n, "office")
+
+
+@pytest.mark.parametrize("cfg", tgl.SECOND_SETS)
+@pytest.mark.parametrize("n", tgl.DESCRIBE_EDGE_N)
+def test_features_bit_identical_at_sort_and_lane_edges_second_sets(liw, synth, n, cfg):
+    _check_features_at_edges(liw, synth, n, cfg)
+
+
+def _check_features_at_edges(liw, synth, n, cfg):
     import torch
-    C_, _ = tgl.describe_edge_case(n)
+    C_, _ = tgl.describe_edge_case(n, cfg)
     B, P = 2, tgl.DESCRIBE_EDGE_CAP
-    p = tgl._params()
-    fl, det = _fleet(liw, synth, p, B, 2, P, P, guard=GUARD), _single(liw, synth, p, 2, P)
+    p = tgl._set_params(cfg)
+    fl, det = _fleet(liw, synth, p, B, 2, P, P, guard=GUARD, cfg=cfg), _single(liw, synth, p, 2, P, cfg=cfg)
     inp = _upload(torch, B, P, [(np.zeros(6), C_)] * B)
     assert fl.add_keyframes(inp["key"], inp["pose"], inp["acc"], inp["n_acc"]).tolist() == [1] * B
     assert det.add_keyframe(cases.make_tf(np.zeros(6)), C_) == 0
@@ -159,11 +181,11 @@ def test_features_bit_identical_at_sort_and_lane_edges(liw, synth, n):
 
 
 # --------------------------------------------------------------------------------------------------------------------- 2
-def _frame_items(robots, t):
-    seqs = cases.sequences()
+def _frame_items(robots, t, cfg="office"):
+    seqs = cases.sequences(cfg)
     items = []
     for r in robots:
-        off = cases.ROBOTS[r][4]
+        off = cases.robots(cfg)[r][4]
         if off <= t < off + cases.KEYFRAMES:
             pose, _, Cn = seqs[r][t - off]
             items.append((pose, Cn))
@@ -178,19 +200,30 @@ def _stats_row(d):
 
 def test_detection_equals_the_single_detectors(liw, synth):
     """Measured on an MI355X: 320 robot-frames, 60 edges, index pair, size and stats equal, tf12 max difference 3.9e-16 (bar 1e-9)."""
+    _check_detection(liw, synth, "office")
+
+
+@pytest.mark.parametrize("cfg", tgl.SECOND_SETS)
+def test_detection_equals_the_single_detectors_second_sets(liw, synth, cfg):
+    """the sequences of loop_batch_cases.ROBOTS_SECOND with detectors created from skewed_params: a generic T_imu_to_wheel through the
+    Tiw, inv_iw conjugation of the tf gate, max_dis != max_tf_p with gate values between the two, a_res != d_res"""
+    _check_detection(liw, synth, cfg)
+
+
+def _check_detection(liw, synth, cfg):
     import torch
-    res = cases.restatement()
+    res = cases.restatement(cfg)
     for r in res:
         assert cases.near_threshold(r["gates"]) == []       # no decision within 1e-6 relative of its threshold
     worst, edges, compared = 0.0, 0, 0
     for S, robots in cases.SETS.items():
-        p, P = cases.params(S), cases.MAX_POINTS[S]
+        p, P = cases.params(S, cfg), cases.MAX_POINTS[S]
         B, K, stride = len(robots), 32, 256
-        fl = _fleet(liw, synth, p, B, K, P, stride)
-        dets = [_single(liw, synth, p, K, P) for _ in robots]
+        fl = _fleet(liw, synth, p, B, K, P, stride, cfg=cfg)
+        dets = [_single(liw, synth, p, K, P, cfg=cfg) for _ in robots]
         first_detect = set()
         for t in range(cases.FRAMES):
-            items = _frame_items(robots, t)
+            items = _frame_items(robots, t, cfg)
             out = fl.push(_upload(torch, B, stride, items))
             found, edge, tf12, stats = [out[k].cpu().numpy() for k in ("found", "edge", "tf12", "stats")]
             for b, it in enumerate(items):
@@ -198,7 +231,7 @@ def test_detection_equals_the_single_detectors(liw, synth):
                 if it is None:
                     assert found[b] == 0, (S, t, b)
                     continue
-                r, kf = robots[b], t - cases.ROBOTS[robots[b]][4]
+                r, kf = robots[b], t - cases.robots(cfg)[robots[b]][4]
                 assert dets[b].add_keyframe(cases.make_tf(it[0]), it[1]) == kf
                 want = dets[b].detect()
                 ws = dets[b].last_stats()
@@ -221,7 +254,7 @@ def test_detection_equals_the_single_detectors(liw, synth):
             assert [fl.status(b, k)["n_points"] for k in range(cases.KEYFRAMES)] == res[r]["n_points"]
         fl.close()
     assert compared == 8 * cases.FRAMES and edges >= 40
-    print("detection: %d robot-frames, %d edges equal (index1, index2, size, stats); tf12 max difference %.3e" % (compared, edges, worst))
+    print("detection at the %s set: %d robot-frames, %d edges equal (index1, index2, size, stats); tf12 max difference %.3e" % (cfg, compared, edges, worst))
     assert worst <= TF_BAR
 
 

@@ -58,8 +58,8 @@ def _room_case(rng, K, n_rays, tilt=0.03, room=None):
     return np.array(tfs), subs
 
 
-def _map(liw, synth, dims=SMALL, res=RES):
-    return liw.gridmap.GridMap(synth.office_params(), dict(resolution=res), dims)
+def _map(liw, synth, dims=SMALL, res=RES, prm=None):
+    return liw.gridmap.GridMap(synth.office_params() if prm is None else prm, dict(resolution=res), dims)
 
 
 def _assert_equal(info, grid, want):
@@ -206,12 +206,32 @@ def test_sub_maps_revisiting_the_same_walls(liw, synth):
     _assert_equal(m.render_tf(tfs[2:3]), m.grid(), ref.render(tfs[2:3], subs[2:3], RES))
 
 
-def test_render_with_poses_equals_render_tf(liw, synth):
+def _poses_case():
+    """five sub-maps of the replay room and five 6-dof poses to render them at (shared with tests/test_second_config_frontend.py)"""
     rng = np.random.default_rng(9)
     _, subs = _room_case(rng, 5, 50)
     poses = np.concatenate([rng.uniform(-3, 3, (5, 3)), rng.uniform(-0.4, 0.4, (5, 3))], axis=1)
     poses[:, 5] = rng.uniform(-3, 3, 5)
-    m = _map(liw, synth)
+    return subs, poses
+
+
+def test_render_with_poses_equals_render_tf(liw, synth):
+    _check_render_with_poses(liw, synth, None)
+
+
+def test_render_with_poses_equals_render_tf_skewed_extrinsic(liw, synth):
+    """the same at second_config.skewed_params: a generic laser rotation, which the loader's quaternion round trip changes, and another
+    translation, so a transposed or office T_imu_to_laser in the composition cannot pass"""
+    import second_config as sc
+    _check_render_with_poses(liw, synth, sc.skewed_params(synth))
+
+
+def _check_render_with_poses(liw, synth, prm):
+    subs, poses = _poses_case()
+    m = _map(liw, synth, prm=prm)
+    if prm is not None:
+        import second_config as sc
+        assert np.array_equal(m.T_imu_to_laser, sc.held_extrinsic(liw, prm))
     for s in subs:
         m.add_submap(s)
     L = liw.lib()

@@ -306,9 +306,18 @@ def test_isolation_and_determinism(liw, synth):
 
 # ------------------------------------------------------------------------------------------------------------------ 6. render from poses
 def test_render_from_poses(liw, synth):
+    _check_render_from_poses(liw, synth, synth.office_params())
+
+
+def test_render_from_poses_skewed_extrinsic(liw, synth):
+    """k_fmap_tf's make_tf(p, q) * T_imu_to_laser at second_config.skewed_params: a generic laser rotation that the loader's quaternion round trip changes"""
+    import second_config as sc
+    _check_render_from_poses(liw, synth, sc.skewed_params(synth))
+
+
+def _check_render_from_poses(liw, synth, prm):
     import torch
     rng = np.random.default_rng(61)
-    prm = synth.office_params()
     rooms = mc.rooms(3)
     h = np.pi / 2
     yaws = [h, -h, np.nextafter(h, 0.0), np.nextafter(h, 4.0), -np.nextafter(h, 0.0), -np.nextafter(h, 4.0), h + 1e-9, -h - 1e-9,
