@@ -319,7 +319,10 @@ class BatchSolver:
         flags, rows, blocks = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
         self._chk(self.L.liw_batch_launch_paths(self.h, C.byref(self.b), self._wsp(), C.byref(flags)))
         self._chk(self.L.liw_batch_packed_rows(self.h, C.byref(self.b), self._wsp(), C.byref(rows), C.byref(blocks)))
+        kern = C.c_int(0)
+        self._chk(self.L.liw_batch_step_kernel(self.h, C.byref(self.b), C.byref(kern)))
         return dict(flags=flags.value, large_batch_format=bool(flags.value & 1), lane_per_group_laser=bool(flags.value & 2), packed_rows=rows.value,
+                    step_kernel=("k_lm_step", "k_lm_step_quad", "k_lm_step_quad_pair")[kern.value],
                     blocks=blocks.value, padding_ratio=(64.0 * rows.value / blocks.value) if (rows.value and blocks.value) else None)
 
     # ---- LM pieces

@@ -2232,6 +2232,7 @@ void launch_lm_step(const StepArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k_lm_step_slow, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a2);
         return;
     }
+    note_step_kernel(0);
     // a two-frame window (what the reference's tracking loop solves every laser frame) is ONE dense 30 x 30 system
     if (a.n == 2 && step_variant_is(f, STEP_DENSE2, true)) hipLaunchKernelGGL(k_lm_step_dense2, dim3(a.B), dim3(64), 0, s, a);
     // two waves per window while that takes no CUs away from other windows and the chain is worth cutting (tools/step_variant_sweep.py: 97 k vs 67 k solves/s at 256 windows, 120 k vs 116 k at 512)

@@ -65,7 +65,9 @@ __device__ __forceinline__ double row_max(double v) {
 // phase stamps (tools/clk_probe_quad.py): s_memtime of one wave at one frame of one LM iteration; dormant unless switched on
 __device__ long long g_qclk[64];
 __device__ int g_qclk_on[4];   // on, block, frame, iteration
-#define QSTAMP(id) do { if (clk_on && i == clk_frame) { if (lane == 0) g_qclk[(id)] = clock64(); } } while (0)
+// (k_lm_step_quad_pair: the eliminator wave stamps entries 0 .. 15, the assembler wave 32 .. 47 — `isA` of lm_step_quad_body, like
+// clk_on, clk_frame, lane and the frame index i, is taken from the scope the macro is used in)
+#define QSTAMP(id) do { if (clk_on && i == clk_frame) { if (lane == 0) g_qclk[(id) + (isA ? 32 : 0)] = clock64(); } } while (0)
 
 constexpr int QTR = 4 * 15 * 6;                           // transposition tile of the carried arrow block (below)
 // Gather table of the assembly phase: one 16-bit LDS byte offset per (read, lane) — see the kernel.  Reads: K_A laser Hbb | gb, K_B wheel
@@ -113,6 +115,7 @@ template <int KIND, int R> __device__ __forceinline__ int quad_code(bool track, 
     return c == 0xff ? -1 : c;
 }
 __device__ __forceinline__ double flip_sign(double x, unsigned m) { return __hiloint2double(__double2hiint(x) ^ (int)m, __double2loint(x)); }   // m: 0x80000000 or 0
+__device__ __forceinline__ void launder(unsigned& x) { asm volatile("" : "+v"(x)); }   // the compiler forgets what it knew about x
 constexpr int BSD2 = 3;   // frames of second-sweep records in flight (2: 30 kB of LDS per wave instead of 38, same speed alone — co-residency experiments)
 constexpr int QTOT_2 = BSD2 * (((4 * REC_GS + 127) / 128) * 128 + 6 * 32);             // second sweep: three frames of records + state / scale / diagonal entries
 constexpr int QTOT = QTOT_1 > QTOT_2 ? QTOT_1 : QTOT_2;   // LDS doubles per wave: the prefetched partial records of its four rows, the tile, a zero word, the gather table (35.6 kB: four waves per CU)
@@ -123,8 +126,30 @@ template <int R> __device__ __forceinline__ int tri_rc(int j, int cj) {   // cj 
     return R <= j ? cR + j : cj + R;
 }
 
-__global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
-    __shared__ double S[QTOT];
+// ---- k_lm_step_quad_pair: the same step with the frame's work split between TWO waves of one work-group (one quad of windows):
+//   wave A, the assembler, one frame ahead: LDS-DMA prefetch of the frame's records, assembly, gradient max-norm / checksum, LM diagonal,
+//           the wheel share of frame i-1 — everything that does not depend on the elimination of the frame behind — and hands the UNSCALED
+//           tile (d, o, the six arrow rows of lanes 0 .. 5, dmp, cw, scm) to E through LDS;
+//   wave E, the eliminator: prologue, Jacobi scaling, carried terms, Cholesky, Schur, back operators, record store, second sweep.
+// Two work-group barriers per frame (tile written, tile consumed).  Every value is produced by the operations of k_lm_step_quad in their
+// order (the scaling FMAs stay in E with their unrounded products), so the two kernels agree bit for bit.  Both waves share one register
+// count (<= 256: two waves per SIMD, four work-groups per CU); the gather table of the assembly lives in 26 registers of wave A instead
+// of LDS, which makes room for the hand-off tile:
+constexpr int QT_DO = 0;                                  // (d[r], o[r]) of lane l at QT_DO + r * 128 + 2 l
+constexpr int QT_RR = QT_DO + 15 * 128;                   // arrow rows, lanes 0 .. 5 only: w * 36 + j * 6 + r
+constexpr int QT_CW = QT_RR + 4 * 36;                     // wheel share, lanes 0 .. 5 and 15 (role 6): w * 42 + role * 6 + r
+constexpr int QT_DS = QT_CW + 4 * 42;                     // (dmp, scm) of lane l at QT_DS + 2 l
+constexpr int QT_GM = QT_DS + 128;                        // after frame 0: gradient max-norm [w], checksum [4 + w]
+constexpr int QTILE = QT_GM + 8;
+constexpr int QTOT_P1 = 4 * (PIFS + LPC + PWS + PGS) + QPAD + QTR + QZB + QTILE;
+constexpr int QTOT_P = QTOT_P1 > QTOT_2 ? QTOT_P1 : QTOT_2;
+static_assert(8 * QTOT_P <= 40960, "pair kernel: four work-groups per CU");
+
+// The body of both kernels.  WHO = 0: one wave does everything (k_lm_step_quad); 1: the assembler wave of the pair kernel, 2: its
+// eliminator wave.  (Two instantiations, not one loop with a branch on the wave: there the carried registers of both are live in each.)
+template <int WHO> __device__ __forceinline__ void lm_step_quad_body(const StepArgs& a, double* const S) {
+    constexpr bool PAIR = WHO != 0, isA = WHO == 1;
+    constexpr int who = WHO;
     const int lane = threadIdx.x & 63, j = lane & 15, w = lane >> 4;
     const int n = a.n;
     // TRACK topology (solver.cpp:631-820): p, q of every frame but the newest are constant (fast mode: its biases too), laser blocks tie
@@ -154,128 +179,148 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
                        LM_X0 = offsetof(LmState, x0) / 8;
     const unsigned oX = (unsigned)b * (unsigned)(n * 15), oLM = (unsigned)b * LMS;
     LmState& st = a.w.lm[b];
-    act = act && !st.done;
-    const int have_cand = st.have_candidate;
-    {
-        const double sl = quad_slow_lane(X + oX, XC + oX, have_cand, n, j, 16) ? 1.0 : 0.0;
-        act = act && !(row_max(sl) > 0.0);
-    }
-    // windows this launch steps are marked: the one-wave kernel launched behind it (only_slow) takes exactly the unmarked ones — it cannot
-    // repeat the test above, because by then this kernel has written new candidates
-    if (act && j == 0) st.pad_ = 1;
-    if (!__any(act)) return;
+    int reuse = 0, cur = 0, iteration = 0;
+    bool proceed = false, last_successful = true, fresh = false, clk_k = false;
+    double inv_radius = 0.0;
+    // The launch's head: which rows step, the prologue.  -> false: no row of the wave goes on.  (PAIR: wave E alone runs it — it reads
+    // and writes the LM state and the states — and hands `proceed`, `reuse`, `cur`, the iteration and 1 / radius to wave A below.)
+    auto head = [&]() -> bool {
+        act = act && !st.done;
+        const int have_cand = st.have_candidate;
+        {
+            const double sl = quad_slow_lane(X + oX, XC + oX, have_cand, n, j, 16) ? 1.0 : 0.0;
+            act = act && !(row_max(sl) > 0.0);
+        }
+        // windows this launch steps are marked: the one-wave kernel launched behind it (only_slow) takes exactly the unmarked ones — it cannot
+        // repeat the test above, because by then this kernel has written new candidates
+        if (act && j == 0) st.pad_ = 1;
+        if (!__any(act)) return false;
 
-    int reuse = st.reuse_diagonal, cur = st.cur;
-    const int iteration = st.iteration;
-    bool proceed = act, last_successful = true;
-    const bool fresh = iteration == 0 && !have_cand;
-    const bool clk_k = g_qclk_on[0] && (int)blockIdx.x == g_qclk_on[1] && iteration == g_qclk_on[3] && lane == 0;
-    if (clk_k) g_qclk[12] = clock64();
-    double inv_radius;
-    // ---------------------------------------------------------------- prologue: cost of the initial point / the pending candidate,
-    //      accept / reject, Ceres' termination tests (liw_lm_rules.hpp), per row
-    {
-        double radius = st.radius, dec = st.decrease_factor, x_cost = st.x_cost, x_norm = st.x_norm;
-        const int max_iters = st.max_iters, successful0 = st.successful;
-        int successful = successful0;
-        const double model0 = st.model_cost_change, cand_step_norm = st.cand_step_norm, initial_cost0 = st.initial_cost;
-        double minimum_cost = st.minimum_cost, initial_cost = initial_cost0;
-        const int cb = (fresh || !have_cand) ? cur : 1 - cur;
-        double cost;
+        reuse = st.reuse_diagonal; cur = st.cur;
+        iteration = st.iteration;
+        proceed = act;
+        fresh = iteration == 0 && !have_cand;
+        clk_k = g_qclk_on[0] && (int)blockIdx.x == g_qclk_on[1] && iteration == g_qclk_on[3] && lane == 0;
+        if (clk_k) g_qclk[12] = clock64();
+        // ---------------------------------------------------------------- prologue: cost of the initial point / the pending candidate,
+        //      accept / reject, Ceres' termination tests (liw_lm_rules.hpp), per row
         {
-            // the records' cost slots, from the compact copy the roles keep (liw_kernels.hpp, cs_index): 8 lines per window instead of 4 n - 2
-            const double* CSb = (cb ? a.w.CS[1] : a.w.CS[0]) + cs_index(n, b, 0, 0);
-            double s = 0.0;
-            for (int i = j; i < n; i += 16) {   // (blocks whose parameters are all constant are not in Ceres' problem)
-                s += CSb[CS_LASER * n + i];
-                if (!(track && i < n - 1)) s += CSb[CS_GROUND * n + i];
-            }
-            for (int k = j; k < n - 1; k += 16) {
-                s += CSb[CS_IMU * n + k];
-                if (!(track && k < n - 2)) s += CSb[CS_WHEEL * n + k];
-            }
-            if (track && !fast && a.has_prior[b] && j < 15) {   // marginalization_factor: r = linearized_J (x_{n-2} - linearized_X)  (:22-53)
-                const double* xs = ((fresh || !have_cand) ? X : XC) + oX + (unsigned)((n - 2) * 15);
-                const double* pJ = a.prior_J + (size_t)b * 225 + j * 15;
-                const double* pX = a.prior_X + (size_t)b * 15;
-                double r = 0.0;
-#pragma unroll
-                for (int q = 0; q < 15; ++q) r += pJ[q] * (xs[q] - pX[q]);
-                s += r * r;
-            }
-            cost = 0.5 * row_sum(s);
-        }
-        int term = 0;
-        bool accept = false, fail_eval = false;
-        if (fresh) {
-            x_cost = cost; initial_cost = cost; minimum_cost = cost;
-            fail_eval = !isfinite(cost);          // IterationZero: non-finite residual -> FAILURE, nothing applied (Jacobians: after the sweep below)
-        } else if (have_cand) {
-            const double cand_cost = isfinite(cost) ? cost : kFailedEvalCost;
-            term = lm_candidate_term(cand_step_norm, x_norm, x_cost, cand_cost);
-            if (!term) {
-                const double rho = (x_cost - cand_cost) / model0;
-                accept = lm_accepts(rho);
-                if (accept) {
-                    cur = cb; x_cost = cand_cost;
-                    lm_step_accepted(rho, radius, dec, reuse);
-                    successful += 1;
-                    if (x_cost < minimum_cost) minimum_cost = x_cost;
-                } else {
-                    lm_step_rejected(radius, dec, reuse);
-                    last_successful = false;
+            double radius = st.radius, dec = st.decrease_factor, x_cost = st.x_cost, x_norm = st.x_norm;
+            const int max_iters = st.max_iters, successful0 = st.successful;
+            int successful = successful0;
+            const double model0 = st.model_cost_change, cand_step_norm = st.cand_step_norm, initial_cost0 = st.initial_cost;
+            double minimum_cost = st.minimum_cost, initial_cost = initial_cost0;
+            const int cb = (fresh || !have_cand) ? cur : 1 - cur;
+            double cost;
+            {
+                // the records' cost slots, from the compact copy the roles keep (liw_kernels.hpp, cs_index): 8 lines per window instead of 4 n - 2
+                const double* CSb = (cb ? a.w.CS[1] : a.w.CS[0]) + cs_index(n, b, 0, 0);
+                double s = 0.0;
+                for (int i = j; i < n; i += 16) {   // (blocks whose parameters are all constant are not in Ceres' problem)
+                    s += CSb[CS_LASER * n + i];
+                    if (!(track && i < n - 1)) s += CSb[CS_GROUND * n + i];
                 }
-            }
-        } else {
-            last_successful = false;   // previous step was invalid
-        }
-        // states: accepted candidate -> live states; a failed evaluation hands back the states the solve started from; x0 / x_norm
-        {
-            double s2 = 0.0;
-            const bool restore = act && fail_eval && !fresh && successful0 > 0;
-            const bool hist = act && a.w.history && iteration < a.w.history_records && !fail_eval;
-            for (int e0 = j; e0 < n * 15; e0 += 16 * 8) {      // eight entries per lane at a time: their loads are in flight together
-                double xv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int e = e0 + 16 * q;
-                    const unsigned ee = (unsigned)(e < n * 15 ? e : j);
-                    xv[q] = restore ? LMD[oLM + LM_X0 + ee] : (accept ? XC[oX + ee] : X[oX + ee]);
+                for (int k = j; k < n - 1; k += 16) {
+                    s += CSb[CS_IMU * n + k];
+                    if (!(track && k < n - 2)) s += CSb[CS_WHEEL * n + k];
                 }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int e = e0 + 16 * q;
-                    if (e < n * 15) {
-                        if (act && (accept || restore)) X[oX + (unsigned)e] = xv[q];
-                        if (act && fresh) LMD[oLM + LM_X0 + (unsigned)e] = xv[q];
-                        if (!is_const(e / 15, e % 15)) s2 += xv[q] * xv[q];
-                        if (hist) a.w.history[((size_t)iteration * a.B + b) * (size_t)(n * 15) + e] = xv[q];
+                if (track && !fast && a.has_prior[b] && j < 15) {   // marginalization_factor: r = linearized_J (x_{n-2} - linearized_X)  (:22-53)
+                    const double* xs = ((fresh || !have_cand) ? X : XC) + oX + (unsigned)((n - 2) * 15);
+                    const double* pJ = a.prior_J + (size_t)b * 225 + j * 15;
+                    const double* pX = a.prior_X + (size_t)b * 15;
+                    double r = 0.0;
+    #pragma unroll
+                    for (int q = 0; q < 15; ++q) r += pJ[q] * (xs[q] - pX[q]);
+                    s += r * r;
+                }
+                cost = 0.5 * row_sum(s);
+            }
+            int term = 0;
+            bool accept = false, fail_eval = false;
+            if (fresh) {
+                x_cost = cost; initial_cost = cost; minimum_cost = cost;
+                fail_eval = !isfinite(cost);          // IterationZero: non-finite residual -> FAILURE, nothing applied (Jacobians: after the sweep below)
+            } else if (have_cand) {
+                const double cand_cost = isfinite(cost) ? cost : kFailedEvalCost;
+                term = lm_candidate_term(cand_step_norm, x_norm, x_cost, cand_cost);
+                if (!term) {
+                    const double rho = (x_cost - cand_cost) / model0;
+                    accept = lm_accepts(rho);
+                    if (accept) {
+                        cur = cb; x_cost = cand_cost;
+                        lm_step_accepted(rho, radius, dec, reuse);
+                        successful += 1;
+                        if (x_cost < minimum_cost) minimum_cost = x_cost;
+                    } else {
+                        lm_step_rejected(radius, dec, reuse);
+                        last_successful = false;
                     }
                 }
+            } else {
+                last_successful = false;   // previous step was invalid
             }
-            s2 = row_sum(s2);
-            if (fresh || accept) x_norm = sqrt(s2);
+            // states: accepted candidate -> live states; a failed evaluation hands back the states the solve started from; x0 / x_norm
+            {
+                double s2 = 0.0;
+                const bool restore = act && fail_eval && !fresh && successful0 > 0;
+                const bool hist = act && a.w.history && iteration < a.w.history_records && !fail_eval;
+                for (int e0 = j; e0 < n * 15; e0 += 16 * 8) {      // eight entries per lane at a time: their loads are in flight together
+                    double xv[8];
+    #pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int e = e0 + 16 * q;
+                        const unsigned ee = (unsigned)(e < n * 15 ? e : j);
+                        xv[q] = restore ? LMD[oLM + LM_X0 + ee] : (accept ? XC[oX + ee] : X[oX + ee]);
+                    }
+    #pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int e = e0 + 16 * q;
+                        if (e < n * 15) {
+                            if (act && (accept || restore)) X[oX + (unsigned)e] = xv[q];
+                            if (act && fresh) LMD[oLM + LM_X0 + (unsigned)e] = xv[q];
+                            if (!is_const(e / 15, e % 15)) s2 += xv[q] * xv[q];
+                            if (hist) a.w.history[((size_t)iteration * a.B + b) * (size_t)(n * 15) + e] = xv[q];
+                        }
+                    }
+                }
+                s2 = row_sum(s2);
+                if (fresh || accept) x_norm = sqrt(s2);
+            }
+            if (act && (fail_eval || term)) {
+                if (j == 0) {
+                    st.done = 1; st.termination = fail_eval ? 6 : term;
+                    if (fail_eval) { st.x_cost = fresh ? cost : initial_cost0; st.have_candidate = 0; if (!fresh) st.iteration = iteration - 1; }
+                    if (fresh) { st.initial_cost = initial_cost; st.minimum_cost = minimum_cost; }
+                }
+                proceed = false;
+            }
+            const bool cap = proceed && lm_cap_reached(iteration, max_iters, fresh);
+            // the LM state as k_lm_step leaves it when a launch ends after the prologue; the tail below re-reads radius / decrease_factor
+            if (proceed && j == 0) {
+                st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm; st.cur = cur;
+                st.successful = successful; st.minimum_cost = minimum_cost;
+                if (fresh) st.initial_cost = initial_cost;
+                if (cap) { st.done = 1; st.termination = 4; st.reuse_diagonal = reuse; st.have_candidate = 0; }
+            }
+            if (cap) proceed = false;
+            inv_radius = 1.0 / radius;
         }
-        if (act && (fail_eval || term)) {
-            if (j == 0) {
-                st.done = 1; st.termination = fail_eval ? 6 : term;
-                if (fail_eval) { st.x_cost = fresh ? cost : initial_cost0; st.have_candidate = 0; if (!fresh) st.iteration = iteration - 1; }
-                if (fresh) { st.initial_cost = initial_cost; st.minimum_cost = minimum_cost; }
-            }
+        return __any(proceed) != 0;
+    };
+    constexpr int S_HAND = 0;   // PAIR: E's hand-over of the head's results, in the (not yet used) record area: 1 / radius [lane], then two ints per lane
+    if constexpr (PAIR) {
+        for (int e = (int)threadIdx.x; e < QZB; e += 128) S[4 * (PIFS + LPC + PWS + PGS) + QPAD + QTR + e] = 0.0;   // the block of zeros (S_ZERO below), visible to both waves behind the barrier
+        if (isA) {
+            __syncthreads();
+            inv_radius = S[S_HAND + lane];
+            const int2 v = reinterpret_cast<const int2*>(S + S_HAND + 64)[lane];
+            proceed = (v.x & 1) != 0; reuse = (v.x >> 1) & 1; cur = (v.x >> 2) & 1; iteration = v.y;
+        } else if (!head()) {
             proceed = false;
         }
-        const bool cap = proceed && lm_cap_reached(iteration, max_iters, fresh);
-        // the LM state as k_lm_step leaves it when a launch ends after the prologue; the tail below re-reads radius / decrease_factor
-        if (proceed && j == 0) {
-            st.radius = radius; st.decrease_factor = dec; st.x_cost = x_cost; st.x_norm = x_norm; st.cur = cur;
-            st.successful = successful; st.minimum_cost = minimum_cost;
-            if (fresh) st.initial_cost = initial_cost;
-            if (cap) { st.done = 1; st.termination = 4; st.reuse_diagonal = reuse; st.have_candidate = 0; }
-        }
-        if (cap) proceed = false;
-        inv_radius = 1.0 / radius;
+    } else {
+        if (!head()) return;
     }
-    if (!__any(proceed)) return;
 
     // current linearisation of this row's window
     const double* const PL0 = a.w.PL[0];
@@ -293,7 +338,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     const bool l6 = j < 6, lm = j < 15;
 
     const bool prior_row = track && !fast && a.has_prior[b] != 0;   // this row's window carries the prior block (frame n-2)
-    if (__any(proceed && fresh)) {   // Jacobi scaling 1 / (1 + sqrt(H_jj)), once per solve (same sums, same order as k_lm_step's frame_diag)
+    if (!isA && __any(proceed && fresh)) {   // Jacobi scaling 1 / (1 + sqrt(H_jj)), once per solve (same sums, same order as k_lm_step's frame_diag)
         // Round 6: the loads of FOUR frames are issued before the first of their sums is stored (as one frame per trip the store of frame i
         // fenced the loads of frame i + 1: six dependent memory round trips per frame on a wave that is alone on its SIMD — the first step
         // of 49 152 two-frame tracking windows took 0.47 ms against 0.17 ms for the others).  Unconditional loads at clamped offsets, the
@@ -334,6 +379,14 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
             }
         }
     }
+    if constexpr (PAIR) {
+        if (!isA) {   // (the barrier also orders E's stores — states, fresh Jacobi scales — before A's loads)
+            S[S_HAND + lane] = inv_radius;
+            reinterpret_cast<int2*>(S + S_HAND + 64)[lane] = make_int2((proceed ? 1 : 0) | (reuse ? 2 : 0) | (cur ? 4 : 0), iteration);
+            __syncthreads();
+        }
+        if (!__any(proceed)) return;   // (the same rows in both waves: the work-group leaves as one)
+    }
     const double sc0 = l6 ? LMD[oSC + (unsigned)jc] : 0.0;           // scale of frame 0's pose entry j (columns of the arrow block)
 
     // Everything frame f needs from HBM is fetched ONE FRAME AHEAD, behind the elimination of frame f+1: the partial records by LDS-DMA
@@ -351,10 +404,12 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     // instruction): the CU's memory pipeline hands out ~8 B per clock — its share of what HBM delivers to this read / write mix
     // (4.9 TB/s chip-wide during the sweep) — and whoever issues next waits for a slot.  Probes with the records aliased to one window
     // (cache-resident) bound the memory share of the kernel at 21 %; the rest is the instruction stream.  The DMA form stays: it needs
-    // no registers.
+    // no registers.  (k_lm_step_quad_pair does run two waves per SIMD, but with ONE staging stream per quad, issued by the assembler wave while
+    // the eliminator computes: a wave's first sweep takes 336 k ticks instead of 452 k, and the launch 3.03 ms instead of 3.13 — the waves of a
+    // SIMD still share what they shared in that experiment; profiles/quad_pair_phases.log, quad_pair_kernel_stats.md.)
     constexpr int S_IMU = 0, S_PL = 4 * PIFS, S_PW = S_PL + 4 * LPC, S_PG = S_PW + 4 * PWS, S_TR = S_PG + 4 * PGS + QPAD;   // (QPAD doubles of pad: the over-read of the last piece)
-    constexpr int S_ZERO = S_TR + QTR, S_TAB = S_ZERO + QZB;
-    static_assert(S_TAB + QTAB <= QTOT && 8 * QTOT < 65536, "LDS layout");
+    constexpr int S_ZERO = S_TR + QTR, S_TAB = S_ZERO + QZB, S_TILE = S_ZERO + QZB;   // (PAIR: the hand-off tile where the table was)
+    static_assert(S_TAB + QTAB <= QTOT && 8 * QTOT < 65536 && S_TILE + QTILE <= QTOT_P && S_ZERO % 2 == 0 && S_TILE % 2 == 0, "LDS layout");
     const unsigned rPI[4] = {(unsigned)__builtin_amdgcn_readlane(oPI, 0), (unsigned)__builtin_amdgcn_readlane(oPI, 16), (unsigned)__builtin_amdgcn_readlane(oPI, 32), (unsigned)__builtin_amdgcn_readlane(oPI, 48)};
     const unsigned rPW[4] = {(unsigned)__builtin_amdgcn_readlane(oPW, 0), (unsigned)__builtin_amdgcn_readlane(oPW, 16), (unsigned)__builtin_amdgcn_readlane(oPW, 32), (unsigned)__builtin_amdgcn_readlane(oPW, 48)};
     const unsigned oPGw = oPG + (unsigned)(PG0 - PW0);   // ground records relative to the wheel buffer (launch_lm_step_quad checks the span): one base pointer per piece
@@ -367,7 +422,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     auto prefetch_regs = [&](int f) {
         const int jq = j_ < 15 ? j_ : 0;
         scm_n = (j_ < 15 && f >= 1) ? LMD[oSC + (unsigned)((f - 1) * 15 + jq)] : 1.0;
-        dg_n = LMD[oDG + (unsigned)(f * 15 + jq)];
+        if constexpr (!PAIR) dg_n = LMD[oDG + (unsigned)(f * 15 + jq)];
         xq_n = X[oX + (unsigned)(f * 15 + jq)];
     };
     // The 26 pieces of a frame as STRAIGHT-LINE code.  Round 3 issued each piece under its own lane mask (the last piece of a record does
@@ -425,29 +480,38 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     // compile-time offset (the assembly forms four bases per frame); the other 46 — packed triangles, a block and its gradient with
     // different strides — take their byte offset from LDS, TAB[k][lane], built here once per launch: ds_read_u16 + ds_read_b64, no
     // vector ALU.  A lane that takes no part in a read is pointed at a block of zeros, so most lane masks of the assembly vanish as well.
+    // PAIR: the table is TP[k / 2], two offsets per register of wave A (the LDS it took holds the hand-off tile), and the reads' addresses
+    // cost a shift or a mask instead of the first LDS round trip.
     unsigned short* const TAB = reinterpret_cast<unsigned short*>(S + S_TAB);
+    unsigned TP[PAIR ? NRD / 2 : 1];
+    static_assert(NRD % 2 == 0, "two table entries per register");
+    if constexpr (PAIR) sfor<0, NRD / 2>([&](auto K) { TP[KI(K)] = 0u; });
     {
         const int jt = j < 15 ? j : 0, cjt = 14 * jt - (jt * (jt - 1)) / 2, j6t = j < 6 ? j : 0;
         const bool t6 = j < 6, t15 = j == 15, tm = j < 15;
         const int oL = S_PL + w * LPC, oW_ = S_PW + w * PWS, oG = S_PG + w * PGS, oI = S_IMU + w * PIFS;
-        auto put = [&](int k, bool on, int idx) { TAB[k * 64 + lane] = (unsigned short)(8 * (on ? idx : S_ZERO)); };
+        auto put = [&](auto K, bool on, int idx) {
+            constexpr int k = KI(K);
+            if constexpr (PAIR) TP[k >> 1] |= (unsigned)(8 * (on ? idx : S_ZERO)) << (16 * (k & 1));
+            else TAB[k * 64 + lane] = (unsigned short)(8 * (on ? idx : S_ZERO));
+        };
         // a laser read: the pair total behind the slot it stands for, or the zero block for a structural zero (the sign: sgA0 / sgA3 / sgR0 below)
         const int role = t15 ? 6 : j6t;
-        auto put_laser = [&](int k, bool on, int code) { put(k, on && code >= 0, oL + (code & 63)); };
-        for (int e = lane; e < QZB; e += 64) S[S_ZERO + e] = 0.0;
+        auto put_laser = [&](auto K, bool on, int code) { put(K, on && code >= 0, oL + (code & 63)); };
+        if constexpr (!PAIR) for (int e = lane; e < QZB; e += 64) S[S_ZERO + e] = 0.0;
         sfor<0, 6>([&](auto R) {
             constexpr int r = KI(R);
-            put_laser(K_A + r, t6 || t15, quad_code<0, r>(track, role));
-            put(K_B + r, t6 || t15, oW_ + (t15 ? PW_G(6 + r) : PW_JJ(r, j6t)));
-            put(K_C + r, t6 || t15, oG + (t15 ? PG_G(r) : PG_H(r, j6t)));
-            put_laser(K_HA + r, t6 || t15, quad_code<1, r>(track, role));
-            put(K_CW + r, t6 || t15, oW_ + (t15 ? PW_G(r) : PW_II(r, j6t)));
-            put_laser(K_RL + r, t6, quad_code<2, r>(track, role));
+            put_laser(KC<K_A + r>{}, t6 || t15, quad_code<0, r>(track, role));
+            put(KC<K_B + r>{}, t6 || t15, oW_ + (t15 ? PW_G(6 + r) : PW_JJ(r, j6t)));
+            put(KC<K_C + r>{}, t6 || t15, oG + (t15 ? PG_G(r) : PG_H(r, j6t)));
+            put_laser(KC<K_HA + r>{}, t6 || t15, quad_code<1, r>(track, role));
+            put(KC<K_CW + r>{}, t6 || t15, oW_ + (t15 ? PW_G(r) : PW_II(r, j6t)));
+            put_laser(KC<K_RL + r>{}, t6, quad_code<2, r>(track, role));
         });
-        put(K_GSH, t6, oW_ + PW_G(j6t));
+        put(KC<K_GSH>{}, t6, oW_ + PW_G(j6t));
         sfor<0, 15>([&](auto R) {
             constexpr int r = KI(R);
-            put(K_D + r, tm, oI + PIF_D + tri_rc<r>(jt, cjt));
+            put(KC<K_D + r>{}, tm, oI + PIF_D + tri_rc<r>(jt, cjt));
         });
     }
     // sign masks of the laser reads (quad_sign_rows_ok): sign bit set where the 128-slot record holds the NEGATED pair total — rows 0, 1 of
@@ -461,10 +525,15 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
         sgA3 = ((t6 || t15) && cA3 >= 0 && (cA3 & 64)) ? 0x80000000u : 0u;
         sgR0 = (t6 && cR0 >= 0 && (cR0 & 64)) ? 0x80000000u : 0u;
     }
+    const unsigned sgP = (sgA0 >> 31) | (sgA3 >> 30) | (sgR0 >> 29);   // (PAIR: the three in one carried register)
     const int lane_tab = lane * 2;                  // byte offset of the lane's entry inside a table row
-    auto RD = [&](auto K) -> double {               // read K of the gather table
+    auto tab_at = [&](auto K) -> unsigned {         // byte offset of read K of the gather table
         constexpr int k = KI(K);
-        const unsigned off = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(TAB) + k * 128 + lane_tab);
+        if constexpr (PAIR) return (k & 1) ? TP[k >> 1] >> 16 : TP[k >> 1] & 0xffffu;
+        else return (unsigned)*reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(TAB) + k * 128 + lane_tab);
+    };
+    auto RD = [&](auto K) -> double {               // read K of the gather table
+        const unsigned off = tab_at(K);
         return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(S) + off);
     };
     double* ST = S + S_TR + w * 90;               // ST[c * 6 + q]: carried arrow block of the frame in front, row c (lane c), hub variable q
@@ -481,7 +550,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     const bool clk_on = g_qclk_on[0] && (int)blockIdx.x == g_qclk_on[1] && iteration == g_qclk_on[3];
     const int clk_frame = g_qclk_on[2];
     if (clk_k) g_qclk[13] = clock64();
-    prefetch(n - 1);
+    if (!PAIR || isA) prefetch(n - 1);
     double sci_carry = (j_ < 15) ? LMD[oSC + (unsigned)((n - 1) * 15 + (j_ < 15 ? j_ : 0))] : 1.0;   // scale of frame n-1; later frames reuse scm
     for (int i = n - 1; i >= 0; --i) {
         QSTAMP(0);
@@ -492,118 +561,229 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
         const int jc = j < 15 ? j : 0, j6 = j < 6 ? j : 0;
         const bool l6 = j < 6, l15 = j == 15, lm = j < 15;
         const bool hasm = i >= 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this frame's records have landed in LDS (and the row's earlier stores are done)
-        QSTAMP(1);
-        const double sci = sci_carry, scm = scm_n, dg_old = dg_n, xq = xq_n;
-        sci_carry = scm;
-        // ---- the frame's blocks out of the staged records, in TWO LDS round trips: (1) the table offsets of the reads whose addresses are not
-        //      affine in the lane (packed triangles, block | gradient with different strides) together with the values of those that are
-        //      (lane base + compile-time offset: the IMU coupling ij | g_j, g_i, the wheel ij and laser Hab blocks), (2) the values behind the offsets.
-        //      Pose blocks: lanes j < 6 the 6x6 blocks, lane 15 the gradient slots, zero in the lanes between; IMU: lane j < 15 column j of
-        //      the complete diagonal tile -> D, row j of ij of block (i-1, i) -> O^T, both gradient parts -> lane 15.
-        // (lane and frame conditions as bit masks: written as selects, `x + (c ? y : 0.0)` came back from the compiler as nests of divergent
-        // branches around the additions — ~40 instructions per entry)
-        const unsigned long long m15 = l15 ? ~0ull : 0ull, mh = hasm ? ~0ull : 0ull;
-        double tS[6], oW[6], rL[6];
-        {
-            constexpr int NT = K_D - K_A;                // K_A, K_B, K_C, K_HA; K_D behind them
-            unsigned of[NT + 15], ofR[6];
-            auto tab_at = [&](int k) { return (unsigned)*reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(TAB) + k * 128 + lane_tab); };
-            sfor<0, NT>([&](auto Q) { constexpr int q = KI(Q); of[q] = tab_at(K_A + q); });
-            sfor<0, 6>([&](auto Q) { constexpr int q = KI(Q); ofR[q] = tab_at(K_RL + q); });
-            if (n > 1) sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); of[NT + q] = tab_at(K_D + q); });
-            const char* const Sb = reinterpret_cast<const char*>(S);
-            const int w8 = (lane >> 4) * 8;
-            const char* const bOV = Sb + (l15 ? 8 * (S_IMU + PIF_GJ) : 8 * (S_IMU + PIF_IJ) + jc * 120) + w8 * PIFS;
-            const char* const bGI = Sb + (l15 ? 8 * (S_IMU + PIF_GI) + w8 * PIFS : 8 * S_ZERO);
-            const char* const bOW = Sb + (l6 ? 8 * (S_PW + PW_IJ(0, 0)) + w8 * PWS + j6 * 48 : 8 * S_ZERO);
-            double gi[15];
-            if (n > 1) {
-                sfor<0, 15>([&](auto R) { constexpr int r = KI(R); o[r] = *reinterpret_cast<const double*>(bOV + 8 * r); gi[r] = *reinterpret_cast<const double*>(bGI + 8 * r); });
-            } else {
-                sfor<0, 15>([&](auto R) { constexpr int r = KI(R); d[r] = 0.0; o[r] = 0.0; gi[r] = 0.0; });
-            }
-            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); oW[r] = *reinterpret_cast<const double*>(bOW + 8 * r); });
-            asm volatile("" ::: "memory");
-            double pb[NT];
-            sfor<0, NT>([&](auto Q) { constexpr int q = KI(Q); pb[q] = *reinterpret_cast<const double*>(Sb + of[q]); });
-            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); rL[r] = *reinterpret_cast<const double*>(Sb + ofR[r]); });
-            if (n > 1) sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); d[q] = *reinterpret_cast<const double*>(Sb + of[NT + q]); });
-            asm volatile("" ::: "memory");
-            // the 128-slot record's negated entries: the pair total with its sign bit flipped (rows 2 are structural zeros: +0, no flip)
-            pb[K_A + 0] = flip_sign(pb[K_A + 0], sgA0); pb[K_A + 1] = flip_sign(pb[K_A + 1], sgA0);
-            pb[K_A + 3] = flip_sign(pb[K_A + 3], sgA3); pb[K_A + 4] = flip_sign(pb[K_A + 4], sgA3); pb[K_A + 5] = flip_sign(pb[K_A + 5], sgA3);
-            rL[0] = flip_sign(rL[0], sgR0); rL[1] = flip_sign(rL[1], sgR0);
-            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); tS[r] = pb[K_A + r] + bits_and(pb[K_B + r], mh) + pb[K_C + r]; });
-            if (!track) {   // every laser frame's Haa / ga lands on frame 0's pose (init topology): summed as the frames stream by (until round 4
-                            // frame 0 re-read the n records from HBM)
-                sfor<0, 6>([&](auto R) { constexpr int r = KI(R); hA[r] += pb[K_HA + r]; });
-                if (i == 0) sfor<0, 6>([&](auto R) { tS[KI(R)] += hA[KI(R)]; });
-            }
-            sfor<0, 15>([&](auto R) { constexpr int r = KI(R); o[r] = bits_and(o[r], mh) + gi[r]; });   // (frame 0's record has no block in front of it)
+        const double sci = sci_carry, xq = xq_n;
+        // (PAIR: what the assembler wave carries from frame to frame is cut to fit two waves per SIMD — lane and sign masks re-derived per
+        // frame like j, the diagonal tile's offsets computed instead of tabled, the old LM diagonal loaded where a row reuses it)
+        int lane_f = lane;
+        unsigned fA0 = sgA0, fA3 = sgA3, fR0 = sgR0;
+        if constexpr (PAIR) {
+            asm volatile("" : "+v"(lane_f));
+            unsigned sp = sgP;
+            launder(sp);
+            fA0 = sp << 31; fA3 = (sp << 30) & 0x80000000u; fR0 = (sp << 29) & 0x80000000u;
         }
-        sfor<0, 15>([&](auto R) { rr[KI(R)] = 0.0; });
-        sfor<0, 6>([&](auto R) {
-            constexpr int r = KI(R);
-            d[r] += bits_and(tS[r], ~m15);
-            o[r] += bits_and(tS[r], m15) + bits_and(oW[r], mh);   // (oW, rL: zero outside lanes 0 .. 5)
-            rr[r] = bits_and(rL[r], mh);
-        });
-        if (track && i == n - 2 && __any(prior_row)) {
-            // marginalization_factor (marginalization_factor.h:22-53, linearized_R omitted there): r = J (x - X), H += J^T J, g += J^T r.
-            // Lane j holds column j of linearized_J; (J^T J)[r][j] = sum_k J[k][r] J[k][j] is one DPP FMA per (r, k).
-            double Jc[15];
-            const double dxl = (lm && prior_row) ? X[oX + (unsigned)((n - 2) * 15 + jc)] - a.prior_X[(size_t)b * 15 + jc] : 0.0;
-            sfor<0, 15>([&](auto K) { constexpr int k = KI(K); Jc[k] = (lm && prior_row) ? a.prior_J[(size_t)b * 225 + k * 15 + jc] : 0.0; });
-            double gp = 0.0;
-            sfor<0, 15>([&](auto K) { constexpr int k = KI(K); const double rp = row_sum(Jc[k] * dxl); gp = __builtin_fma(Jc[k], rp, gp); });
-            dpp_fence();
+        const int wf = lane_f >> 4;
+        double scm = scm_n, dmp, cw[6];
+        const unsigned long long m15 = l15 ? ~0ull : 0ull, mh = hasm ? ~0ull : 0ull;
+        auto read_cw = [&] {   // frame i-1's wheel share out of the staged records (zero outside lanes 0..5, 15); gsh: its unscaled gradient share, lane per entry
+            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); cw[r] = RD(KC<K_CW + r>{}); });
+            gsh = RD(KC<K_GSH>{});
+        };
+        // (PAIR: both waves fold.  A keeps pdiag alone — its cd is dead; E keeps cd alone — its pdiag is dead, the compiler drops the chain)
+        auto fold_cw = [&] {   // ... in scaled space: the start of frame i-1's carried terms, and their diagonal (LM diagonal of frame i-1)
             sfor<0, 15>([&](auto R) {
                 constexpr int r = KI(R);
-                sfor<0, 15>([&](auto K) { constexpr int k = KI(K); fnma_bc<r>(d[r], Jc[k], -Jc[k]); });
-                const double gr = bc<r>(gp);
-                o[r] += l15 ? gr : 0.0;
+                double fi = 0.0;
+                if constexpr (r < 6) {
+                    const double rs = bc<r>(scm);
+                    fi = cw[r] * (rs * scm);
+                }
+                cd[r] = fi;
+                pdiag = (j == r) ? cd[r] : pdiag;
             });
-        }
-        QSTAMP(2);
-        // ---- gradient max-norm of this frame, |x - Plus(x, -g)|, lane per entry: lane r takes entry r of the unscaled tangent gradient = the
-        //      share of block (i-1, i) + the pose blocks (lane 15's o registers, turned into a lane-per-entry vector through the LDS words of
-        //      the IMU record's ij block, which the assembly above has consumed) + the share of block (i, i+1) (gsh)
-        QSTAMP(3);
-        {
-            double* GT = const_cast<double*>(SI) + PIF_IJ;
-            if (l15) sfor<0, 15>([&](auto R) { constexpr int r = KI(R); GT[r] = o[r]; });
-            const double gt = gsh + (lm ? GT[jc] : 0.0);
-            double m = fabs(gt);                                   // |q - (q - g)| when Plus does not wrap (rotation entries), |g| elsewhere
+        };
+        if constexpr (who != 2) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this frame's records have landed in LDS (and the row's earlier stores are done)
+            QSTAMP(1);
+            // ---- the frame's blocks out of the staged records, in TWO LDS round trips: (1) the table offsets of the reads whose addresses are not
+            //      affine in the lane (packed triangles, block | gradient with different strides) together with the values of those that are
+            //      (lane base + compile-time offset: the IMU coupling ij | g_j, g_i, the wheel ij and laser Hab blocks), (2) the values behind the offsets.
+            //      Pose blocks: lanes j < 6 the 6x6 blocks, lane 15 the gradient slots, zero in the lanes between; IMU: lane j < 15 column j of
+            //      the complete diagonal tile -> D, row j of ij of block (i-1, i) -> O^T, both gradient parts -> lane 15.
+            // (lane and frame conditions as bit masks: written as selects, `x + (c ? y : 0.0)` came back from the compiler as nests of divergent
+            // branches around the additions — ~40 instructions per entry)
+            double tS[6], oW[6], rL[6];
             {
-                const double av = xq - gt;
-                const double a2 = mul_nop(av, av);
-                const double s2 = bc<3>(a2) + bc<4>(a2) + bc<5>(a2);
-                if (__any(proceed && !(s2 < 9.8))) {
-                    dpp_fence();
-                    const V3<double> nq = normalize_so3(V3<double>(bc<3>(av), bc<4>(av), bc<5>(av)));
-                    if (j == 3) m = fabs(xq - nq.x);
-                    if (j == 4) m = fabs(xq - nq.y);
-                    if (j == 5) m = fabs(xq - nq.z);
+                constexpr int NT = K_D - K_A;                // K_A, K_B, K_C, K_HA; K_D behind them
+                unsigned of[NT + 15], ofR[6];
+                if constexpr (PAIR) sfor<0, NRD / 2>([&](auto K) { constexpr int k = KI(K); if constexpr (2 * k + 1 < K_D || 2 * k >= K_D + 15) launder(TP[k]); });   // (laundered like the lane id: the unpacked offsets are not hoisted out of the loop, where they would be 52 registers)
+                sfor<0, NT>([&](auto Q) { constexpr int q = KI(Q); of[q] = tab_at(KC<K_A + q>{}); });
+                sfor<0, 6>([&](auto Q) { constexpr int q = KI(Q); ofR[q] = tab_at(KC<K_RL + q>{}); });
+                if constexpr (PAIR) {
+                    const int cj = 14 * jc - (jc * (jc - 1)) / 2;
+                    const unsigned bI = (unsigned)(8 * (S_IMU + PIF_D) + wf * 8 * PIFS);
+                    sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); of[NT + q] = lm ? bI + 8u * (unsigned)tri_rc<q>(jc, cj) : (unsigned)(8 * S_ZERO); });
+                } else {
+                    if (n > 1) sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); of[NT + q] = tab_at(KC<K_D + q>{}); });
+                }
+                const char* const Sb = reinterpret_cast<const char*>(S);
+                const int w8 = wf * 8;
+                const char* const bOV = Sb + (l15 ? 8 * (S_IMU + PIF_GJ) : 8 * (S_IMU + PIF_IJ) + jc * 120) + w8 * PIFS;
+                const char* const bGI = Sb + (l15 ? 8 * (S_IMU + PIF_GI) + w8 * PIFS : 8 * S_ZERO);
+                const char* const bOW = Sb + (l6 ? 8 * (S_PW + PW_IJ(0, 0)) + w8 * PWS + j6 * 48 : 8 * S_ZERO);
+                double gi[15], pb[NT];
+                auto load_og = [&] {     // IMU coupling ij | g_j, g_i
+                    if (n > 1) {
+                        sfor<0, 15>([&](auto R) { constexpr int r = KI(R); o[r] = *reinterpret_cast<const double*>(bOV + 8 * r); gi[r] = *reinterpret_cast<const double*>(bGI + 8 * r); });
+                    } else {
+                        sfor<0, 15>([&](auto R) { constexpr int r = KI(R); d[r] = 0.0; o[r] = 0.0; gi[r] = 0.0; });
+                    }
+                };
+                auto load_ow = [&] { sfor<0, 6>([&](auto R) { constexpr int r = KI(R); oW[r] = *reinterpret_cast<const double*>(bOW + 8 * r); }); };
+                auto load_pb = [&](auto LO, auto HI) { sfor<KI(LO), KI(HI)>([&](auto Q) { constexpr int q = KI(Q); pb[q] = *reinterpret_cast<const double*>(Sb + of[q]); }); };   // the pose blocks' parts
+                auto load_rl = [&] { sfor<0, 6>([&](auto R) { constexpr int r = KI(R); rL[r] = *reinterpret_cast<const double*>(Sb + ofR[r]); }); };
+                auto load_d = [&] { if (n > 1) sfor<0, 15>([&](auto Q) { constexpr int q = KI(Q); d[q] = *reinterpret_cast<const double*>(Sb + of[NT + q]); }); };
+                auto sum_ts = [&] {
+                    // the 128-slot record's negated entries: the pair total with its sign bit flipped (rows 2 are structural zeros: +0, no flip)
+                    pb[K_A + 0] = flip_sign(pb[K_A + 0], fA0); pb[K_A + 1] = flip_sign(pb[K_A + 1], fA0);
+                    pb[K_A + 3] = flip_sign(pb[K_A + 3], fA3); pb[K_A + 4] = flip_sign(pb[K_A + 4], fA3); pb[K_A + 5] = flip_sign(pb[K_A + 5], fA3);
+                    sfor<0, 6>([&](auto R) { constexpr int r = KI(R); tS[r] = pb[K_A + r] + bits_and(pb[K_B + r], mh) + pb[K_C + r]; });
+                };
+                // every laser frame's Haa / ga lands on frame 0's pose (init topology): summed as the frames stream by (until round 4 frame 0
+                // re-read the n records from HBM)
+                auto flip_rl = [&] { rL[0] = flip_sign(rL[0], fR0); rL[1] = flip_sign(rL[1], fR0); };
+                auto sum_ha = [&] { if (!track) sfor<0, 6>([&](auto R) { constexpr int r = KI(R); hA[r] += pb[K_HA + r]; }); };
+                auto add_ha = [&] { if (!track && i == 0) sfor<0, 6>([&](auto R) { tS[KI(R)] += hA[KI(R)]; }); };
+                auto sum_o = [&] { sfor<0, 15>([&](auto R) { constexpr int r = KI(R); o[r] = bits_and(o[r], mh) + gi[r]; }); };   // (frame 0's record has no block in front of it)
+                if constexpr (!PAIR) {
+                    load_og(); load_ow();
+                    asm volatile("" ::: "memory");
+                    load_pb(KC<0>{}, KC<NT>{}); load_rl(); load_d();
+                    asm volatile("" ::: "memory");
+                    sum_ts(); flip_rl(); sum_ha(); add_ha(); sum_o();
+                } else {   // the same reads and sums in batches (no table round trip to hide behind the first): a read's address is a register here
+                    load_pb(KC<K_HA>{}, KC<NT>{});
+                    asm volatile("" ::: "memory");
+                    sum_ha(); load_pb(KC<0>{}, KC<K_HA>{});
+                    asm volatile("" ::: "memory");
+                    sum_ts(); add_ha(); load_rl(); load_ow(); load_og();
+                    asm volatile("" ::: "memory");
+                    flip_rl(); sum_o(); load_d();
+                    asm volatile("" ::: "memory");
                 }
             }
-            if (!lm || is_const(i, j)) m = 0.0;                    // (constant blocks are not parameters of the problem)
-            gm = fmax(gm, m);
-            // checksum of the assembled gradient: a non-finite residual or Jacobian entry anywhere in the evaluation makes it non-finite
-            gsum += lm ? gt : 0.0;
-        }
-        // ---- LM diagonal (LevenbergMarquardtStrategy::ComputeStep): clamp(S H S, 1e-6, 1e32) at the last accepted point
-        double dmp;
-        {
-            double mjj = d[0];
-            sfor<1, 15>([&](auto R) { constexpr int r = KI(R); mjj = (j == r) ? d[r] : mjj; });
-            double dgv = dg_old;
-            if (!reuse) {
-                dgv = fmin(fmax(__builtin_fma(mjj, sci * sci, pdiag), kMinDiag), kMaxDiag);   // (pdiag: the diagonal of block (i, i+1)'s share, already scaled)
-                if (proceed && lm) LMD[oDG + (unsigned)(i * 15 + j)] = dgv;
+            sfor<0, 15>([&](auto R) { rr[KI(R)] = 0.0; });
+            sfor<0, 6>([&](auto R) {
+                constexpr int r = KI(R);
+                d[r] += bits_and(tS[r], ~m15);
+                o[r] += bits_and(tS[r], m15) + bits_and(oW[r], mh);   // (oW, rL: zero outside lanes 0 .. 5)
+                rr[r] = bits_and(rL[r], mh);
+            });
+            if (track && i == n - 2 && __any(prior_row)) {
+                // marginalization_factor (marginalization_factor.h:22-53, linearized_R omitted there): r = J (x - X), H += J^T J, g += J^T r.
+                // Lane j holds column j of linearized_J; (J^T J)[r][j] = sum_k J[k][r] J[k][j] is one DPP FMA per (r, k).
+                double Jc[15];
+                unsigned oXp = oX, bp = (unsigned)b;
+                if constexpr (PAIR) { launder(oXp); launder(bp); }   // (this once-per-launch block's addresses are formed here, not carried through the sweep)
+                const double dxl = (lm && prior_row) ? X[oXp + (unsigned)((n - 2) * 15 + jc)] - a.prior_X[(size_t)bp * 15 + jc] : 0.0;
+                sfor<0, 15>([&](auto K) { constexpr int k = KI(K); Jc[k] = (lm && prior_row) ? a.prior_J[(size_t)bp * 225 + k * 15 + jc] : 0.0; });
+                double gp = 0.0;
+                sfor<0, 15>([&](auto K) { constexpr int k = KI(K); const double rp = row_sum(Jc[k] * dxl); gp = __builtin_fma(Jc[k], rp, gp); });
+                dpp_fence();
+                sfor<0, 15>([&](auto R) {
+                    constexpr int r = KI(R);
+                    sfor<0, 15>([&](auto K) { constexpr int k = KI(K); fnma_bc<r>(d[r], Jc[k], -Jc[k]); });
+                    const double gr = bc<r>(gp);
+                    o[r] += l15 ? gr : 0.0;
+                });
             }
-            dmp = dgv * inv_radius;
+            QSTAMP(2);
+            // ---- gradient max-norm of this frame, |x - Plus(x, -g)|, lane per entry: lane r takes entry r of the unscaled tangent gradient = the
+            //      share of block (i-1, i) + the pose blocks (lane 15's o registers, turned into a lane-per-entry vector through the LDS words of
+            //      the IMU record's ij block, which the assembly above has consumed) + the share of block (i, i+1) (gsh)
+            QSTAMP(3);
+            {
+                double* GT = (PAIR ? S + S_IMU + wf * PIFS : const_cast<double*>(SI)) + PIF_IJ;
+                if (l15) sfor<0, 15>([&](auto R) { constexpr int r = KI(R); GT[r] = o[r]; });
+                const double gt = gsh + (lm ? GT[jc] : 0.0);
+                double m = fabs(gt);                                   // |q - (q - g)| when Plus does not wrap (rotation entries), |g| elsewhere
+                {
+                    const double av = xq - gt;
+                    const double a2 = mul_nop(av, av);
+                    const double s2 = bc<3>(a2) + bc<4>(a2) + bc<5>(a2);
+                    if (__any(proceed && !(s2 < 9.8))) {
+                        dpp_fence();
+                        const V3<double> nq = normalize_so3(V3<double>(bc<3>(av), bc<4>(av), bc<5>(av)));
+                        if (j == 3) m = fabs(xq - nq.x);
+                        if (j == 4) m = fabs(xq - nq.y);
+                        if (j == 5) m = fabs(xq - nq.z);
+                    }
+                }
+                if (!lm || is_const(i, j)) m = 0.0;                    // (constant blocks are not parameters of the problem)
+                gm = fmax(gm, m);
+                // checksum of the assembled gradient: a non-finite residual or Jacobian entry anywhere in the evaluation makes it non-finite
+                gsum += lm ? gt : 0.0;
+            }
+            // ---- LM diagonal (LevenbergMarquardtStrategy::ComputeStep): clamp(S H S, 1e-6, 1e32) at the last accepted point
+            {
+                double mjj = d[0];
+                sfor<1, 15>([&](auto R) { constexpr int r = KI(R); mjj = (j == r) ? d[r] : mjj; });
+                double dgv = PAIR ? 0.0 : dg_n;
+                if constexpr (PAIR) { if (reuse) dgv = LMD[oDG + (unsigned)(i * 15 + jc)]; }
+                if (!reuse) {
+                    dgv = fmin(fmax(__builtin_fma(mjj, sci * sci, pdiag), kMinDiag), kMaxDiag);   // (pdiag: the diagonal of block (i, i+1)'s share, already scaled)
+                    if (proceed && lm) LMD[oDG + (unsigned)(i * 15 + j)] = dgv;
+                }
+                dmp = dgv * inv_radius;
+            }
         }
+        if constexpr (PAIR) {
+            // ---- the hand-off.  A: wheel share of frame i-1 (pdiag for its LM diagonal), the next frame's records ordered, tile out, barrier
+            //      `written`, barrier `consumed`.  E: barrier `written`, tile in, barrier `consumed`.  (Raw s_barrier behind an LDS-only wait:
+            //      A's DMA pieces and E's record stores stay in flight across it.)
+            double* const TL = S + S_TILE;
+            const int role = l15 ? 6 : j6;
+            double* const trr = l6 ? TL + QT_RR + wf * 36 + j6 * 6 : S + S_ZERO;
+            double* const tcw = (l6 || l15) ? TL + QT_CW + wf * 42 + role * 6 : S + S_ZERO;
+            if constexpr (who == 1) {
+                QSTAMP(4);
+                if (hasm) {
+                    dpp_fence();
+                    read_cw();
+                    __builtin_amdgcn_sched_barrier(0);
+                    fold_cw();
+                } else {
+                    gsh = 0.0;
+                }
+                if (i >= 1) prefetch(i - 1);   // (this frame's records are consumed)
+                QSTAMP(5);
+                sfor<0, 15>([&](auto R) { constexpr int r = KI(R); reinterpret_cast<double2*>(TL + QT_DO + r * 128)[lane_f] = make_double2(d[r], o[r]); });
+                reinterpret_cast<double2*>(TL + QT_DS)[lane_f] = make_double2(dmp, scm);
+                if (l6) sfor<0, 6>([&](auto R) { constexpr int r = KI(R); trr[r] = rr[r]; });
+                if ((l6 || l15) && hasm) sfor<0, 6>([&](auto R) { constexpr int r = KI(R); tcw[r] = cw[r]; });
+                if (i == 0) {   // the sweep's gradient max-norm and checksum, reduced as k_lm_step_quad reduces them behind its loop
+                    dpp_fence();
+                    const double gmax = row_max(gm), gs = row_sum(gsum);
+                    if (j == 0) { TL[QT_GM + wf] = gmax; TL[QT_GM + 4 + wf] = gs; }
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LM diagonals stored above are read by E's second sweep
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                QSTAMP(6);
+                __builtin_amdgcn_s_barrier();
+                QSTAMP(7);
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                QSTAMP(8);
+                sci_carry = scm;
+                continue;
+            } else {
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                QSTAMP(1);
+                sfor<0, 15>([&](auto R) { constexpr int r = KI(R); const double2 v = reinterpret_cast<const double2*>(TL + QT_DO + r * 128)[lane]; d[r] = v.x; o[r] = v.y; });
+                { const double2 v = reinterpret_cast<const double2*>(TL + QT_DS)[lane]; dmp = v.x; scm = v.y; }
+                sfor<0, 15>([&](auto R) { rr[KI(R)] = 0.0; });
+                sfor<0, 6>([&](auto R) { constexpr int r = KI(R); rr[r] = trr[r]; });                 // (zero block outside lanes 0 .. 5)
+                if (hasm) sfor<0, 6>([&](auto R) { constexpr int r = KI(R); cw[r] = tcw[r]; });       // (zero block outside lanes 0 .. 5, 15)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                QSTAMP(2);
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                QSTAMP(3);
+            }
+        }
+        sci_carry = scm;
         // ---- Jacobi scaling, carried Schur terms, damping
         QSTAMP(4);
         dpp_fence();
@@ -644,27 +824,16 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
         if (hasm) {
             dpp_fence();
             // (the IMU share of frame i-1 arrives with that frame's own record: only the wheel block's pose share is folded here)
-            double cw[6];
-            sfor<0, 6>([&](auto R) { constexpr int r = KI(R); cw[r] = RD(KC<K_CW + r>{}); });   // (zero outside lanes 0..5, 15)
-            gsh = RD(KC<K_GSH>{});                          // frame i-1's unscaled wheel gradient share, lane per entry
+            if constexpr (!PAIR) read_cw();                 // (PAIR: cw came with the tile)
             __builtin_amdgcn_sched_barrier(0);
-            sfor<0, 15>([&](auto R) {
-                constexpr int r = KI(R);
-                double fi = 0.0;
-                if constexpr (r < 6) {
-                    const double rs = bc<r>(scm);
-                    fi = cw[r] * (rs * scm);
-                }
-                cd[r] = fi;
-                pdiag = (j == r) ? cd[r] : pdiag;  // its diagonal (LM diagonal of frame i-1)
-            });
+            fold_cw();
         } else {
             gsh = 0.0;
         }
         sfor<0, 6>([&](auto Q) { crt[KI(Q)] = 0.0; });
         // this frame is in registers: the next one streams in behind the elimination.  (Spreading the 30 pieces over the pivots of the
         // elimination was measured: each piece still costs ~130 ticks of issue there, no gain over the burst.)
-        if (i >= 1) prefetch(i - 1);
+        if constexpr (!PAIR) if (i >= 1) prefetch(i - 1);   // (PAIR: wave A's, above)
         QSTAMP(6);
         // ---- right-looking Cholesky of D fused with the forward substitution of O^T | g and R^T: pivot k broadcasts L_kk, every lane
         //      forms w_k = a[k] / L_kk of its three columns and updates a[r] -= L[r][k] w_k with L[r][k] = w_k of lane r (DPP operand).
@@ -733,13 +902,14 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
         }
         QSTAMP(10);
     }
+    if constexpr (isA) return;   // (nothing of wave A's is live in LDS behind the last barrier)
     if (clk_k) g_qclk[14] = clock64();
     dpp_fence();
-    const double gmax = row_max(gm);
+    const double gmax = PAIR ? S[S_TILE + QT_GM + w] : row_max(gm);
     ytg = bc<15>(ytg);
     // ---- was the evaluation this linearisation came from valid?  (see k_lm_step: Ceres' IsEvaluationValid on the fused partial sums)
     {
-        const bool bad = !isfinite(row_sum(gsum));
+        const bool bad = !isfinite(PAIR ? S[S_TILE + QT_GM + 4 + w] : row_sum(gsum));
         if (proceed && bad) {   // IterationZero / HandleSuccessfulStep: evaluation failed -> FAILURE, the states the solve started from are handed back
             if (!fresh) for (int e = j; e < n * 15; e += 16) X[oX + (unsigned)e] = LMD[oLM + LM_X0 + (unsigned)e];
             if (j == 0) {
@@ -773,7 +943,7 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     // makes the wait stricter).
     constexpr int RECP = (4 * REC_GS + 127) / 128, XP = (4 * 30 + 63) / 64, LP_ = (8 * 30 + 63) / 64;   // 16-byte pieces of the records; 4-byte pieces of X; of scale + diagonal
     constexpr int NLD = RECP + XP + LP_, BUFD = RECP * 128 + (XP + LP_) * 32;
-    static_assert(BSD2 * BUFD <= QTOT && 2 * NLD <= 63 && (BSD2 == 2 || BSD2 == 3), "second-sweep staging");
+    static_assert(BSD2 * BUFD <= (PAIR ? QTOT_P : QTOT) && 2 * NLD <= 63 && (BSD2 == 2 || BSD2 == 3), "second-sweep staging");
     const unsigned rWS[4] = {(unsigned)__builtin_amdgcn_readlane(oWS, 0), (unsigned)__builtin_amdgcn_readlane(oWS, 16), (unsigned)__builtin_amdgcn_readlane(oWS, 32), (unsigned)__builtin_amdgcn_readlane(oWS, 48)};
     const unsigned rX[4] = {(unsigned)__builtin_amdgcn_readlane(oX, 0), (unsigned)__builtin_amdgcn_readlane(oX, 16), (unsigned)__builtin_amdgcn_readlane(oX, 32), (unsigned)__builtin_amdgcn_readlane(oX, 48)};
     const unsigned rLM[4] = {(unsigned)__builtin_amdgcn_readlane(oLM, 0), (unsigned)__builtin_amdgcn_readlane(oLM, 16), (unsigned)__builtin_amdgcn_readlane(oLM, 32), (unsigned)__builtin_amdgcn_readlane(oLM, 48)};
@@ -903,6 +1073,16 @@ __global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
     }
 }
 
+__global__ __launch_bounds__(64, 1) void k_lm_step_quad(StepArgs a) {
+    __shared__ double S[QTOT];
+    lm_step_quad_body<0>(a, S);
+}
+__global__ __launch_bounds__(128, 2) void k_lm_step_quad_pair(StepArgs a) {
+    __shared__ double S[QTOT_P];
+    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1) lm_step_quad_body<1>(a, S);
+    else lm_step_quad_body<2>(a, S);
+}
+
 // every row-dependent address of the kernel is a base + unsigned 32-bit element offset
 bool lm_step_quad_fits(const StepArgs& a) {
     const unsigned long long lim = 0xFFFFFFFFull - 4096;
@@ -923,8 +1103,17 @@ extern "C" void liw_debug_quad_clk(int on, int block, int frame, int iteration, 
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_qclk_on), v, sizeof(v));
     if (out) (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_qclk), sizeof(long long) * 64);
 }
+bool lm_step_quad_pair_on() {   // LIW_QUAD_PAIR=0 (read per call): the one-wave kernel — A/B partner and test reference
+    const char* e = std::getenv("LIW_QUAD_PAIR");
+    return !(e && e[0] == '0');
+}
+static int g_last_step_kernel = 0;   // what the last launch_lm_step of the process launched (launch-path report; written by the launching thread)
+void note_step_kernel(int k) { __atomic_store_n(&g_last_step_kernel, k, __ATOMIC_RELAXED); }
+int last_step_kernel() { return __atomic_load_n(&g_last_step_kernel, __ATOMIC_RELAXED); }
 void launch_lm_step_quad(const StepArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_lm_step_quad, dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+    note_step_kernel(lm_step_quad_pair_on() ? 2 : 1);
+    if (lm_step_quad_pair_on()) hipLaunchKernelGGL(k_lm_step_quad_pair, dim3((a.B + 3) / 4), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL(k_lm_step_quad, dim3((a.B + 3) / 4), dim3(64), 0, s, a);
 }
 
 }  // namespace liw

@@ -413,6 +413,13 @@ int liw_batch_launch_paths(liw_ctx* c, const liw_batch* b, const void* ws, int* 
     *flags = (pi_frame_format(b->B) ? 1 : 0) | (lpk_matches(c, b, ws) ? 2 : 0);
     return LIW_OK;
 }
+int liw_batch_step_kernel(liw_ctx* c, const liw_batch* b, int* kernel) {
+    if (!c) return LIW_EINVAL;
+    if (int r = check_batch(c, b)) return r;
+    if (!kernel) return fail(c, LIW_EINVAL, "liw_batch_step_kernel: null kernel");
+    *kernel = last_step_kernel();
+    return LIW_OK;
+}
 int liw_batch_packed_rows(liw_ctx* c, const liw_batch* b, const void* ws, long long* rows, long long* blocks) {
     if (!c) return LIW_EINVAL;
     if (int r = check_batch(c, b)) return r;

@@ -366,6 +366,9 @@ void launch_lm_begin(int B, int n, LmState* lm, int max_iters, hipStream_t s);
 void launch_lm_step(const StepArgs& a, hipStream_t s);
 void launch_lm_step_quad(const StepArgs& a, hipStream_t s);   // k_lm_quad.hip: four windows per wave (INIT topology, large batches)
 bool lm_step_quad_fits(const StepArgs& a);
+void note_step_kernel(int k);                                  // launch_lm_step's record of what it launched: 0 one of k_lm_step's family, 1 k_lm_step_quad, 2 k_lm_step_quad_pair
+int last_step_kernel();
+bool lm_step_quad_pair_on();                                   // k_lm_step_quad_pair (two waves per quad) unless LIW_QUAD_PAIR=0
 size_t compact_list_bytes_host(int B);                // bytes of WsView::active (list + ticket + publication words)
 bool lin_builds_active_list(int B, int eval_small);   // k_linearize.hip: does launch_linearize (with LM state) compact the active windows?
 void launch_lm_finish(const StepArgs& a, hipStream_t s);

@@ -220,6 +220,11 @@ int liw_batch_lm_begin(liw_ctx* ctx, const liw_batch* b, int mode, int max_iters
  * k_lm_step_quad), bit 1 = the lane-per-group laser kernel is armed for this (batch, workspace) (k_lin_laser_slab; k_lin_laser_slab1 for TRACK and
  * for the marginalisation that follows on the same arrays). */
 int liw_batch_launch_paths(liw_ctx* ctx, const liw_batch* b, const void* ws, int* flags);
+/* The LM step kernel the LAST step launch of this process took, recorded where it is launched (no reference counterpart; ask right
+ * behind the solve in question): *kernel = 0: the small-batch kernels (k_lm_step and its variants; also before any launch),
+ * 1: k_lm_step_quad, 2: k_lm_step_quad_pair (the default wherever bit 0 of the launch-path flags is set and the batch fits the quad
+ * kernels' 32-bit offsets; LIW_QUAD_PAIR=0, read per call, selects k_lm_step_quad).  Beside the flags, whose values tests pin, not a third bit of them. */
+int liw_batch_step_kernel(liw_ctx* ctx, const liw_batch* b, int* kernel);
 /* Size of the re-packed laser rows of that solve (measurement aid, no reference counterpart): *rows = 64-block rows packed (0: the
  * lane-per-group kernel is not armed for this batch), *blocks = laser blocks of the batch; 64 * rows / blocks = the padding ratio — 1.0
  * means every lane of every row carries a block.  Since round 6 the windows are taken in a per-frame order by group length, so ragged
