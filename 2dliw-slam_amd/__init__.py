@@ -356,5 +356,5 @@ from . import fleet, gridmap, laser, laser_batch, loop, loop_batch, map_batch, o
 from .fleet import FleetTracker, FleetTrajectory  # noqa: E402,F401
 from .loop_batch import FleetLoopDetector  # noqa: E402,F401
 from .posegraph_batch import FleetBackEnd  # noqa: E402,F401
-from .map_batch import FleetMapper  # noqa: E402,F401
+from .map_batch import FleetGroupMap, FleetMapper  # noqa: E402,F401
 from .preint_batch import FleetPreint  # noqa: E402,F401

@@ -32,51 +32,11 @@
 
 #include "../../include/liw_map_batch.h"
 #include "k_map_batch.hpp"
-#include "k_map_dev.hpp"
-#include "liw_crmath.hpp"
-#include "liw_dual.hpp"
+#include "k_map_batch_dev.hpp"   // the bodies shared with k_map_group.hip
 
 namespace liw_fmap_dev {
 
-using liw_map_dev::Grid;
-using liw_map_dev::kBlock;
-using liw_map_dev::kLdsSteps;
-using liw_map_dev::kRayLanes;
-using liw_map_dev::Ray;
-
-// A double whose sin / cos / atan2 are the correctly rounded ones of liw_crmath.hpp, as in k_loop_batch.hip
-struct CR {
-    double v;
-    __host__ __device__ CR() : v(0.0) {}
-    __host__ __device__ CR(double c) : v(c) {}  // NOLINT(implicit)
-};
-__host__ __device__ inline CR operator+(const CR& a, const CR& b) { return CR(a.v + b.v); }
-__host__ __device__ inline CR operator-(const CR& a, const CR& b) { return CR(a.v - b.v); }
-__host__ __device__ inline CR operator-(const CR& a) { return CR(-a.v); }
-__host__ __device__ inline CR operator*(const CR& a, const CR& b) { return CR(a.v * b.v); }
-__host__ __device__ inline CR operator/(const CR& a, const CR& b) { return CR(a.v / b.v); }
-__host__ __device__ inline bool operator>(const CR& a, const CR& b) { return a.v > b.v; }
-__host__ __device__ inline bool operator<(const CR& a, const CR& b) { return a.v < b.v; }
-__host__ __device__ inline CR dsqrt(const CR& a) { return CR(sqrt(a.v)); }
-__host__ __device__ inline CR dsin(const CR& a) { return CR(liw_cr::cr_sin(a.v)); }
-__host__ __device__ inline CR dcos(const CR& a) { return CR(liw_cr::cr_cos(a.v)); }
-__host__ __device__ inline CR datan2(const CR& y, const CR& x) { return CR(liw_cr::cr_atan2(y.v, x.v)); }
-__host__ __device__ inline CR dfloor(const CR& a) { return CR(floor(a.v)); }
-
-struct Til12 { double v[12]; };      // T_imu_to_laser by value
-
-__device__ __forceinline__ char* robot_region(char* store, const Lay& L, int b) { return store + (size_t)b * L.robot_bytes; }
 __device__ __forceinline__ bool robot_on(const unsigned char* a, int b) { return !a || a[b] != 0; }
-__device__ __forceinline__ liw_map_info* held_info(char* R) { return (liw_map_info*)(R + HB_INFO); }
-
-__device__ __forceinline__ liw_map_info empty_info(double res) {
-    liw_map_info mi;
-    mi.width = mi.height = 0;
-    mi.resolution = res;
-    mi.origin_x = mi.origin_y = 0.0;
-    mi.rays = mi.samples = mi.unknown = mi.free_cells = mi.hit_once = mi.hit_more = 0;
-    return mi;
-}
 
 __global__ __launch_bounds__(256) void k_fmap_reset(char* store, Lay L, const unsigned char* __restrict__ mask) {
     const int nrb = (L.B + 255) / 256;
@@ -158,12 +118,7 @@ __global__ __launch_bounds__(256) void k_fmap_tf(char* store, Lay L, const doubl
     const int nsub = hdr[H_NSUB];
     if (k == 0) hdr[H_NTF] = nsub;
     if (k >= nsub) return;
-    const double* ps = poses + (size_t)b * robot_stride + (size_t)k * 6;
-    const liw::Iso<CR> A = liw::make_tf(liw::V3<CR>(ps[0], ps[1], ps[2]), liw::V3<CR>(ps[3], ps[4], ps[5]));
-    const liw::Iso<CR> T = liw::mul(A, liw::cast_iso<CR>(til.v, til.v + 9));
-    double* tf = (double*)(R + L.r_tf) + (size_t)k * 12;
-    for (int e = 0; e < 9; ++e) tf[e] = T.R.m[e].v;
-    tf[9] = T.t.x.v; tf[10] = T.t.y.v; tf[11] = T.t.z.v;
+    compose_twl(poses + (size_t)b * robot_stride + (size_t)k * 6, til, (double*)(R + L.r_tf) + (size_t)k * 12);
 }
 
 __global__ __launch_bounds__(kBlock) void k_fmap_bounds(char* store, Lay L, const double* __restrict__ tfbase, long long tfstride,
@@ -172,19 +127,8 @@ __global__ __launch_bounds__(kBlock) void k_fmap_bounds(char* store, Lay L, cons
     const int b = blockIdx.x / L.nchunk, c = blockIdx.x % L.nchunk;
     if (!robot_on(sel, b)) return;
     char* R = robot_region(store, L, b);
-    const int npts = ((const int*)R)[H_NPTS];
-    const double* pts = (const double*)(R + L.r_pts);
-    const int* sub = (const int*)(R + L.r_sub);
-    const double* tf = tfbase + (size_t)b * tfstride;
-    double v[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0.0, 0.0};
-    for (int i = c * kBlock + threadIdx.x; i < npts; i += L.nchunk * kBlock) {
-        const Ray r = liw_map_dev::make_ray(pts, sub, tf, i);
-        if (r.valid) {
-            v[0] = fmin(v[0], r.P[0]); v[1] = fmax(v[1], r.P[0]); v[2] = fmin(v[2], r.P[1]); v[3] = fmax(v[3], r.P[1]);
-            v[4] = fmax(v[4], r.len); v[5] += 1.0;
-        }
-    }
-    liw_map_dev::block_fold6(v, sm);
+    double v[6];
+    bounds_body(R, L, tfbase + (size_t)b * tfstride, c, v, sm);
     if (threadIdx.x < 6) ((double*)(R + L.r_partial))[(size_t)c * 6 + threadIdx.x] = v[0];
 }
 
@@ -195,10 +139,7 @@ __global__ __launch_bounds__(64) void k_fmap_fold(char* store, Lay L, const unsi
     char* R = robot_region(store, L, b);
     const double* partial = (const double*)(R + L.r_partial);
     double v[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0.0, 0.0};
-    for (int c = lane; c < L.nchunk; c += 64) {
-        const double* p = partial + (size_t)c * 6;
-        v[0] = fmin(v[0], p[0]); v[1] = fmax(v[1], p[1]); v[2] = fmin(v[2], p[2]); v[3] = fmax(v[3], p[3]); v[4] = fmax(v[4], p[4]); v[5] += p[5];
-    }
+    for (int c = lane; c < L.nchunk; c += 64) fold_partial(v, partial + (size_t)c * 6);
     for (int o = 32; o > 0; o >>= 1) {
         v[0] = fmin(v[0], __shfl_xor(v[0], o));
         v[1] = fmax(v[1], __shfl_xor(v[1], o));
@@ -208,29 +149,8 @@ __global__ __launch_bounds__(64) void k_fmap_fold(char* store, Lay L, const unsi
         v[5] = v[5] + __shfl_xor(v[5], o);
     }
     if (lane != 0) return;
-    // from here on the arithmetic of liw_map_render_tf's host code (visualization.cpp:412-413)
-    const double res = L.res, step = res / 2;
-    liw_map_info mi = empty_info(res);
-    mi.rays = (long long)v[5];
-    int st = LIW_FMAP_OK;
-    if (mi.rays == 0) st = LIW_FMAP_EMPTY;   // no valid point: a 0 x 0 map
-    else {
-        const double wd = (v[1] - v[0]) / res + 1, hd = (v[3] - v[2]) / res + 1;
-        mi.origin_x = v[0];
-        mi.origin_y = v[2];
-        if (!(wd < 2147483647.0) || !(hd < 2147483647.0)) {
-            mi.width = mi.height = 2147483647;
-            st = LIW_FMAP_OVER_CELLS;
-        } else {
-            mi.width = (int)wd;
-            mi.height = (int)hd;
-            const long long ncell = (long long)mi.width * mi.height;
-            const double nsteps = v[4] / step;
-            if (ncell > (long long)L.C) st = LIW_FMAP_OVER_CELLS;
-            else if (!(nsteps < (double)(L.S - 2))) st = LIW_FMAP_RAY_TOO_LONG;   // k_fmap_rays looks one entry past int(len / step)
-            else mi.unknown = ncell;   // k_fmap_finish takes the known cells off
-        }
-    }
+    liw_map_info mi;
+    const int st = derive_box(v, L.res, L.C, L.S, &mi);
     ((int*)R)[H_STATUS] = st;
     status[b] = st;
     info[b] = mi;
@@ -244,13 +164,7 @@ __global__ __launch_bounds__(kBlock) void k_fmap_clear(char* store, Lay L, const
     const int b = blockIdx.x / L.cchunk, c = blockIdx.x % L.cchunk;
     char* R = robot_region(store, L, b);
     if (!rendered(R, sel, b)) return;
-    const liw_map_info* hi = held_info(R);
-    const long long n16 = ((long long)hi->width * hi->height + 15) / 16;
-    unsigned long long* bits8 = (unsigned long long*)(R + L.r_bits);   // the store is 8-byte aligned: two 8-byte words per item
-    for (long long i = (long long)c * kBlock + threadIdx.x; i < n16; i += (long long)L.cchunk * kBlock) {
-        bits8[2 * i] = 0ull;
-        bits8[2 * i + 1] = 0ull;
-    }
+    clear_body(held_info(R), R + L.r_bits, c, L.cchunk);
 }
 
 __global__ __launch_bounds__(kBlock) void k_fmap_rays(char* store, Lay L, const double* __restrict__ tfbase, long long tfstride,
@@ -259,76 +173,22 @@ __global__ __launch_bounds__(kBlock) void k_fmap_rays(char* store, Lay L, const 
     const int b = blockIdx.x / L.rchunk, c = blockIdx.x % L.rchunk;
     char* R = robot_region(store, L, b);
     if (!rendered(R, sel, b)) return;
-    const double* T = (const double*)(store + L.s_table);
-    const int nl = L.S < kLdsSteps ? L.S : kLdsSteps;
-    for (int e = threadIdx.x; e < nl; e += kBlock) sT[e] = T[e];
-    __syncthreads();
-    liw_map_info* hi = held_info(R);
-    const Grid g{hi->width, hi->height, hi->origin_x, hi->origin_y, L.res, L.res / 2};
-    const int npts = ((const int*)R)[H_NPTS];
-    const double* pts = (const double*)(R + L.r_pts);
-    const int* sub = (const int*)(R + L.r_sub);
-    const double* tf = tfbase + (size_t)b * tfstride;
-    uint8_t* bits = (uint8_t*)(R + L.r_bits);
-    const int group = threadIdx.x / kRayLanes, s = threadIdx.x % kRayLanes;
-    constexpr int kGroups = kBlock / kRayLanes;
-    unsigned long long samples = 0, visits = 0, atomics = 0, hit_atomics = 0;   // the last three depend on the arrival order: not kept
-    for (int ray = c * kGroups + group; ray < npts; ray += L.rchunk * kGroups) {
-        const Ray r = liw_map_dev::make_ray(pts, sub, tf, ray);
-        if (!r.valid) continue;
-        liw_map_dev::walk_ray(r, g, sT, T, nl, s, bits, samples, visits, atomics, hit_atomics);
-    }
-    samples = liw_map_dev::wave_sum(samples);
-    if ((threadIdx.x & 63) == 0 && samples) {
-        atomicAdd((unsigned long long*)&hi->samples, samples);
-        atomicAdd((unsigned long long*)&info[b].samples, samples);
-    }
-}
-
-// the known cells of a wave go from `unknown` to their counts
-__device__ __forceinline__ void add_counts(liw_map_info* mi, unsigned long long c0, unsigned long long c50, unsigned long long c100) {
-    if (c0) atomicAdd((unsigned long long*)&mi->free_cells, c0);
-    if (c50) atomicAdd((unsigned long long*)&mi->hit_once, c50);
-    if (c100) atomicAdd((unsigned long long*)&mi->hit_more, c100);
-    atomicAdd((unsigned long long*)&mi->unknown, 0ull - (c0 + c50 + c100));
+#define RAYS_INFO held_info(R)
+#define RAYS_BITS R + L.r_bits
+#define RAYS_TF tfbase + (size_t)b * tfstride
+#define RAYS_ROW info[b]
+#include "k_map_rays_body.inc"
+#undef RAYS_INFO
+#undef RAYS_BITS
+#undef RAYS_TF
+#undef RAYS_ROW
 }
 
 __global__ __launch_bounds__(kBlock) void k_fmap_finish(char* store, Lay L, const unsigned char* __restrict__ sel, liw_map_info* __restrict__ info) {
     const int b = blockIdx.x / L.cchunk, c = blockIdx.x % L.cchunk;
     char* R = robot_region(store, L, b);
     if (!rendered(R, sel, b)) return;
-    liw_map_info* hi = held_info(R);
-    const long long n16 = ((long long)hi->width * hi->height + 15) / 16;
-    const uint2* bits8 = (const uint2*)(R + L.r_bits);
-    uint2* grid8 = (uint2*)(R + L.r_grid);
-    unsigned long long c0 = 0, c50 = 0, c100 = 0;
-    for (long long i = (long long)c * kBlock + threadIdx.x; i < n16; i += (long long)L.cchunk * kBlock) {
-        const uint2 lo = bits8[2 * i], hi2 = bits8[2 * i + 1];
-        const unsigned in[4] = {lo.x, lo.y, hi2.x, hi2.y};
-        unsigned out[4];
-        for (int w = 0; w < 4; ++w) {
-            unsigned o = 0;
-            for (int e = 0; e < 4; ++e) {
-                const unsigned v = (in[w] >> (8 * e)) & 0xFFu;
-                unsigned val;
-                if (v & liw_map_dev::kHit2) { val = 100u; ++c100; }
-                else if (v & liw_map_dev::kHit1) { val = 50u; ++c50; }
-                else if (v & liw_map_dev::kSampled) { val = 0u; ++c0; }
-                else val = 0xFFu;   // -1
-                o |= val << (8 * e);
-            }
-            out[w] = o;
-        }
-        grid8[2 * i] = make_uint2(out[0], out[1]);
-        grid8[2 * i + 1] = make_uint2(out[2], out[3]);
-    }
-    c0 = liw_map_dev::wave_sum(c0);
-    c50 = liw_map_dev::wave_sum(c50);
-    c100 = liw_map_dev::wave_sum(c100);
-    if ((threadIdx.x & 63) == 0 && (c0 | c50 | c100)) {
-        add_counts(hi, c0, c50, c100);
-        add_counts(info + b, c0, c50, c100);
-    }
+    finish_body(held_info(R), R + L.r_bits, R + L.r_grid, info + b, c, L.cchunk);
 }
 
 static int launched() { return hipGetLastError() == hipSuccess ? 0 : 1; }

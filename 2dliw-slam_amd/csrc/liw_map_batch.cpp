@@ -12,6 +12,7 @@
 #include "../../include/liw_lie.h"
 #include "../../include/liw_map_batch.h"
 #include "k_map_batch.hpp"
+#include "k_map_group.hpp"   // fmap_view: what a group map (liw_map_group.cpp) borrows from a ctx
 #include "liw_host_common.hpp"
 
 namespace {
@@ -54,6 +55,15 @@ struct liw_fmap_ctx : liw_fleet_ctx_base {
     Lay L{};
     double Til[12];
 };
+
+liw_fmap_dev::FmapView liw_fmap_dev::fmap_view(const liw_fmap_ctx* c) {
+    FmapView v;
+    v.L = c->L;
+    std::memcpy(v.Til, c->Til, sizeof(v.Til));
+    v.device = c->device;
+    v.have_device = c->have_device;
+    return v;
+}
 
 namespace {
 

@@ -385,7 +385,8 @@ class BatchFrontEnd:
             out["match_pose"] = torch.zeros(self.B * n * 12, dtype=torch.float64, device=self.dev)
         if "has_match" not in out:
             out["has_match"] = torch.zeros(self.B * n, dtype=torch.uint8, device=self.dev)
-        if bufs is None:   # every entry the result exposes is written by the call
+        fresh = bufs is None
+        if fresh:   # every entry the result exposes is written by the call, but for the one padding entry of an empty pack
             bufs = dict(laser_off=torch.empty(self.B + 1, dtype=torch.int32, device=self.dev),
                         laser_frame=torch.empty(max(L_cap, 1), dtype=torch.int32, device=self.dev),
                         laser_pts=torch.empty(12 * max(L_cap, 1), dtype=torch.float64, device=self.dev))
@@ -393,6 +394,9 @@ class BatchFrontEnd:
         assert off.numel() >= self.B + 1 and lf.numel() >= max(L_cap, 1) and lp.numel() >= 12 * max(L_cap, 1)
         Ltot = self._chk(self.L.liw_lfe_pack_track(self.h, int(n), int(frame), cap, self._p(m["count"]), self._p(m["recs"]), self._p(m["match_pose"]),
                                                    L_cap, self._p(off), self._p(lf), self._p(lp), self._p(out["match_pose"]), self._p(out["has_match"]), self._s()))
+        if fresh and Ltot == 0:   # no record: the entry kept so that no array is empty was never written
+            lf[:1].zero_()
+            lp[:12].zero_()
         res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
         return res, Ltot
 
@@ -444,7 +448,8 @@ class BatchFrontEnd:
             if k not in out:
                 out[k] = torch.zeros(max(size, 1), dtype=dt, device=self.dev)
             assert out[k].dtype == dt and out[k].is_contiguous() and out[k].numel() >= size, k
-        if bufs is None:
+        fresh = bufs is None
+        if fresh:
             bufs = dict(laser_off=torch.empty(self.B + 1, dtype=torch.int32, device=self.dev),
                         laser_frame=torch.empty(max(L_cap, 1), dtype=torch.int32, device=self.dev),
                         laser_pts=torch.empty(12 * max(L_cap, 1), dtype=torch.float64, device=self.dev))
@@ -453,6 +458,9 @@ class BatchFrontEnd:
         Ltot = self._chk(self.L.liw_lfe_pack_init(self.h, n, cap, self._p(m["count"]), self._p(m["recs"]), self._p(m["match_pose"]), self._p(pf), L_cap,
                                                   self._p(off), self._p(lf), self._p(lp), self._p(out["match_pose"]), self._p(out["has_match"]),
                                                   self._p(out["init_ok"]), self._s()))
+        if fresh and Ltot == 0:   # no record: the entry kept so that no array is empty was never written
+            lf[:1].zero_()
+            lp[:12].zero_()
         res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
         return res, Ltot, out["init_ok"]
 
@@ -639,7 +647,8 @@ class BatchFrontEnd:
             if k not in out:
                 out[k] = torch.zeros(max(size, 1), dtype=dt, device=self.dev)
             assert out[k].dtype == dt and out[k].is_contiguous() and out[k].numel() >= size, k
-        if bufs is None:
+        fresh = bufs is None
+        if fresh:
             bufs = dict(laser_off=torch.empty(R + 1, dtype=torch.int32, device=self.dev),
                         laser_frame=torch.empty(max(L_cap, 1), dtype=torch.int32, device=self.dev),
                         laser_pts=torch.empty(12 * max(L_cap, 1), dtype=torch.float64, device=self.dev))
@@ -648,6 +657,9 @@ class BatchFrontEnd:
         Ltot = self._chk(self.L.liw_lfe_pack_init_sel(self.h, R, self._p(sel), n, cap, self._p(m["count"]), self._p(m["recs"]), self._p(m["match_pose"]),
                                                       self._p(pf), int(pf.stride(0)), L_cap, self._p(off), self._p(lf), self._p(lp),
                                                       self._p(out["match_pose"]), self._p(out["has_match"]), self._p(out["init_ok"]), self._s()))
+        if fresh and Ltot == 0:   # no record: the entry kept so that no array is empty was never written
+            lf[:1].zero_()
+            lp[:12].zero_()
         res = dict(laser_off=off, laser_frame=lf[:max(Ltot, 1)], laser_pts=lp[:12 * max(Ltot, 1)], match_pose=out["match_pose"], has_match=out["has_match"])
         return res, Ltot, out["init_ok"]
 

@@ -2,7 +2,8 @@
 key frame of B robots in one store and renders the reference's 5 cm occupancy grid of the selected robots from the back-end's
 corrected poses, on torch's current stream, without a host loop over robots and without a read-back.  It is the last stage of
 `FleetTrajectory.step -> FleetLoopDetector.push -> FleetBackEnd.push -> FleetMapper.push`.  `gridmap.GridMap` (one robot, host
-glue) is its parity reference.  There is no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device."""
+glue) is its parity reference.  `FleetGroupMap` (C ABI include/liw_map_group.h) renders one shared grid per group of a FleetMapper's
+robots from the same store.  There is no CPU fallback: compute calls raise LiwError(LIW_ENODEV) without a gfx950 device."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,11 @@ from .gridmap import MapInfoC, MapParamsC, _info_dict, _palette, office_map_para
 FMAP_EXPORTS = ["liw_fmap_store_bytes", "liw_fmap_layout", "liw_fmap_create", "liw_fmap_destroy", "liw_fmap_last_error", "liw_fmap_reset",
                 "liw_fmap_add_keyframes", "liw_fmap_render_tf", "liw_fmap_render", "liw_fmap_num_submaps", "liw_fmap_full", "liw_fmap_get_submap",
                 "liw_fmap_get_tf", "liw_fmap_last_info", "liw_fmap_get", "liw_fmap_device_data", "liw_fmap_write_pgm"]
+
+# every symbol include/liw_map_group.h declares (checked by tests/test_map_group_abi.py)
+GMAP_EXPORTS = ["liw_gmap_store_bytes", "liw_gmap_layout", "liw_gmap_create", "liw_gmap_destroy", "liw_gmap_last_error", "liw_gmap_reset",
+                "liw_gmap_render_tf", "liw_gmap_render", "liw_gmap_last_info", "liw_gmap_members", "liw_gmap_get", "liw_gmap_device_data",
+                "liw_gmap_write_pgm"]
 
 OK, EMPTY, OVER_CELLS, RAY_TOO_LONG = 0, 1, 2, 3   # LIW_FMAP_*
 INFO_BYTES = C.sizeof(MapInfoC)                    # sizeof(liw_map_info)
@@ -27,6 +33,14 @@ class FmapDimsC(C.Structure):
 class FmapLayoutC(C.Structure):
     _fields_ = [(k, C.c_size_t) for k in ("bytes", "robot_bytes", "shared_off", "shared_bytes", "cell_bytes", "offsets_off", "points_off", "index_off",
                                           "tf_off", "partial_off", "bits_off", "grid_off")] + [("partials", C.c_int)]
+
+
+class GmapDimsC(C.Structure):
+    _fields_ = [("G", C.c_int), ("max_cells", C.c_int)]
+
+
+class GmapLayoutC(C.Structure):
+    _fields_ = [(k, C.c_size_t) for k in ("bytes", "group_bytes", "cell_bytes", "bits_off", "grid_off")] + [("cell_chunks", C.c_int)]
 
 
 def dims_struct(d):
@@ -62,6 +76,24 @@ def _lib():
         L.liw_fmap_device_data.restype = vp
         L.liw_fmap_device_data.argtypes = [vp, vp, ci]
         L.liw_fmap_write_pgm.argtypes = [vp, vp, ci, C.c_char_p, C.POINTER(C.c_ubyte)]
+        gd = C.POINTER(GmapDimsC)
+        L.liw_gmap_store_bytes.argtypes = [gd, C.POINTER(C.c_size_t)]
+        L.liw_gmap_layout.argtypes = [gd, C.POINTER(GmapLayoutC)]
+        L.liw_gmap_create.restype = vp
+        L.liw_gmap_create.argtypes = [vp, gd]
+        L.liw_gmap_destroy.argtypes = [vp]
+        L.liw_gmap_last_error.restype = C.c_char_p
+        L.liw_gmap_last_error.argtypes = [vp]
+        L.liw_gmap_reset.argtypes = [vp, vp, vp, vp]
+        L.liw_gmap_render_tf.argtypes = [vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp]
+        L.liw_gmap_render.argtypes = [vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp]
+        L.liw_gmap_last_info.argtypes = [vp, vp, ci, C.POINTER(MapInfoC), C.POINTER(ci)]
+        L.liw_gmap_members.argtypes = [vp, vp, ci, C.POINTER(ci), C.POINTER(ci)]
+        L.liw_gmap_get.restype = ll
+        L.liw_gmap_get.argtypes = [vp, vp, ci, C.POINTER(C.c_byte), ll]
+        L.liw_gmap_device_data.restype = vp
+        L.liw_gmap_device_data.argtypes = [vp, vp, ci]
+        L.liw_gmap_write_pgm.argtypes = [vp, vp, ci, C.c_char_p, C.POINTER(C.c_ubyte)]
         L._fmap_ready = True
     return L
 
@@ -83,6 +115,26 @@ def store_bytes(params, dims):
     r = _lib().liw_fmap_store_bytes(C.byref(params_struct(params)), C.byref(dims_struct(dims)), C.byref(n))
     if r:
         raise LiwError(r, "liw_fmap_store_bytes: bad params or dims")
+    return n.value
+
+
+def group_layout(G, max_cells):
+    """dict of liw_gmap_layout_info (host-only); raises LiwError(LIW_EINVAL) on bad dims"""
+    from . import LiwError
+    out = GmapLayoutC()
+    r = _lib().liw_gmap_layout(C.byref(GmapDimsC(int(G), int(max_cells))), C.byref(out))
+    if r:
+        raise LiwError(r, "liw_gmap_layout: bad dims")
+    return {k: getattr(out, k) for k, _ in GmapLayoutC._fields_}
+
+
+def group_store_bytes(G, max_cells):
+    """bytes of the group store (host-only)"""
+    from . import LiwError
+    n = C.c_size_t(0)
+    r = _lib().liw_gmap_store_bytes(C.byref(GmapDimsC(int(G), int(max_cells))), C.byref(n))
+    if r:
+        raise LiwError(r, "liw_gmap_store_bytes: bad dims")
     return n.value
 
 
@@ -235,3 +287,98 @@ class FleetMapper(FleetStore):
     def write_pgm(self, robot, path_stem, palette=None):
         self._sync()
         self._chk(self.L.liw_fmap_write_pgm(self.h, self._ptr(self.store), C.c_int(robot), str(path_stem).encode(), _palette(palette)))
+
+
+class FleetGroupMap(FleetStore):
+    """One shared occupancy grid per group of a FleetMapper's robots (C ABI include/liw_map_group.h): the grid of the concatenation
+    of the members' sub-maps, robot b's moved into its group's frame by T_g_w[b].  mapper: the FleetMapper that holds the sub-maps
+    (its store is read in place; a render overwrites its robots' tf scratch, so mapper.tf(b) returns T_g_l afterwards); G groups
+    of at most max_cells cells each.  Owns the group store (`guard` bytes of 0xA5 on either side for tests) and the outputs gstatus
+    [G] int32 and ginfo [G, INFO_BYTES] uint8: device tensors, valid until the next call.  Every call runs on torch's current
+    stream; reset, render_tf, render and render_all neither synchronise nor read back."""
+
+    _destroy, _last_error = "liw_gmap_destroy", "liw_gmap_last_error"
+
+    def __init__(self, mapper, G, max_cells, guard=0):
+        torch = mapper.torch
+        self.torch, self.LiwError, self.L = torch, mapper.LiwError, _lib()
+        self.mapper, self.G, self.max_cells, self.dev = mapper, int(G), int(max_cells), mapper.dev
+        self.B = mapper.B
+        self.lay = group_layout(self.G, self.max_cells)
+        self.h = C.c_void_p(self.L.liw_gmap_create(mapper.h, C.byref(GmapDimsC(self.G, self.max_cells))))
+        if not self.h:
+            raise self.LiwError(-22, "liw_gmap_create: bad dims")
+        self._alloc_store(guard)
+        self.gstatus = torch.zeros(self.G, dtype=torch.int32, device=self.dev)
+        self.ginfo = torch.zeros(self.G, INFO_BYTES, dtype=torch.uint8, device=self.dev)
+        self.reset()
+
+    def _gmask(self, m):
+        return None if m is None else self._t(m, self.torch.uint8, (self.G,))
+
+    def reset(self, gmask=None):
+        m = self._gmask(gmask)
+        self._chk(self.L.liw_gmap_reset(self.h, self._ptr(self.store), self._ptr(m), self._stream()))
+
+    def _render(self, fn, a, width, group_of, T_g_w, gsel):
+        torch = self.torch
+        t, stride = self.mapper._strided(a, width)
+        go = self._t(group_of, torch.int32, (self.B,))
+        tg = None if T_g_w is None else self._t(T_g_w, torch.float64, (self.B, 12))
+        s = self._gmask(gsel)
+        self._keep = (t, go, tg, s)   # the kernels read them after this call has returned
+        self._chk(fn(self.h, self._ptr(self.mapper.store), self._ptr(self.store), self._ptr(t), C.c_longlong(stride), self._ptr(go), self._ptr(tg),
+                     self._ptr(s), self._ptr(self.gstatus), self._ptr(self.ginfo), self._stream()))
+        return dict(status=self.gstatus, info=self.ginfo)
+
+    def render_tf(self, T_w_l, group_of, T_g_w=None, gsel=None):
+        """T_w_l [B, n, 12] as FleetMapper.render_tf takes it; group_of [B] int32 (outside 0 .. G-1: in no group); T_g_w [B, 12] group
+        <- robot world (None: T_w_l is used bit for bit); gsel [G] uint8 (None: all) -> dict(status [G] int32, info [G, INFO_BYTES])"""
+        return self._render(self.L.liw_gmap_render_tf, T_w_l, 12, group_of, T_g_w, gsel)
+
+    def render(self, poses, group_of, T_g_w=None, gsel=None):
+        """the same from IMU poses [B, n, 6] (p, rotation vector), e.g. FleetBackEnd.poses()"""
+        return self._render(self.L.liw_gmap_render, poses, 6, group_of, T_g_w, gsel)
+
+    def render_all(self, backend, group_of, T_g_w=None, gsel=None):
+        """the end of a log: every (selected) group's map from the back-end's corrected poses"""
+        return self.render(backend.poses(), group_of, T_g_w=T_g_w, gsel=gsel)
+
+    def group_regions(self):
+        """[G, group_bytes] uint8 view of the group regions"""
+        return self.store.view(self.G, self.lay["group_bytes"])
+
+    # ---- inspection (synchronous)
+    def infos(self):
+        """the info rows of the last render as dicts"""
+        self._sync()
+        return info_rows(self.ginfo.cpu().numpy())
+
+    def info_of(self, g):
+        """info dict of the grid the group holds, with `status` of its last render"""
+        self._sync()
+        i, st = MapInfoC(), C.c_int(0)
+        self._chk(self.L.liw_gmap_last_info(self.h, self._ptr(self.store), C.c_int(g), C.byref(i), C.byref(st)))
+        return dict(_info_dict(i), status=st.value)
+
+    def members(self, g):
+        """(member robots, sub-maps used) of the group's last render"""
+        self._sync()
+        r, k = C.c_int(0), C.c_int(0)
+        self._chk(self.L.liw_gmap_members(self.h, self._ptr(self.store), C.c_int(g), C.byref(r), C.byref(k)))
+        return r.value, k.value
+
+    def grid(self, g):
+        """the grid the group holds, int8 [height][width]"""
+        i = self.info_of(g)
+        n = i["width"] * i["height"]
+        out = np.zeros(max(n, 1), dtype=np.int8)
+        self._chk(self.L.liw_gmap_get(self.h, self._ptr(self.store), C.c_int(g), out.ctypes.data_as(C.POINTER(C.c_byte)), C.c_longlong(n)))
+        return out[:n].reshape(i["height"], i["width"])
+
+    def device_data(self, g):
+        return self.L.liw_gmap_device_data(self.h, self._ptr(self.store), C.c_int(g))
+
+    def write_pgm(self, g, path_stem, palette=None):
+        self._sync()
+        self._chk(self.L.liw_gmap_write_pgm(self.h, self._ptr(self.store), C.c_int(g), str(path_stem).encode(), _palette(palette)))

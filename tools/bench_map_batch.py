@@ -5,8 +5,10 @@ GridMap.render_tf calls, one handle per robot.
 The host loop is linear in the robots by construction (serial calls with two synchronising read-backs each), so it is measured on
 at most --baseline-robots robots and scaled to B; the JSON says which.  Wall times around torch.cuda.synchronize(), the median of
 --reps after one warm-up render.  Per B two rows: every robot selected, and one robot in 16 (the work-groups of the others exit at
-once).  The rows are printed as JSON lines and written to --out (profiles/fleet_map_bench.json).
-  python tools/bench_map_batch.py --fleet 1,64,1024 [--keyframes 200] [--rays 360] [--reps 5]
+once).  With --groups G a third row per B: one FleetGroupMap.render_tf of the whole fleet split evenly into G groups (robot b in
+group b mod G, all in one frame, so every member of a group hits the same walls), next to the per-robot render of the same fleet.
+The rows are printed as JSON lines and written to --out (profiles/fleet_map_bench.json).
+  python tools/bench_map_batch.py --fleet 1,64,1024 [--keyframes 200] [--rays 360] [--reps 5] [--groups 16]
 Under rocprofv3 --kernel-trace --stats: --fleet 1024 --no-baseline --reps 1 --out ''."""
 import argparse
 import importlib
@@ -47,6 +49,7 @@ def main():
     ap.add_argument("--rooms", type=int, default=16)
     ap.add_argument("--baseline-robots", type=int, default=64)
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--groups", type=int, default=0, help="also time one group render of the fleet split evenly into this many groups")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_map_bench.json"))
     a = ap.parse_args()
     import torch
@@ -108,6 +111,30 @@ def main():
                            speedup=round(t_host / t_fleet, 2), robot0_equals_single_map=same)
             print(json.dumps(row), flush=True)
             rows.append(row)
+        if a.groups > 0:
+            G = min(a.groups, B)
+            t_all = next(r["fleet_ms_per_render"] for r in rows if r["B"] == B and r["selected"] == B)
+            gm = liw.FleetGroupMap(fm, G, 2 * cells)     # the rooms differ by a wall stub outside the shared walls
+            group_of = (torch.arange(B, device="cuda") % G).to(torch.int32)
+            ts = []
+            for rep in range(a.reps + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gm.render_tf(T, group_of)
+                torch.cuda.synchronize()
+                if rep:
+                    ts.append(time.perf_counter() - t0)
+            t_group = float(np.median(ts))
+            info = gm.info_of(0)
+            row = dict(bench="fleet_group_map", B=B, groups=G, members=gm.members(0)[0], submaps=gm.members(0)[1], keyframes=K, rays=R,
+                       status_ok=bool((gm.gstatus == 0).all().item()), grid="%d x %d" % (info["width"], info["height"]), rays_cast=info["rays"],
+                       samples=info["samples"], hit_more=info["hit_more"], group_MB=round(gm.lay["group_bytes"] / 1e6, 3),
+                       group_ms_per_render=round(t_group * 1e3, 3), group_us_per_robot=round(t_group * 1e6 / B, 2),
+                       per_robot_ms_per_render=t_all, group_over_per_robot=round(t_group * 1e3 / t_all, 2))
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            gm.close()
+            del gm
         fm.close()
         del fm, T
         if not a.no_baseline:
