@@ -136,34 +136,29 @@ def _lib():
     return L
 
 
-def store_bytes(dims):
-    """bytes of the store for dims (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
+def _layout_bytes(fn, dims):
+    """what the C layout function `fn` answers for dims (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
     from . import LiwError
     n = C.c_size_t(0)
-    r = _lib().liw_lfe_store_layout(C.byref(dims_struct(dims)), C.byref(n))
+    r = getattr(_lib(), fn)(C.byref(dims_struct(dims)), C.byref(n))
     if r < 0:
-        raise LiwError(r, "liw_lfe_store_layout")
+        raise LiwError(r, fn)
     return int(n.value)
+
+
+def store_bytes(dims):
+    """bytes of the store for dims (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
+    return _layout_bytes("liw_lfe_store_layout", dims)
 
 
 def track_bytes(dims):
     """bytes of the tracking record for dims, 256 per robot (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
-    from . import LiwError
-    n = C.c_size_t(0)
-    r = _lib().liw_lfe_track_layout(C.byref(dims_struct(dims)), C.byref(n))
-    if r < 0:
-        raise LiwError(r, "liw_lfe_track_layout")
-    return int(n.value)
+    return _layout_bytes("liw_lfe_track_layout", dims)
 
 
 def init_bytes(dims):
     """bytes of the initialisation record for dims, 256 per robot (host-only; LiwError(LIW_EINVAL) for a non-positive dimension)"""
-    from . import LiwError
-    n = C.c_size_t(0)
-    r = _lib().liw_lfe_init_layout(C.byref(dims_struct(dims)), C.byref(n))
-    if r < 0:
-        raise LiwError(r, "liw_lfe_init_layout")
-    return int(n.value)
+    return _layout_bytes("liw_lfe_init_layout", dims)
 
 
 WINDOW_KEYS = (("imu_X", 15), ("imu_J", 225), ("imu_sqrtP", 225), ("imu_Dt", 1), ("wheel_T", 12), ("wheel_sqrtP", 9))

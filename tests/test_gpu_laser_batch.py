@@ -367,6 +367,38 @@ def test_end_to_end_track_batch(env, synth):
           % (B, F, d_pts, d_state))
 
 
+@pytest.mark.parametrize("B", [1025, 1])
+def test_pack_track_offsets(env, B):
+    """pack_track on its own: laser_off is the exclusive cumulative sum of the counts clamped to [0, cap], Ltot its last element,
+    and laser_frame / laser_pts hold the records in robot order.  B = 1025 gives a thread of the one-block scan more than one
+    robot and is no multiple of its 1 024 threads; counts below 0 and above cap hit both clamps."""
+    liw, lp, sc, torch = env
+    cap, n, frame = 4, 2, 1
+    fe = liw.laser_batch.BatchFrontEnd(lp, dict(B=B, slots=1, max_points=8, max_lines=4, max_cell_entries=16))
+    rng = np.random.default_rng(650 + B)
+    count = rng.choice(np.array([-3, 0, 1, 4, 9], dtype=np.int32), B)
+    if B > 1:
+        assert (count < 0).any() and (count > cap).any()
+    recs, pose = rng.standard_normal((B, cap, 12)), rng.standard_normal((B, 12))
+    m = dict(count=torch.from_numpy(count).cuda(), recs=torch.from_numpy(recs).cuda(), match_pose=torch.from_numpy(pose).cuda(), cap=cap)
+    pk, Ltot = fe.pack_track(m, n=n, frame=frame)
+    torch.cuda.synchronize()
+    kept = np.clip(count, 0, cap)
+    off = np.zeros(B + 1, dtype=np.int32)
+    off[1:] = np.cumsum(kept)
+    assert np.array_equal(pk["laser_off"].cpu().numpy(), off)
+    assert Ltot == int(off[-1])
+    rows = np.concatenate([recs[b, :kept[b]] for b in range(B)], 0)          # [Ltot, 12] in robot order
+    if Ltot:
+        assert np.array_equal(pk["laser_frame"].cpu().numpy(), np.full(Ltot, frame, dtype=np.int32))
+        assert np.array_equal(pk["laser_pts"].cpu().numpy().reshape(12, Ltot), rows.T)
+    else:   # the one entry kept so that no array is empty
+        assert pk["laser_frame"].numel() == 1 and pk["laser_pts"].numel() == 12
+    assert np.array_equal(pk["match_pose"].cpu().numpy().reshape(B, n, 12)[:, frame], pose)
+    assert np.array_equal(pk["has_match"].cpu().numpy().reshape(B, n)[:, frame], np.ones(B, dtype=np.uint8))
+    fe.close()
+
+
 # ------------------------------------------------------------------------------------------------------------------ 7
 def test_scale_determinism(env):
     liw, lp, sc, torch = env
