@@ -494,6 +494,11 @@ int launch_add(char* store, const Lay& L, const Prm& p, const unsigned char* key
     return ok();
 }
 
+int launch_scan(char* store, const Lay& L, hipStream_t s) {
+    hipLaunchKernelGGL(k_floop_scan, dim3(1), dim3(1024), 0, s, store, L);
+    return ok();
+}
+
 int launch_detect(char* store, const Lay& L, const Prm& p, const unsigned char* key, const unsigned char* mask, unsigned char* found, int* edge,
                   double* tf12, long long* stats, hipStream_t s) {
     const long long slots = (long long)L.B * L.NC;

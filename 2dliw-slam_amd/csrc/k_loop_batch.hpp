@@ -56,5 +56,7 @@ int launch_add(char* store, const Lay& L, const Prm& p, const unsigned char* key
                const int* n_corners, const unsigned char* mask, unsigned char* added, hipStream_t s);
 int launch_detect(char* store, const Lay& L, const Prm& p, const unsigned char* key, const unsigned char* mask, unsigned char* found, int* edge,
                   double* tf12, long long* stats, hipStream_t s);
+// k_floop_scan alone (f_cnt, f_cmax -> f_base, f_hdr), for the cross detection of k_loop_cross.hip
+int launch_scan(char* store, const Lay& L, hipStream_t s);
 
 }  // namespace liw_floop_dev

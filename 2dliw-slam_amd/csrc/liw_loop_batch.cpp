@@ -12,6 +12,7 @@
 #include "../../include/liw_loop_batch.h"
 #include "k_loop_batch.hpp"
 #include "liw_host_common.hpp"
+#include "liw_loop_batch_ctx.hpp"
 
 namespace {
 
@@ -57,11 +58,6 @@ bool make_lay(const liw_loop_params* p, const liw_floop_dims* d, Lay* L, int* nA
 }
 
 }  // namespace
-
-struct liw_floop_ctx : liw_fleet_ctx_base {
-    Lay L{};
-    Prm P{};
-};
 
 namespace {
 

@@ -15,6 +15,8 @@ are timed in which a fraction --key-fraction of the robots (staggered) has a key
 construction (serial, a synchronising read-back per call), so it is measured on at most --baseline-robots detectors and scaled to
 B; the JSON says which.  Wall times around torch.cuda.synchronize().  One JSON line per (B, P, fraction).
   python tools/bench_loop.py --fleet 1,64,1024,4096 [--points 10,150] [--key-fraction 1.0,0.25] [--frames 12] [--no-baseline]
+--fleet B[,B...] --cross times liw_xloop_detect (include/liw_loop_cross.h; robots paired 2j <-> 2j + 1, every odd robot queries its even
+partner) beside FleetLoopDetector.detect for the same robots of the same store, and writes the lines to profiles/fleet_cross_loop_bench.json.
 Under rocprofv3 --kernel-trace --stats: --fleet 1024 --points 150 --key-fraction 1.0 --no-baseline."""
 import argparse
 import importlib
@@ -143,6 +145,47 @@ def run_fleet(liw, synth, B, P, frac, preload, frames, baseline_robots):
     return r
 
 
+def run_cross(liw, synth, B, P, preload, frames):
+    """liw_xloop_detect (robots paired 2j <-> 2j + 1, every odd robot queries its even partner) beside FleetLoopDetector.detect for the
+    same odd robots of the same store, in one process.  min_interval = 1, so that own detection walks the same candidate slots but
+    the newest one: the same match bodies over (nearly) the same task counts."""
+    import torch
+    lp = liw.loop
+    p = dict(lp.office_loop_params(), min_interval=1)
+    sc = p["submap_count"]
+    S = scene(P)
+    slices = np.array_split(np.arange(P), sc)
+    stride = max(len(s) for s in slices)
+    fl = liw.FleetLoopDetector(synth.office_params(), p, dict(B=B, max_keyframes=preload, max_points=P, max_kf_corners=stride))
+    pose = torch.zeros(B, 6, dtype=torch.float64, device="cuda")
+    ones = torch.ones(B, dtype=torch.uint8, device="cuda")
+    for k in range(preload):
+        c = S[slices[k % sc]]
+        a = np.zeros((stride, 3))
+        a[:len(c)] = c
+        fl.add_keyframes(ones, pose, torch.from_numpy(a).cuda().expand(B, stride, 3).contiguous(), torch.full((B,), len(c), dtype=torch.int32, device="cuda"))
+    odd = (np.arange(B) % 2 == 1) & (np.arange(B) < B - B % 2 + 1)
+    key = torch.from_numpy(odd.astype(np.uint8)).cuda()
+    partner = torch.from_numpy(np.where(odd, np.arange(B) - 1, -1).astype(np.int32)).cuda()
+    al = liw.FleetGroupAligner(fl, np.zeros(B, np.int32), [0], p["min_match_threshold"], 0.05)
+    res = {}
+    for name, fn in (("cross", lambda: al.detect_cross(key, partner)), ("detect", lambda: fl.detect(key))):
+        ts = []
+        for f in range(frames + 2):               # two warm-up calls
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if f >= 2:
+                ts.append(time.perf_counter() - t0)
+        st = out["stats"].cpu().numpy()[odd] if odd.any() else np.zeros((1, 6), np.int64)
+        res[name] = dict(ms=1e3 * float(np.median(ts)), ms_min=1e3 * float(np.min(ts)), ms_max=1e3 * float(np.max(ts)), found=int(out["found"].sum()),
+                         candidates_per_robot=int(st[:, 0].max()), launched_per_robot=int(st[:, 1].max()), tasks_per_robot=int(st[:, 2].max()))
+    fl.close()
+    return dict(fleet=B, points=P, preload=preload, frames=frames, queries=int(odd.sum()), cross=res["cross"], detect=res["detect"],
+                ratio=res["cross"]["ms"] / res["detect"]["ms"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", default="500,2000,5000")
@@ -154,9 +197,19 @@ def main():
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--baseline-robots", type=int, default=64)
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--cross", action="store_true", help="with --fleet: time liw_xloop_detect (2j <-> 2j + 1, odd robots query) beside detect")
     a = ap.parse_args()
     liw = importlib.import_module("2dliw-slam_amd")
     synth = importlib.import_module("2dliw-slam_amd.synth")
+    if a.fleet and a.cross:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "fleet_cross_loop_bench.json"), "w") as f:
+            for B in [int(v) for v in a.fleet.split(",")]:
+                for P in [int(v) for v in (a.points or "10,150").split(",")]:
+                    line = json.dumps(run_cross(liw, synth, B, P, a.preload, a.frames))
+                    print(line, flush=True)
+                    f.write(line + "\n")
+        return
     if a.fleet:
         for B in [int(v) for v in a.fleet.split(",")]:
             for P in [int(v) for v in (a.points or "10,150").split(",")]:
