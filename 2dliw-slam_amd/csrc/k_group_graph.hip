@@ -1,0 +1,549 @@
+// k_group_graph.hip — the group pose graph of the fleet on the MI355X (C ABI include/liw_group_graph.h, host side
+// liw_group_graph.cpp): the cross edges of a group are kept, and T_g_w of its linked robots is refined from all of them and from the
+// back-end's current corrected poses.
+//   k_ggraph_reset      a work-group per group: header and edge records cleared.
+//   k_ggraph_add_edges  a wave per group walks the fleet 64 robots at a time: the checks, the duplicate scan of the held list by the
+//                       lanes, the position by ballot and prefix count in robot order.
+//   k_ggraph_partner    a wave per robot counts and picks the other linked members of its group with ballots (k_xloop_partner's
+//                       body with the robot itself left out, which changes nothing for an unlinked robot).
+//   k_ggraph_solve      a work-group per group runs the WHOLE Levenberg-Marquardt loop in one launch: node list by ballots, Z per
+//                       edge, then per iteration what k_posegraph_batch.hip spreads over eight launches: 16 lanes per edge with a
+//                       dual direction per lane (edge_res / plus_jac of k_posegraph_dev.hpp), a wave per node gathers its blocks in
+//                       edge order, the packed triangle (LDS when it fits, else the work area: the same instructions on another
+//                       pointer), right-looking Cholesky and both triangular solves, and wave 0 takes the decisions of
+//                       liw_lm_rules.hpp.  A group is small (a few dozen nodes), so the loop is bound by latency, not by width.
+// No atomics.  Every sum runs in an order fixed by the group's own graph: results are reproducible bit for bit.
+#pragma clang fp contract(off)   // Z is liw_lie_mul's product bit for bit
+
+#include <hip/hip_runtime.h>
+
+#include "k_group_graph.hpp"
+#include "k_posegraph_dev.hpp"
+#include "k_posegraph_lm_dev.hpp"
+#include "liw_dual.hpp"
+#include "liw_lm_rules.hpp"
+
+namespace liw_ggraph_dev {
+
+using namespace liw;
+
+using IsoD = Iso<double>;
+
+enum { PH_IDLE = 0, PH_SOLVE = 1, PH_CAND = 2, PH_ASM = 3, PH_INIT = 4 };
+// LM state of a group (head of its work area)
+struct Lm {
+    double radius, dec, x_cost, x_norm, gmax, mcc, init_cost, step_norm;
+    int iter, invalid, succ, last_ok, term, reuse, done, phase, N, ne, used, anyfixed;
+};
+static_assert(sizeof(Lm) <= 256, "the LM state has 256 bytes");
+
+struct Wk {   // a group's work area
+    Lm* lm; int *nodes, *cst, *enode; double *x, *cand, *y, *scale, *dgn, *gd, *Dd, *Ye, *Z, *Hr, *rhs;
+};
+__device__ __forceinline__ char* region(char* store, const Lay& L, int g) { return store + (size_t)g * L.group_bytes; }
+__device__ __forceinline__ Wk work_of(char* store, const Lay& L, int g) {
+    char* W = store + L.work_off + (size_t)g * L.work_group_bytes;
+    Wk w;
+    w.lm = (Lm*)W;
+    w.nodes = (int*)(W + L.w_nodes); w.cst = (int*)(W + L.w_const); w.enode = (int*)(W + L.w_enode);
+    w.x = (double*)(W + L.w_x); w.cand = (double*)(W + L.w_cand); w.y = (double*)(W + L.w_y); w.scale = (double*)(W + L.w_scale);
+    w.dgn = (double*)(W + L.w_dgn); w.gd = (double*)(W + L.w_gd); w.Dd = (double*)(W + L.w_Dd); w.Ye = (double*)(W + L.w_Ye);
+    w.Z = (double*)(W + L.w_Z); w.Hr = (double*)(W + L.w_Hr); w.rhs = (double*)(W + L.w_rhs);
+    return w;
+}
+__device__ __forceinline__ bool robot_on(const unsigned char* a, int b) { return !a || a[b] != 0; }
+
+__device__ __forceinline__ IsoD load_iso(const double* T) { return cast_iso<double>(T, T + 9); }
+__device__ __forceinline__ void store_iso(const IsoD& A, double* T) {
+    for (int k = 0; k < 9; ++k) T[k] = A.R.m[k];
+    T[9] = A.t.x; T[10] = A.t.y; T[11] = A.t.z;
+}
+__device__ __forceinline__ IsoD tf_of_pose(const double* ps) {   // make_tf with the correctly rounded sin / cos
+    const Iso<CR> T = make_tf(V3<CR>(ps[0], ps[1], ps[2]), V3<CR>(ps[3], ps[4], ps[5]));
+    IsoD o;
+    for (int k = 0; k < 9; ++k) o.R.m[k] = T.R.m[k].v;
+    o.t = V3<double>(T.t.x.v, T.t.y.v, T.t.z.v);
+    return o;
+}
+__device__ __forceinline__ void pose_of_tf(const double* tf, double* ps) {   // log_SE3: p = t, q = log_SO3(R)
+    const V3<CR> q = log_SO3(cast_iso<CR>(tf, tf + 9).R);
+    ps[0] = tf[9]; ps[1] = tf[10]; ps[2] = tf[11]; ps[3] = q.x.v; ps[4] = q.y.v; ps[5] = q.z.v;
+}
+
+
+// ------------------------------------------------------------------------------------------------------------- the edge lists
+__global__ __launch_bounds__(256) void k_ggraph_reset(char* store, Lay L, const unsigned char* __restrict__ gmask) {
+    const int g = blockIdx.x;
+    if (!robot_on(gmask, g)) return;
+    int* R = (int*)region(store, L, g);
+    const size_t words = L.group_bytes / 4;
+    for (size_t k = threadIdx.x; k < words; k += 256) R[k] = 0;
+}
+
+__global__ __launch_bounds__(64) void k_ggraph_add_edges(char* store, Lay L, const int* __restrict__ group_of, const unsigned char* __restrict__ found,
+                                                         const int* __restrict__ edge, const double* __restrict__ tf12, const unsigned char* __restrict__ mask) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    char* R = region(store, L, g);
+    int* hdr = (int*)R;
+    const int n0 = min(max(hdr[H_NE], 0), L.E);   // held before this call: a robot is walked once, so a duplicate can only be among these
+    int n = n0;
+    bool bad_any = false, full_any = false;
+    for (int a0 = 0; a0 < L.B; a0 += 64) {
+        const int a = a0 + lane;
+        const bool cand = a < L.B && robot_on(mask, a) && found[a] != 0 && group_of[a] == g;
+        int q = 0, b = 0, i = 0, size = 0;
+        if (cand) { q = edge[(size_t)a * 4]; b = edge[(size_t)a * 4 + 1]; i = edge[(size_t)a * 4 + 2]; size = edge[(size_t)a * 4 + 3]; }
+        const bool bad = cand && (b < 0 || b >= L.B || b == a || group_of[b] != g);
+        bool keep = cand && !bad;
+        if (keep)
+            for (int e = 0; e < n0; ++e) {
+                const int* rec = (const int*)(R + kHeaderBytes + (size_t)e * kEdgeBytes);
+                if (rec[0] == a && rec[1] == q && rec[2] == b && rec[3] == i) keep = false;
+            }
+        const unsigned long long m = __ballot(keep);
+        const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && pos < L.E) {
+            char* rec = R + kHeaderBytes + (size_t)pos * kEdgeBytes;
+            int* ri = (int*)rec;
+            ri[0] = a; ri[1] = q; ri[2] = b; ri[3] = i; ri[4] = size; ri[5] = 0; ri[6] = 0; ri[7] = 0;
+            double* rt = (double*)(rec + kEdgeTf);
+            for (int k = 0; k < 12; ++k) rt[k] = tf12[(size_t)a * 12 + k];
+        }
+        bad_any = bad_any || __ballot(bad) != 0ull;
+        full_any = full_any || n + __popcll(m) > L.E;
+        n = min(n + __popcll(m), L.E);
+    }
+    if (lane == 0) {
+        if (n != n0) hdr[H_NE] = n;
+        if (full_any) hdr[H_EFULL] = 1;
+        if (bad_any) hdr[H_BAD] = 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_ggraph_partner(int B, const int* __restrict__ group_of, const unsigned char* __restrict__ linked, int round,
+                                                       int* __restrict__ partner) {
+    const int a = blockIdx.x, lane = threadIdx.x;
+    const int g = group_of[a];
+    int pick = -1;
+    if (g >= 0) {
+        int n = 0;
+        for (int m0 = 0; m0 < B; m0 += 64) {
+            const int m = m0 + lane;
+            n += __popcll(__ballot(m < B && m != a && linked[m] && group_of[m] == g));
+        }
+        if (n > 0) {
+            int want = round % n;    // the want-th other linked member in index order
+            for (int m0 = 0; m0 < B && pick < 0; m0 += 64) {
+                const int m = m0 + lane;
+                unsigned long long bal = __ballot(m < B && m != a && linked[m] && group_of[m] == g);
+                const int c = __popcll(bal);
+                if (want >= c) { want -= c; continue; }
+                for (int k = 0; k < want; ++k) bal &= bal - 1;   // drop the lowest `want` set bits
+                pick = m0 + __ffsll(bal) - 1;
+            }
+        }
+    }
+    if (lane == 0) partner[a] = pick;
+}
+
+// ------------------------------------------------------------------------------------------------------------- the solve
+
+// Y of edge e [6][13] = [J | r] at x (which = 0) or at the candidate; all 256 threads, 16 edges a pass
+__device__ __forceinline__ void linearize(const Wk& w, const Noise& noise, int ne, int which, int tid) {
+    const int sub = tid >> 4, d = tid & 15;
+    const double* x = which ? w.cand : w.x;
+    for (int e0 = 0; e0 < ne; e0 += 16) {
+        const int e = e0 + sub;
+        const bool on = e < ne && w.enode[3 * e + 2] != 0;
+        const int i = on ? w.enode[3 * e] : 0, j = on ? w.enode[3 * e + 1] : 0;
+        const double* xi = x + (size_t)i * 6;
+        const double* xj = x + (size_t)j * 6;
+        double* Y = w.Ye + (size_t)(on ? e : 0) * 78;
+        if (on && d < 13) {
+            LJ pi[3], qi[3], pj[3], qj[3], res[6];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                pi[k] = LJ(xi[k], d == k ? 1.0 : 0.0);
+                qi[k] = LJ(xi[3 + k], d == 3 + k ? 1.0 : 0.0);
+                pj[k] = LJ(xj[k], d == 6 + k ? 1.0 : 0.0);
+                qj[k] = LJ(xj[3 + k], d == 9 + k ? 1.0 : 0.0);
+            }
+            edge_res<LJ>(w.Z + (size_t)e * 36, 1.0, noise.J, pi, qi, pj, qj, res);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) Y[r * 13 + d] = d < 12 ? res[r].d : res[r].v;
+        }
+        __syncthreads();
+        if (on && d < 12) {   // local parameterisation: J_theta <- J_theta * dPlus/ddelta  (lane = (row r, pose side))
+            const int r = d % 6, side = d / 6;
+            double Pq[9];
+            if (plus_jac((side ? xj : xi) + 3, Pq)) {
+                double* row = &Y[r * 13 + 6 * side + 3];
+                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
+                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
+                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
+                row[0] = t0; row[1] = t1; row[2] = t2;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// a wave per node: 6x6 diagonal block and gradient, gathered over the node's edges in list order; a constant node gets the identity
+__device__ __forceinline__ void assemble(const Wk& w, int N, int ne, int wave, int lane) {
+    const int r = lane / 6, c = lane % 6;
+    for (int k = wave; k < N; k += 4) {
+        const bool is_const = w.cst[k] != 0;
+        double acc = 0.0;
+        if (!is_const)
+            for (int e = 0; e < ne; ++e) {
+                if (!w.enode[3 * e + 2]) continue;
+                int side;
+                if (w.enode[3 * e] == k) side = 0; else if (w.enode[3 * e + 1] == k) side = 1; else continue;
+                const double* Y = w.Ye + (size_t)e * 78;
+                double sm = 0.0;
+                if (lane < 36) {
+#pragma unroll
+                    for (int t = 0; t < 6; ++t) sm += Y[t * 13 + 6 * side + r] * Y[t * 13 + 6 * side + c];
+                } else if (lane < 42) {
+#pragma unroll
+                    for (int t = 0; t < 6; ++t) sm += Y[t * 13 + 6 * side + (lane - 36)] * Y[t * 13 + 12];
+                }
+                acc += sm;
+            }
+        if (is_const && lane < 36) acc = r == c ? 1.0 : 0.0;
+        if (lane < 36) w.Dd[(size_t)k * 36 + lane] = acc;
+        else if (lane < 42) w.gd[k * 6 + (lane - 36)] = acc;
+    }
+}
+
+// 1/2 sum r^2 of the used edges, by one wave
+__device__ __forceinline__ double cost_of(const Wk& w, int ne, int lane) {
+    double s = 0.0;
+    for (int e = lane; e < ne; e += 64)
+        if (w.enode[3 * e + 2])
+#pragma unroll
+            for (int r = 0; r < 6; ++r) { const double v = w.Ye[(size_t)e * 78 + r * 13 + 12]; s += v * v; }
+    return 0.5 * wave_sum(s);
+}
+
+// the group is done (wave 0): T_g_w of its non-constant nodes unless the solve failed, the summary, the header
+__device__ __forceinline__ void finish(int* hdr, const Wk& w, int N, int iter, int succ, double init_cost, double x_cost, int term, double* T_g_w,
+                                       liw_summary* summary_g, int lane) {
+    const bool failed = term == 6 || !isfinite(x_cost) || !isfinite(init_cost);
+    if (!failed)
+        for (int k = lane; k < N; k += 64)
+            if (!w.cst[k]) store_iso(tf_of_pose(w.x + (size_t)k * 6), T_g_w + (size_t)w.nodes[k] * 12);
+    if (lane == 0) {
+        liw_summary sm;
+        sm.iterations = iter; sm.successful_steps = succ; sm.termination = term; sm.initial_cost = init_cost; sm.final_cost = x_cost;
+        *(liw_summary*)((char*)hdr + HB_SUMMARY) = sm;
+        *summary_g = sm;
+        hdr[H_SOLVES] += 1;
+        w.lm->term = term;   // the rest of the state is not read again
+        w.lm->done = 1;
+    }
+}
+
+// wave 0: cost / norms of a new point, termination 1 / 4 / 5, the LM diagonal (k_fpg_head)
+__device__ __forceinline__ void head(int* hdr, const Wk& w, int max_iters, double* T_g_w, liw_summary* summary_g, int lane) {
+    Lm s = *w.lm;
+    const int N = s.N, n = 6 * N;
+    if (s.phase == PH_INIT) {
+        s.x_cost = cost_of(w, s.ne, lane);
+        s.init_cost = s.x_cost;
+        for (int i = lane; i < n; i += 64) w.scale[i] = w.cst[i / 6] ? 1.0 : 1.0 / (1.0 + sqrt(w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7]));
+    }
+    if (s.phase == PH_INIT || s.phase == PH_ASM) {
+        double sq = 0.0, m = 0.0;
+        for (int i = lane; i < n; i += 64)
+            if (!w.cst[i / 6]) sq += w.x[i] * w.x[i];
+        s.x_norm = sqrt(wave_sum(sq));
+        for (int f = lane; f < N; f += 64) {   // max |x - Plus(x, -g)|
+            if (w.cst[f]) continue;
+            double ng[6], xp[6];
+            for (int k = 0; k < 6; ++k) ng[k] = -w.gd[f * 6 + k];
+            plus6(w.x + (size_t)f * 6, ng, xp);
+            for (int k = 0; k < 6; ++k) m = max_skip_nan(m, fabs(w.x[f * 6 + k] - xp[k]));
+        }
+        s.gmax = wave_max(m);
+    }
+    int term = 0;
+    if (lm_cap_reached(s.iter, max_iters, s.phase == PH_INIT)) term = 4;
+    else term = lm_gradient_term(s.iter == 0, s.last_ok != 0, s.gmax, s.radius > kMinRadius);
+    if (term) {
+        finish(hdr, w, s.N, s.iter, s.succ, s.init_cost, s.x_cost, term, T_g_w, summary_g, lane);
+        return;
+    }
+    ++s.iter;
+    if (!s.reuse)
+        for (int i = lane; i < n; i += 64) {
+            const double sc = w.scale[i];
+            double v = w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7] * sc * sc;   // clamped as std::min(std::max(v, lo), hi) does: a NaN stays
+            v = (v < kMinDiag) ? kMinDiag : v;
+            v = (kMaxDiag < v) ? kMaxDiag : v;
+            w.dgn[i] = w.cst[i / 6] ? 0.0 : v;
+        }
+    s.reuse = 1;
+    s.phase = PH_SOLVE;
+    if (lane == 0) *w.lm = s;
+}
+
+// all 256 threads: (J'J scaled + D^2 / radius) y = g scaled on the packed triangle A; false when a pivot is not positive and finite
+__device__ __forceinline__ bool reduced(const Wk& w, double* A, int N, int ne, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int nr = 6 * N, tri_n = nr * (nr + 1) / 2;
+    double* rhs = w.rhs;
+    const double radius = w.lm->radius;
+    for (int e = tid; e < tri_n; e += 256) A[e] = 0.0;
+    __syncthreads();
+    for (int t = wave; t < N; t += 4) {
+        const int r = lane / 6, c = lane % 6;
+        const double* sf = w.scale + (size_t)t * 6;
+        const bool is_const = w.cst[t] != 0;
+        if (lane < 36) {
+            const double v = is_const ? (r == c ? 1.0 : 0.0) : w.Dd[(size_t)t * 36 + lane] * sf[r] * sf[c] + (r == c ? w.dgn[(size_t)t * 6 + c] / radius : 0.0);
+            if (r >= c) A[tri(t * 6 + r, t * 6 + c)] = v;
+        } else if (lane < 42) {
+            const int k = lane - 36;
+            rhs[t * 6 + k] = is_const ? 0.0 : w.gd[(size_t)t * 6 + k] * sf[k];
+        }
+    }
+    __syncthreads();
+    if (wave == 0 && lane < 36) {   // off-diagonal blocks in list order by one wave (several edges may share a block); a lane owns the
+        const int r = lane / 6, c = lane % 6;   // same entry (row r of the higher node, column c of the lower) whatever the edge's direction
+        for (int e = 0; e < ne; ++e) {
+            if (!w.enode[3 * e + 2]) continue;
+            const int i1 = w.enode[3 * e], i2 = w.enode[3 * e + 1];
+            if (w.cst[i1] || w.cst[i2]) continue;
+            const double* Y = w.Ye + (size_t)e * 78;
+            const int ra = i1 > i2 ? r : c, cb = i1 > i2 ? c : r;   // H[i1, i2](ra, cb) = sum_k J1[k][ra] J2[k][cb]
+            double o = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o += Y[k * 13 + ra] * Y[k * 13 + 6 + cb];
+            const double v = o * w.scale[(size_t)i1 * 6 + ra] * w.scale[(size_t)i2 * 6 + cb];
+            const int hi = i1 > i2 ? i1 : i2, lo = i1 > i2 ? i2 : i1;
+            A[tri(hi * 6 + r, lo * 6 + c)] += v;
+        }
+    }
+    __syncthreads();
+#include "k_pg_chol_body.inc"
+    for (int e = tid; e < nr; e += 256) w.y[e] = rhs[e];
+    return ok;
+}
+
+// wave 0: step validity, model cost change, Plus into the candidate, step norm; termination 6 (k_fpg_decide1)
+__device__ __forceinline__ void decide1(int* hdr, const Wk& w, bool chol_ok, double* T_g_w, liw_summary* summary_g, int lane) {
+    Lm s = *w.lm;
+    const int N = s.N, n = 6 * N;
+    bool fin = true;
+    for (int i = lane; i < n; i += 64) fin = fin && isfinite(w.y[i]);
+    const bool solved = chol_ok && __ballot(!fin) == 0ull;
+    // model cost change with (A + D^2) y = g_s, step = -y:  (y'g_s + y'D^2 y) / 2
+    double mcc = 0.0;
+    if (solved) {
+        double ytg = 0.0, dsum = 0.0;
+        for (int i = lane; i < n; i += 64) {
+            if (w.cst[i / 6]) continue;
+            const double yi = w.y[i];
+            ytg += yi * (w.gd[i] * w.scale[i]);
+            dsum += w.dgn[i] / s.radius * yi * yi;
+        }
+        mcc = 0.5 * (wave_sum(ytg) + wave_sum(dsum));
+    }
+    if (!lm_step_valid(solved, mcc)) {
+        if (lm_gives_up(s.invalid++)) {
+            finish(hdr, w, s.N, s.iter - 1, s.succ, s.init_cost, s.x_cost, 6, T_g_w, summary_g, lane);
+            return;
+        }
+        lm_step_rejected(s.radius, s.dec, s.reuse);
+        s.last_ok = 0;
+        s.phase = PH_IDLE;
+        if (lane == 0) *w.lm = s;
+        return;
+    }
+    s.invalid = 0;
+    s.mcc = mcc;
+    double sq = 0.0;
+    for (int f = lane; f < N; f += 64) {
+        if (w.cst[f]) continue;
+        double dl[6], xc[6];
+        for (int k = 0; k < 6; ++k) dl[k] = -w.y[f * 6 + k] * w.scale[f * 6 + k];
+        plus6(w.x + (size_t)f * 6, dl, xc);
+        for (int k = 0; k < 6; ++k) {
+            w.cand[f * 6 + k] = xc[k];
+            const double df = w.x[f * 6 + k] - xc[k];
+            sq += df * df;
+        }
+    }
+    s.step_norm = sqrt(wave_sum(sq));
+    s.phase = PH_CAND;
+    if (lane == 0) *w.lm = s;
+}
+
+// wave 0: candidate cost, termination 2 / 3, rho, accept / reject, radius (k_fpg_decide2)
+__device__ __forceinline__ void decide2(int* hdr, const Wk& w, double* T_g_w, liw_summary* summary_g, int lane) {
+    Lm s = *w.lm;
+    const int n = 6 * s.N;
+    double cc = cost_of(w, s.ne, lane);
+    if (!isfinite(cc)) cc = kFailedEvalCost;
+    const int term = lm_candidate_term(s.step_norm, s.x_norm, s.x_cost, cc);
+    if (term) {
+        finish(hdr, w, s.N, s.iter, s.succ, s.init_cost, s.x_cost, term, T_g_w, summary_g, lane);
+        return;
+    }
+    const double rho = (s.x_cost - cc) / s.mcc;
+    if (lm_accepts(rho)) {
+        for (int i = lane; i < n; i += 64) w.x[i] = w.cand[i];
+        s.x_cost = cc;
+        lm_step_accepted(rho, s.radius, s.dec, s.reuse);
+        ++s.succ;
+        s.last_ok = 1;
+        s.phase = PH_ASM;
+    } else {
+        lm_step_rejected(s.radius, s.dec, s.reuse);
+        s.last_ok = 0;
+        s.phase = PH_IDLE;
+    }
+    if (lane == 0) *w.lm = s;
+}
+
+// what wave 0 left in the LM state, read by every thread between two barriers (wave 0 may write the state again right afterwards)
+__device__ __forceinline__ void state(const Wk& w, int& done, int& phase) {
+    __syncthreads();
+    const volatile Lm* s = w.lm;
+    done = s->done; phase = s->phase;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_ggraph_solve(char* store, Lay L, Noise noise, const double* __restrict__ poses, long long robot_stride,
+                                                      const int* __restrict__ n_keyframes, const int* __restrict__ group_of,
+                                                      const unsigned char* __restrict__ linked, const unsigned char* __restrict__ fixed, double* T_g_w,
+                                                      const unsigned char* __restrict__ gsel, int max_iters, int lds_doubles, liw_summary* summary) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!gsel[g]) return;
+    char* R = region(store, L, g);
+    int* hdr = (int*)R;
+    Wk w = work_of(store, L, g);
+    // nodes: the linked members in index order, by ballots and prefix counts
+    if (wave == 0) {
+        int base = 0;
+        bool anyfixed = false;
+        for (int r0 = 0; r0 < L.B; r0 += 64) {
+            const int r = r0 + lane;
+            const bool flag = r < L.B && linked[r] != 0 && group_of[r] == g;
+            const bool fx = flag && fixed[r] != 0;
+            const unsigned long long m = __ballot(flag);
+            const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (flag && pos < L.M) { w.nodes[pos] = r; w.cst[pos] = fx ? 1 : 0; }
+            anyfixed = anyfixed || __ballot(fx) != 0ull;
+            base += __popcll(m);
+        }
+        if (lane == 0) { w.lm->N = base; w.lm->anyfixed = anyfixed ? 1 : 0; w.lm->ne = min(max(hdr[H_NE], 0), L.E); }
+    }
+    __syncthreads();
+    const int N = w.lm->N, ne = w.lm->ne;
+    if (N > L.M) {
+        if (tid == 0) hdr[H_MFULL] = 1;
+        return;
+    }
+    if (N < 2 || ne < 1) return;
+    if (tid == 0 && !w.lm->anyfixed) w.cst[0] = 1;
+    __syncthreads();
+    // edges: node indices, the use flag, Z from the corrected poses
+    for (int e = tid; e < ne; e += 256) {
+        const char* rec = R + kHeaderBytes + (size_t)e * kEdgeBytes;
+        const int* ri = (const int*)rec;
+        const int a = ri[0], q = ri[1], b = ri[2], i = ri[3];
+        int ia = -1, ib = -1;
+        for (int k = 0; k < N; ++k) { const int r = w.nodes[k]; if (r == a) ia = k; if (r == b) ib = k; }
+        bool use = ia >= 0 && ib >= 0 && a != b;   // nodes are robots of 0 .. B-1
+        use = use && q >= 0 && q < n_keyframes[a] && i >= 0 && i < n_keyframes[b] && !(w.cst[ia] && w.cst[ib]);
+        w.enode[3 * e] = ia; w.enode[3 * e + 1] = ib; w.enode[3 * e + 2] = use ? 1 : 0;
+        if (use) {
+            const IsoD Ta = tf_of_pose(poses + (size_t)a * robot_stride + (size_t)q * 6);
+            const IsoD Tb = tf_of_pose(poses + (size_t)b * robot_stride + (size_t)i * 6);
+            double* z = w.Z + (size_t)e * 36;
+            store_iso(mul(mul(Ta, load_iso((const double*)(rec + kEdgeTf))), inverse(Tb)), z);
+            store_iso(Ta, z + 12);
+            store_iso(Tb, z + 24);
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int used = 0;
+        for (int e0 = 0; e0 < ne; e0 += 64) used += __popcll(__ballot(e0 + lane < ne && w.enode[3 * (e0 + lane) + 2] != 0));
+        if (lane == 0) w.lm->used = used;
+    }
+    __syncthreads();
+    const int used = w.lm->used;
+    if (used < 1) return;
+    for (int k = tid; k < N; k += 256) {
+        double ps[6];
+        pose_of_tf(T_g_w + (size_t)w.nodes[k] * 12, ps);
+        for (int t = 0; t < 6; ++t) { w.x[k * 6 + t] = ps[t]; w.cand[k * 6 + t] = ps[t]; w.y[k * 6 + t] = 0.0; }
+    }
+    if (tid == 0) {
+        Lm s;
+        s.radius = kInitRadius; s.dec = 2.0; s.x_cost = 0.0; s.x_norm = 0.0; s.gmax = 0.0; s.mcc = 0.0; s.init_cost = 0.0; s.step_norm = 0.0;
+        s.iter = 0; s.invalid = 0; s.succ = 0; s.last_ok = 1; s.term = 0; s.reuse = 0; s.done = 0; s.phase = PH_INIT; s.N = N; s.ne = ne; s.used = used;
+        s.anyfixed = w.lm->anyfixed;
+        *w.lm = s;
+        hdr[H_SKIPPED] = ne - used; hdr[H_NODES] = N; hdr[H_USED] = used;
+    }
+    __syncthreads();
+    const int K = max_iters > 0 ? max_iters : 50;
+    const int nr = 6 * N, tri_n = nr * (nr + 1) / 2;
+    double* A = tri_n <= lds_doubles ? lds : w.Hr;   // the same instructions either way
+    liw_summary* sg = summary + g;
+    linearize(w, noise, ne, 0, tid);
+    assemble(w, N, ne, wave, lane);
+    __syncthreads();
+    for (;;) {   // ends by termination: the iteration cap (4) at the latest
+        int done, phase;
+        if (wave == 0) head(hdr, w, K, T_g_w, sg, lane);
+        state(w, done, phase);
+        if (done) break;
+        const bool ok = reduced(w, A, N, ne, tid);
+        __syncthreads();
+        if (wave == 0) decide1(hdr, w, ok, T_g_w, sg, lane);
+        state(w, done, phase);
+        if (done) break;
+        if (phase != PH_CAND) continue;
+        linearize(w, noise, ne, 1, tid);
+        if (wave == 0) decide2(hdr, w, T_g_w, sg, lane);
+        state(w, done, phase);
+        if (done) break;
+        if (phase == PH_ASM) assemble(w, N, ne, wave, lane);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- launches
+static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+
+int launch_reset(char* store, const Lay& L, const unsigned char* gmask, hipStream_t s) {
+    hipLaunchKernelGGL(k_ggraph_reset, dim3(L.G), dim3(256), 0, s, store, L, gmask);
+    return launched();
+}
+int launch_add_edges(char* store, const Lay& L, const int* group_of, const unsigned char* found, const int* edge, const double* tf12,
+                     const unsigned char* mask, hipStream_t s) {
+    hipLaunchKernelGGL(k_ggraph_add_edges, dim3(L.G), dim3(64), 0, s, store, L, group_of, found, edge, tf12, mask);
+    return launched();
+}
+int launch_partner(int B, const int* group_of, const unsigned char* linked, int round, int* partner, hipStream_t s) {
+    hipLaunchKernelGGL(k_ggraph_partner, dim3(B), dim3(64), 0, s, B, group_of, linked, round, partner);
+    return launched();
+}
+int launch_solve(char* store, const Lay& L, const Noise& noise, const double* poses, long long robot_stride, const int* n_keyframes, const int* group_of,
+                 const unsigned char* linked, const unsigned char* fixed, double* T_g_w, const unsigned char* gsel, int max_iters, int lds_cap_doubles,
+                 liw_summary* summary, hipStream_t s) {
+    // LDS for the triangle: what a full group of this store needs, 64 KiB at the most; a larger triangle runs from the work area
+    const int nr = 6 * L.M, tri_max = nr * (nr + 1) / 2;
+    const int lds_doubles = tri_max <= lds_cap_doubles ? tri_max : lds_cap_doubles;
+    hipLaunchKernelGGL(k_ggraph_solve, dim3(L.G), dim3(256), sizeof(double) * (size_t)lds_doubles, s, store, L, noise, poses, robot_stride, n_keyframes,
+                       group_of, linked, fixed, T_g_w, gsel, max_iters, lds_doubles, summary);
+    return launched();
+}
+
+}  // namespace liw_ggraph_dev

@@ -24,30 +24,12 @@
 // (modify_delta_tf, pending flag, last_solve_time, solves) itself.
 #include "k_posegraph_batch.hpp"
 #include "k_posegraph_dev.hpp"
-#include "liw_crmath.hpp"
+#include "k_posegraph_lm_dev.hpp"
 
 namespace liw_fpg_dev {
 
 using namespace liw;
 
-// A double whose sin / cos / atan2 are the correctly rounded ones of liw_crmath.hpp (as the tracking glue's and k_loop_batch.hip's)
-struct CR {
-    double v;
-    __host__ __device__ CR() : v(0.0) {}
-    __host__ __device__ CR(double c) : v(c) {}  // NOLINT(implicit)
-};
-__host__ __device__ inline CR operator+(const CR& a, const CR& b) { return CR(a.v + b.v); }
-__host__ __device__ inline CR operator-(const CR& a, const CR& b) { return CR(a.v - b.v); }
-__host__ __device__ inline CR operator-(const CR& a) { return CR(-a.v); }
-__host__ __device__ inline CR operator*(const CR& a, const CR& b) { return CR(a.v * b.v); }
-__host__ __device__ inline CR operator/(const CR& a, const CR& b) { return CR(a.v / b.v); }
-__host__ __device__ inline bool operator>(const CR& a, const CR& b) { return a.v > b.v; }
-__host__ __device__ inline bool operator<(const CR& a, const CR& b) { return a.v < b.v; }
-__host__ __device__ inline CR dsqrt(const CR& a) { return CR(sqrt(a.v)); }
-__host__ __device__ inline CR dsin(const CR& a) { return CR(liw_cr::cr_sin(a.v)); }
-__host__ __device__ inline CR dcos(const CR& a) { return CR(liw_cr::cr_cos(a.v)); }
-__host__ __device__ inline CR datan2(const CR& y, const CR& x) { return CR(liw_cr::cr_atan2(y.v, x.v)); }
-__host__ __device__ inline CR dfloor(const CR& a) { return CR(floor(a.v)); }
 
 enum { PH_IDLE = 0, PH_SOLVE = 1, PH_CAND = 2, PH_ASM = 3, PH_INIT = 4 };
 // LM state of a robot (head of its work block)
@@ -72,18 +54,6 @@ __device__ __forceinline__ void pose_of_tf(const Iso<CR>& T, double* ps) {
     ps[0] = T.t.x.v; ps[1] = T.t.y.v; ps[2] = T.t.z.v; ps[3] = q.x.v; ps[4] = q.y.v; ps[5] = q.z.v;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// std::max as the host loop folds it: a NaN operand never replaces the running maximum
-__device__ __forceinline__ double max_skip_nan(double m, double v) { return (m < v) ? v : m; }
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max_skip_nan(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------------------- bookkeeping
 __global__ __launch_bounds__(256) void k_fpg_reset(char* store, Lay L, const unsigned char* __restrict__ mask) {
@@ -388,12 +358,6 @@ __device__ __forceinline__ double cost_of(const Lay& L, const Wk& w, int N, int 
     return 0.5 * wave_sum(s);
 }
 
-// Plus of the so3 parameterisation (factor_common.h:41-53): the rotation vectors add, then wrap
-__device__ __forceinline__ void plus6(const double* x, const double* d, double* out) {
-    for (int k = 0; k < 3; ++k) out[k] = x[k] + d[k];
-    const V3<double> r = normalize_so3(V3<double>(x[3] + d[3], x[4] + d[4], x[5] + d[5]));
-    out[3] = r.x; out[4] = r.y; out[5] = r.z;
-}
 
 // the robot is done: poses, summary and keyframe_manager's commit after a solve (mirror :178-188)
 __device__ __forceinline__ void finish(char* store, const Lay& L, int b, const Wk& w, int term, const double* stamp, liw_summary* summary, int lane) {
@@ -474,7 +438,6 @@ __global__ __launch_bounds__(64) void k_fpg_seg_elim(char* store, Lay L) {
     if (!ok && lane == 0) atomicOr(&w.lm->status, 1);
 }
 
-__device__ __forceinline__ size_t tri(int r, int c) { return (size_t)r * (r + 1) / 2 + c; }   // packed lower triangle, c <= r
 
 // work-group per robot: the separators' system A y = g_s (as k_pg_reduced + k_pg_reduced_loops build it), Cholesky, both solves, scatter
 __global__ __launch_bounds__(256) void k_fpg_reduced(char* store, Lay L, int lds_doubles) {
@@ -532,36 +495,7 @@ __global__ __launch_bounds__(256) void k_fpg_reduced(char* store, Lay L, int lds
         }
     }
     __syncthreads();
-    // right-looking Cholesky, a column per step; every thread reads the same pivot
-    bool ok = true;
-    for (int k = 0; k < nr; ++k) {
-        const double piv = A[tri(k, k)];
-        if (!(piv > 0.0) || !isfinite(piv)) ok = false;
-        const double inv = 1.0 / sqrt(piv);
-        __syncthreads();
-        for (int i = k + tid; i < nr; i += 256) A[tri(i, k)] *= inv;   // i = k: sqrt(piv)
-        __syncthreads();
-        const int m = nr - k - 1;
-        for (int e = tid; e < m * m; e += 256) {
-            const int i = k + 1 + e / m, j = k + 1 + e % m;
-            if (j <= i) A[tri(i, j)] -= A[tri(i, k)] * A[tri(j, k)];
-        }
-        __syncthreads();
-    }
-    for (int k = 0; k < nr; ++k) {          // L y = b
-        const double xk = rhs[k] / A[tri(k, k)];
-        __syncthreads();
-        if (tid == 0) rhs[k] = xk;
-        for (int i = k + 1 + tid; i < nr; i += 256) rhs[i] -= A[tri(i, k)] * xk;
-        __syncthreads();
-    }
-    for (int k = nr - 1; k >= 0; --k) {     // L^T x = y
-        const double xk = rhs[k] / A[tri(k, k)];
-        __syncthreads();
-        if (tid == 0) rhs[k] = xk;
-        for (int i = tid; i < k; i += 256) rhs[i] -= A[tri(k, i)] * xk;
-        __syncthreads();
-    }
+#include "k_pg_chol_body.inc"
     for (int e = tid; e < nr; e += 256) w.y[(size_t)sep[e / 6] * 6 + e % 6] = rhs[e];
     if (!ok && tid == 0) atomicOr(&w.lm->status, 1);
 }
