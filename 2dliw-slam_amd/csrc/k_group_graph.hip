@@ -12,6 +12,8 @@
 //                       edge order, the packed triangle (LDS when it fits, else the work area: the same instructions on another
 //                       pointer), right-looking Cholesky and both triangular solves, and wave 0 takes the decisions of
 //                       liw_lm_rules.hpp.  A group is small (a few dozen nodes), so the loop is bound by latency, not by width.
+//   k_ggate             (include/liw_group_gate.h) a work-group per group: the squared residual of every used edge at the last solve's
+//                       x, the edges of a robot pair counted as each other's support, a fixed-order block arg-max, one edge retired.
 // No atomics.  Every sum runs in an order fixed by the group's own graph: results are reproducible bit for bit.
 #pragma clang fp contract(off)   // Z is liw_lie_mul's product bit for bit
 
@@ -459,6 +461,7 @@ __global__ __launch_bounds__(256) void k_ggraph_solve(char* store, Lay L, Noise 
         for (int k = 0; k < N; ++k) { const int r = w.nodes[k]; if (r == a) ia = k; if (r == b) ib = k; }
         bool use = ia >= 0 && ib >= 0 && a != b;   // nodes are robots of 0 .. B-1
         use = use && q >= 0 && q < n_keyframes[a] && i >= 0 && i < n_keyframes[b] && !(w.cst[ia] && w.cst[ib]);
+        use = use && ri[R_STATE] == 0;   // an edge that k_ggate rejected
         w.enode[3 * e] = ia; w.enode[3 * e + 1] = ib; w.enode[3 * e + 2] = use ? 1 : 0;
         if (use) {
             const IsoD Ta = tf_of_pose(poses + (size_t)a * robot_stride + (size_t)q * 6);
@@ -519,6 +522,70 @@ __global__ __launch_bounds__(256) void k_ggraph_solve(char* store, Lay L, Noise 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------- the edge gate
+// include/liw_group_gate.h: a work-group per group works on what the group's last solve left in its work area.  Edges are strided over
+// the threads: c = |edge_res|^2 at the accepted x into the record, the support by a scan of that solve's edge list (E^2 / 256 pair
+// tests a thread), the thread's best candidate; then a block arg-max on (c, index) in a fixed order, and thread 0 retires the winner.
+__global__ __launch_bounds__(256) void k_ggate(char* store, Lay L, Noise noise, const unsigned char* __restrict__ gsel, double chi2_max, int min_support,
+                                               unsigned char* __restrict__ changed) {
+    __shared__ double best_c[256];
+    __shared__ int best_e[256];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    char* R = region(store, L, g);
+    int* hdr = (int*)R;
+    const int solves = hdr[H_SOLVES];
+    const liw_summary sm = *(const liw_summary*)(R + HB_SUMMARY);
+    const bool eligible = gsel[g] != 0 && solves > 0 && solves != hdr[H_GATED] && sm.termination != 6 && isfinite(sm.final_cost);
+    if (!eligible) {   // the same for every thread of the group
+        if (tid == 0) changed[g] = 0;
+        return;
+    }
+    const Wk w = work_of(store, L, g);
+    const int N = min(max(hdr[H_NODES], 0), L.M);                      // of the last completed solve; edges appended since are beyond ne
+    const int ne = min(max(hdr[H_USED] + hdr[H_SKIPPED], 0), L.E);
+    double bc = 0.0;
+    int be = -1;
+    for (int e = tid; e < ne; e += 256) {
+        const int ia = w.enode[3 * e], ib = w.enode[3 * e + 1];
+        if (!w.enode[3 * e + 2] || ia < 0 || ia >= N || ib < 0 || ib >= N) continue;
+        double res[6];
+        const double *xa = w.x + (size_t)ia * 6, *xb = w.x + (size_t)ib * 6;
+        edge_res<double>(w.Z + (size_t)e * 36, 1.0, noise.J, xa, xa + 3, xb, xb + 3, res);
+        double c = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) c += res[r] * res[r];
+        *(double*)(R + kHeaderBytes + (size_t)e * kEdgeBytes + kEdgeChi2) = c;
+        const int lo = min(ia, ib), hi = max(ia, ib);
+        int support = 0;
+        for (int f = 0; f < ne; ++f) {
+            if (f == e || !w.enode[3 * f + 2]) continue;
+            const int ja = w.enode[3 * f], jb = w.enode[3 * f + 1];
+            if (min(ja, jb) == lo && max(ja, jb) == hi) ++support;
+        }
+        if (c > chi2_max && support >= min_support && (be < 0 || c > bc)) { bc = c; be = e; }   // a NaN compares false; e ascends: ties keep the lowest
+    }
+    best_c[tid] = bc; best_e[tid] = be;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            const double oc = best_c[tid + s];
+            const int oe = best_e[tid + s];
+            const int me = best_e[tid];
+            if (oe >= 0 && (me < 0 || oc > best_c[tid] || (oc == best_c[tid] && oe < me))) { best_c[tid] = oc; best_e[tid] = oe; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int e = best_e[0];
+        if (e >= 0) {
+            ((int*)(R + kHeaderBytes + (size_t)e * kEdgeBytes))[R_STATE] = 1;
+            hdr[H_REJECTED] += 1;
+        }
+        hdr[H_GATED] = solves;
+        changed[g] = e >= 0 ? 1 : 0;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------- launches
 static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
@@ -543,6 +610,11 @@ int launch_solve(char* store, const Lay& L, const Noise& noise, const double* po
     const int lds_doubles = tri_max <= lds_cap_doubles ? tri_max : lds_cap_doubles;
     hipLaunchKernelGGL(k_ggraph_solve, dim3(L.G), dim3(256), sizeof(double) * (size_t)lds_doubles, s, store, L, noise, poses, robot_stride, n_keyframes,
                        group_of, linked, fixed, T_g_w, gsel, max_iters, lds_doubles, summary);
+    return launched();
+}
+int launch_gate(char* store, const Lay& L, const Noise& noise, const unsigned char* gsel, double chi2_max, int min_support, unsigned char* changed,
+                hipStream_t s) {
+    hipLaunchKernelGGL(k_ggate, dim3(L.G), dim3(256), 0, s, store, L, noise, gsel, chi2_max, min_support, changed);
     return launched();
 }
 

@@ -11,6 +11,9 @@ namespace liw_ggraph_dev {
 // header of a group region: int32 words, then the summary (byte offsets in include/liw_group_graph.h)
 constexpr int H_NE = 0, H_EFULL = 1, H_MFULL = 2, H_BAD = 3, H_SOLVES = 4, H_SKIPPED = 5, H_NODES = 6, H_USED = 7;
 constexpr size_t HB_SUMMARY = 32, kHeaderBytes = 256, kEdgeBytes = 128, kEdgeTf = 32;
+// what include/liw_group_gate.h adds: two header words behind the summary, and in an edge record the state word and chi2
+constexpr int H_REJECTED = 16, H_GATED = 17, R_STATE = 5;
+constexpr size_t kEdgeChi2 = 24;
 
 struct Lay {
     int B, G, M, E;
@@ -31,5 +34,7 @@ int launch_partner(int B, const int* group_of, const unsigned char* linked, int 
 int launch_solve(char* store, const Lay& L, const Noise& noise, const double* poses, long long robot_stride, const int* n_keyframes, const int* group_of,
                  const unsigned char* linked, const unsigned char* fixed, double* T_g_w, const unsigned char* gsel, int max_iters, int lds_cap_doubles,
                  liw_summary* summary, hipStream_t s);
+int launch_gate(char* store, const Lay& L, const Noise& noise, const unsigned char* gsel, double chi2_max, int min_support, unsigned char* changed,
+                hipStream_t s);
 
 }  // namespace liw_ggraph_dev

@@ -1,13 +1,15 @@
-// liw_group_graph.cpp — host side of the group pose graph (C ABI include/liw_group_graph.h; kernels in k_group_graph.hip): the store
-// layout, argument checks, the launches and the synchronous getters.  No per-group work happens here.  Bad arguments are reported
-// before the missing device, so that the checks run on any machine.
+// liw_group_graph.cpp — host side of the group pose graph (C ABI include/liw_group_graph.h, and include/liw_group_gate.h on the same ctx
+// and store; kernels in k_group_graph.hip): the store layout, argument checks, the launches and the synchronous getters.  No per-group
+// work happens here.  Bad arguments are reported before the missing device, so that the checks run on any machine.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "../../include/liw_group_gate.h"
 #include "../../include/liw_group_graph.h"
 #include "k_group_graph.hpp"
 #include "liw_host_common.hpp"
@@ -198,6 +200,37 @@ int liw_ggraph_get_Z(liw_ggraph_ctx* c, const void* store, int group, int cap, i
         if (Ta) std::copy(s + 12, s + 24, Ta + (size_t)e * 12);
         if (Tb) std::copy(s + 24, s + 36, Tb + (size_t)e * 12);
     }
+    return n;
+}
+
+// ---- include/liw_group_gate.h: the same ctx and store
+int liw_ggate_gate(liw_ggraph_ctx* c, void* store, const unsigned char* gsel, double chi2_max, int min_support, unsigned char* changed, void* stream) {
+    if (!c) return LIW_EINVAL;
+    if (bad_store(store) || !gsel || !changed || !(chi2_max > 0.0) || !std::isfinite(chi2_max) || min_support < 1)
+        return fail(c, LIW_EINVAL, "liw_ggate_gate: bad argument");
+    LIW_FLEET_DEV(c);
+    if (launch_gate((char*)store, c->L, c->noise, gsel, chi2_max, min_support, changed, (hipStream_t)stream))
+        return fail(c, LIW_EHIP, "liw_ggate_gate: kernel launch failed");
+    return LIW_OK;
+}
+
+int liw_ggate_get(liw_ggraph_ctx* c, const void* store, int group, int cap, int* state, double* chi2, int* counts2) {
+    if (!c) return LIW_EINVAL;
+    if (cap < 0) return fail(c, LIW_EINVAL, "liw_ggate_get: cap");
+    int hdr[8];
+    if (int r = group_header(c, store, group, hdr)) return r;
+    const size_t G0 = (size_t)group * c->L.group_bytes;
+    const int n = std::max(0, std::min(hdr[H_NE], c->L.E)), m = std::min(n, cap);
+    std::vector<char> rec((size_t)std::max(m, 1) * kEdgeBytes);
+    int counts[2];
+    if (!pull(store, G0 + kHeaderBytes, rec.data(), (size_t)m * kEdgeBytes) || !pull(store, G0 + 4 * (size_t)H_REJECTED, counts, 2))
+        return fail(c, LIW_EHIP, "liw_ggate_get: hipMemcpy");
+    for (int e = 0; e < m; ++e) {
+        const char* r = rec.data() + (size_t)e * kEdgeBytes;
+        if (state) state[e] = ((const int*)r)[R_STATE];
+        if (chi2) chi2[e] = *(const double*)(r + kEdgeChi2);
+    }
+    if (counts2) { counts2[0] = counts[0]; counts2[1] = counts[1]; }
     return n;
 }
 

@@ -8,6 +8,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import group_gate
 from ._fleet import FleetStore, _pd, _pi
 from .posegraph import PgParamsC, pg_struct
 from .posegraph_batch import SUMMARY_BYTES, summary_rows
@@ -86,12 +87,14 @@ class FleetGroupGraph(FleetStore):
     no edge linked, are the fixed nodes); backend: the FleetBackEnd whose corrected poses are read in place; max_members: linked robots
     a group's solve can hold; max_edges: cross edges kept per group; groups: G (default: the highest group index + 1); pg: dict as
     posegraph.office_pg_params (default: the back-end's), of which the loop sigmas are used; max_iters (<= 0: 50) is the default of
-    solve().  Owns the store (a torch uint8 tensor, with `guard` bytes of 0xA5 on either side for tests) and the outputs partner [B]
-    int32, gsel [G] uint8, summary [G, 32] uint8 (liw_summary rows; summaries() decodes them): views valid until the next call."""
+    solve().  chi2_max (None: no gate), min_support and gate_rounds are the edge gate's (include/liw_group_gate.h): with chi2_max set,
+    push() follows its solve with gate_rounds rounds of gate and re-solve.  Owns the store (a torch uint8 tensor, with `guard` bytes of
+    0xA5 on either side for tests) and the outputs partner [B] int32, gsel [G] uint8, changed [G] uint8, summary [G, 32] uint8
+    (liw_summary rows; summaries() decodes them): views valid until the next call."""
 
     _destroy, _last_error = "liw_ggraph_destroy", "liw_ggraph_last_error"
 
-    def __init__(self, aligner, backend, max_members, max_edges, groups=None, pg=None, guard=0, max_iters=0):
+    def __init__(self, aligner, backend, max_members, max_edges, groups=None, pg=None, guard=0, max_iters=0, chi2_max=None, min_support=2, gate_rounds=2):
         from . import LiwError
         torch = aligner.torch
         self.torch, self.LiwError, self.L = torch, LiwError, _lib()
@@ -106,6 +109,8 @@ class FleetGroupGraph(FleetStore):
         self.dims = dict(B=self.B, G=G, max_members=int(max_members), max_edges=int(max_edges))
         self.lay = layout(self.dims)
         self.max_iters = int(max_iters)
+        self.chi2_max, self.min_support, self.gate_rounds = (None if chi2_max is None else float(chi2_max)), int(min_support), int(gate_rounds)
+        self.Lg = group_gate._lib()
         self._pgs = pg_struct(dict(backend.pg if pg is None else pg))
         index = self.dev.index if self.dev.index is not None else 0
         self.h = C.c_void_p(self.L.liw_ggraph_create(C.byref(self._pgs), C.byref(dims_struct(self.dims)), C.c_int(index)))
@@ -115,6 +120,8 @@ class FleetGroupGraph(FleetStore):
         self.partner = torch.full((self.B,), -1, dtype=torch.int32, device=self.dev)
         self.gsel = torch.zeros(G, dtype=torch.uint8, device=self.dev)
         self.summary = torch.zeros(G, SUMMARY_BYTES, dtype=torch.uint8, device=self.dev)
+        self._changed = [torch.zeros(G, dtype=torch.uint8, device=self.dev) for _ in range(2)]   # a gate reads one and writes the other
+        self.changed, self._ci = self._changed[0], 0
         self._group_index = aligner.group_of.clamp(min=0).long()
         self.round = 0
         self.reset()
@@ -179,10 +186,40 @@ class FleetGroupGraph(FleetStore):
                                           self._stream()))
         return self.summary
 
+    def gate(self, gsel=None, chi2_max=None, min_support=None):
+        """one gate step (liw_ggate_gate) on the groups in gsel [G] uint8 (default: all), on what their last solve left: the used edge
+        with the largest squared residual above chi2_max whose robot pair holds at least min_support other used edges is retired
+        (defaults: the constructor's) -> changed [G] uint8, 1 where an edge was retired: the gsel of the next solve"""
+        torch = self.torch
+        c2 = self.chi2_max if chi2_max is None else float(chi2_max)
+        if c2 is None:
+            raise ValueError("gate() needs chi2_max, here or in the constructor")
+        ms = self.min_support if min_support is None else int(min_support)
+        gs = torch.ones(self.G, dtype=torch.uint8, device=self.dev) if gsel is None else self._gmask(gsel)
+        self._ci ^= 1                                 # the two outputs take turns, so that one gate's changed can be the next one's gsel
+        if gs.data_ptr() == self._changed[self._ci].data_ptr():
+            self._ci ^= 1
+        out = self._changed[self._ci]
+        self._keep_gate = gs
+        self._chk(group_gate.gate(self.Lg, self.h, self._ptr(self.store), self._ptr(gs), c2, ms, self._ptr(out), self._stream()))
+        self.changed = out
+        return out
+
+    def solve_gated(self, gsel=None, max_iters=None, fixed=None, n_keyframes=None):
+        """solve(gsel), then gate_rounds times: changed = gate(the groups just solved); solve(changed).  Everything is enqueued, nothing is
+        read back; a group whose edges are consistent costs one gate and launches that return at once.  -> summary"""
+        self.solve(gsel, max_iters, fixed, n_keyframes)
+        current = gsel
+        for _ in range(self.gate_rounds):
+            current = self.gate(current)
+            self.solve(current, max_iters, fixed, n_keyframes)
+        return self.summary
+
     def push(self, loop_out, back_out=None, mask=None):
         """behind FleetLoopDetector.push and FleetBackEnd.push: partner choice of this round (linked robots included), cross detection for
         the robots whose key frame was stored, link for the still unlinked robots, the edges appended, and a solve of the groups that gained
-        an edge in this call or have a linked member in back_out["due"].  That group set is computed on the device; nothing is read back.
+        an edge in this call or have a linked member in back_out["due"] (solve_gated when chi2_max is set).  That group set is computed
+        on the device; nothing is read back.
         -> the views of detect_cross and link, partner, gsel and summary"""
         torch, a = self.torch, self.al
         key = loop_out["added"]
@@ -199,7 +236,10 @@ class FleetGroupGraph(FleetStore):
             member = ((self._t(back_out["due"], torch.uint8, (self.B,)) != 0) & (a.linked != 0) & (a.group_of >= 0)).to(torch.uint8)
             gsel = torch.maximum(gsel, torch.zeros_like(gsel).scatter_reduce(0, self._group_index, member, "amax"))
         self.gsel = gsel
-        self.solve(gsel)
+        if self.chi2_max is None:
+            self.solve(gsel)
+        else:
+            self.solve_gated(gsel)
         out.update(partner=partner, gsel=gsel, summary=self.summary)
         return out
 
@@ -222,6 +262,12 @@ class FleetGroupGraph(FleetStore):
         i, t = np.zeros((max(n, 1), 5), dtype=np.int32), np.zeros((max(n, 1), 12))
         self._chk(self.L.liw_ggraph_get_edges(self.h, self._ptr(self.store), C.c_int(group), C.c_int(n), _pi(i), _pd(t)))
         return i[:n], t[:n]
+
+    def edge_states(self, group):
+        """dict(state [n] int32 (0 active, 1 rejected), chi2 [n] (of the last gate that saw the edge in a solve), rejected, gated_solves)"""
+        self._sync()
+        out = group_gate.get(self.Lg, self.h, self._ptr(self.store), group)
+        return out if isinstance(out, dict) else self._chk(out)
 
     def last_summary(self, group):
         from . import SummaryC

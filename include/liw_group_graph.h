@@ -20,6 +20,8 @@
  *   header   256 B   int32 [0] edges held, [1] edges_full, [2] members_full, [3] bad_edge, [4] solves, and of the last solve [5] edges
  *                    skipped, [6] nodes, [7] edges used; bytes 32..63 the liw_summary of the last solve
  *   edges    128 B each, max_edges of them: int32 a, q, b, i, size, 3 words of padding, then tf12[12]
+ * liw_group_gate.h, the edge gate on this ctx and store, gives the padding words of a record (a state and a double) and header bytes
+ * 64 .. 71 a meaning; here they are written as zeros, and an edge whose state is not 0 is no part of a solve.
  * Work area of a group (M = max_members, E = max_edges): the LM state (256 B), the node list and constant flags, the node indices and
  * the use flag of every edge, x, candidate, step, Jacobi scale, LM diagonal and gradient (48 M each), the diagonal blocks (288 M), the
  * edge blocks [J | r] (624 E), Z with its two pose transforms (288 E), the packed lower triangle of the 6 M unknowns (8 * 3 M (6 M + 1))
@@ -95,7 +97,8 @@ int liw_ggraph_partner(liw_ggraph_ctx* ctx, const int* group_of, const unsigned 
  *          than max_members of them: members_full is set and the group is not solved.  Fixed members are constant (identity block,
  *          zero gradient); when no linked member is fixed, the lowest-index linked member is constant.
  *   edges  every held edge with a != b whose two robots are nodes, whose q and i are inside the robots' key frames and whose nodes
- *          are not both constant (an edge between constants has no unknown and, as in Ceres, is no part of the problem).  The others
+ *          are not both constant (an edge between constants has no unknown and, as in Ceres, is no part of the problem), and that
+ *          the edge gate of liw_group_gate.h has not rejected (state word 0, as every edge is without the gate).  The others
  *          are skipped and counted in the header.
  *   solve  Levenberg-Marquardt under the rules of liw_lm_rules.hpp with Jacobi scaling and the termination tests of liw_fpg_solve, at
  *          most max_iters iterations (<= 0: 50).  One work-group per group runs the whole loop inside ONE launch: 16 lanes evaluate an

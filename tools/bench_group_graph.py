@@ -3,8 +3,10 @@ cycle with two rings of chords (3 M edges, noisy measurements, the start 2 cm / 
 yardstick for the lock-step alternative, FleetBackEnd.solve (about ten launches per iteration) for G robots whose graphs have the
 same node and edge counts: M key frames, M - 1 sequential edges and 2 M + 1 loops, ground factors off.  Median of --reps calls after
 two warm-ups, wall time around torch.cuda.synchronize(); the time per LM iteration divides by the most iterations any group (robot)
-took.  One JSON line per (G, M), also written to --out.
-  python tools/bench_group_graph.py [--groups 64,1024] [--members 4,16] [--reps 12] [--out profiles/group_graph_bench.json]"""
+took.  The edge gate (include/liw_group_gate.h) on the same, all-consistent edges: liw_ggate_gate alone after a solve (gate_ms; every
+edge is evaluated and its pair's support counted, none is retired), and FleetGroupGraph.solve_gated, which adds to the solve two gates
+and two solve launches that return at once (solve_gated_ms, against solve_ms).  One JSON line per (G, M), also written to --out.
+  python tools/bench_group_graph.py [--groups 64,1024] [--members 4,16] [--reps 12] [--no-backend] [--out profiles/group_graph_bench.json]"""
 import argparse
 import importlib
 import json
@@ -65,7 +67,7 @@ def group_graph_leg(liw, synth, gg, G, M, reps):
     fb = liw.FleetBackEnd(prm, liw.posegraph.office_pg_params(), dict(B=B, max_keyframes=K, max_loops=1))
     al = liw.FleetGroupAligner(fl, np.repeat(np.arange(G), M), list(range(0, B, M)), 9, 0.01)       # the first robot of a group is its anchor
     al.linked.fill_(1)
-    gr = gg.FleetGroupGraph(al, fb, M, 3 * M)
+    gr = gg.FleetGroupGraph(al, fb, M, 3 * M, chi2_max=12.0, min_support=2, gate_rounds=2)
     # one group's data, tiled: truth W, poses P, start T0
     W = [np.eye(4)] + [_tf(rng, 4.0, 2.5) for _ in range(M - 1)]
     P = [[_tf(rng, 3.0, 2.5) for _ in range(K)] for _ in range(M)]
@@ -99,8 +101,16 @@ def group_graph_leg(liw, synth, gg, G, M, reps):
     ms = timed(torch, reps, lambda: al.T_g_w.copy_(start), lambda: gr.solve(fixed=fixed, n_keyframes=nkf))
     sm = gr.summaries()
     fl0 = gr.flags(0)
+    gated_word = gr.group_regions()[:, 68:72]      # gated_solves: cleared, the group is eligible for a gate again
+
+    def ungate():
+        gated_word.zero_()
+    gate_ms = timed(torch, reps, ungate, lambda: gr.gate())
+    both_ms = timed(torch, reps, lambda: al.T_g_w.copy_(start), lambda: gr.solve_gated(fixed=fixed, n_keyframes=nkf))
+    rejected = sum(gr.edge_states(g)["rejected"] for g in range(0, G, max(G // 8, 1)))
     its = max(s["iterations"] for s in sm)
-    out = dict(solve_ms=ms[0], solve_ms_min=ms[1], solve_ms_max=ms[2], iterations=its, ms_per_iteration=ms[0] / max(its, 1), edges=fl0["used"],
+    out = dict(solve_ms=ms[0], solve_ms_min=ms[1], solve_ms_max=ms[2], gate_ms=gate_ms[0], gate_ms_min=gate_ms[1], gate_ms_max=gate_ms[2],
+               solve_gated_ms=both_ms[0], solve_gated_ms_min=both_ms[1], solve_gated_ms_max=both_ms[2], rejected=rejected, iterations=its, ms_per_iteration=ms[0] / max(its, 1), edges=fl0["used"],
                terminations=sorted(set(s["termination"] for s in sm)), lds_triangle=bool(3 * M * (6 * M + 1) <= 8192))
     for o in (gr, fb, fl):
         o.close()
@@ -145,6 +155,7 @@ def main():
     ap.add_argument("--groups", default="64,1024")
     ap.add_argument("--members", default="4,16")
     ap.add_argument("--reps", type=int, default=12)
+    ap.add_argument("--no-backend", action="store_true", help="leave the FleetBackEnd yardstick out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "group_graph_bench.json"))
     a = ap.parse_args()
     liw = importlib.import_module("2dliw-slam_amd")
@@ -155,7 +166,9 @@ def main():
     for G in (int(v) for v in a.groups.split(",")):
         for M in (int(v) for v in a.members.split(",")):
             row = dict(bench="group_graph", device=torch.cuda.get_device_name(0), groups=G, members=M, reps=a.reps,
-                       ggraph=group_graph_leg(liw, synth, gg, G, M, a.reps), fleet_backend=backend_leg(liw, synth, G, M, a.reps))
+                       ggraph=group_graph_leg(liw, synth, gg, G, M, a.reps))
+            if not a.no_backend:
+                row["fleet_backend"] = backend_leg(liw, synth, G, M, a.reps)
             print(json.dumps(row), flush=True)
             lines.append(row)
     with open(a.out, "w") as f:
