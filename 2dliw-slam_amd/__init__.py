@@ -352,10 +352,11 @@ class HostPreint:
 
 
 from .batch import BatchPreint, BatchSolver, shard_laser  # noqa: E402,F401
-from . import fleet, gridmap, laser, laser_batch, loop, loop_batch, loop_cross, map_batch, outputs, posegraph, posegraph_batch, preint_batch  # noqa: E402,F401
+from . import fleet, gridmap, laser, laser_batch, loop, loop_batch, loop_cross, map_batch, map_locate, outputs, posegraph, posegraph_batch, preint_batch  # noqa: E402,F401
 from .fleet import FleetTracker, FleetTrajectory  # noqa: E402,F401
 from .loop_batch import FleetLoopDetector  # noqa: E402,F401
 from .loop_cross import FleetGroupAligner  # noqa: E402,F401
 from .posegraph_batch import FleetBackEnd  # noqa: E402,F401
 from .map_batch import FleetGroupMap, FleetMapper  # noqa: E402,F401
+from .map_locate import FleetLocalizer  # noqa: E402,F401
 from .preint_batch import FleetPreint  # noqa: E402,F401
