@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libliw_window.so")
 
 LIW_MODE_INIT, LIW_MODE_TRACK, LIW_MODE_MARG = 0, 1, 2
 LIW_ENODEV = -19
+LIW_EINVAL = -22
 LASER_PARTIAL = 128
 LASER_PARTIAL_COMPACT = 48   # doubles per laser group record in the large-batch workspace format (include/liw_window.h)
 
@@ -73,7 +74,7 @@ EXPORTS = [
     "liw_linearize", "liw_eval_factors", "liw_marginalize", "liw_get_prior", "liw_set_prior", "liw_batch_ws_layout",
     "liw_batch_set_max_iters", "liw_batch_launch_paths", "liw_batch_step_kernel", "liw_batch_packed_rows", "liw_batch_linearize", "liw_batch_time_kernels", "liw_batch_lm_begin", "liw_batch_lm_linearize", "liw_batch_laser_records", "liw_batch_lm_step",
     "liw_batch_lm_finish", "liw_batch_lm_linearize_async", "liw_batch_lm_join", "liw_batch_exchange_doubles", "liw_batch_exchange_pack",
-    "liw_batch_exchange_unpack", "liw_batch_solve_sharded", "liw_batch_exchange_timing", "liw_batch_p2p_area_doubles", "liw_batch_p2p_setup", "liw_batch_p2p_status", "liw_batch_solve", "liw_batch_marg_linearize", "liw_batch_marg_schur", "liw_batch_export_dense",
+    "liw_batch_exchange_unpack", "liw_batch_solve_sharded", "liw_batch_exchange_timing", "liw_batch_p2p_area_doubles", "liw_batch_p2p_setup", "liw_batch_p2p_status", "liw_batch_solve", "liw_batch_marg_linearize", "liw_batch_marg_schur", "liw_batch_export_dense", "liw_batch_marg_eig_probe",
     "liw_set_timing", "liw_get_timing", "liw_batch_imu_preint", "liw_batch_wheel_preint", "liw_imu_preint_create", "liw_imu_preint_destroy", "liw_imu_preint_reset",
     "liw_imu_preint_add", "liw_imu_preint_update_only_t", "liw_imu_preint_Dt", "liw_imu_preint_result",
     "liw_wheel_preint_create", "liw_wheel_preint_destroy", "liw_wheel_preint_reset", "liw_wheel_preint_add",

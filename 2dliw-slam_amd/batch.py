@@ -604,6 +604,24 @@ class BatchSolver:
                                               C.c_void_p(dg.data_ptr()), s))
         return sH, dH, dg
 
+    def marg_eig_probe(self, variant, dH, dg, ok=None):
+        """liw_batch_marg_eig_probe (test hook): the eigen square root alone on dH [B,15,15] / dg [B,15] (arrays or device tensors; None
+        goes through as a null pointer), by implementation `variant` (0 jacobi15_wave, 1 jacobi15_block, 2 k_marg_schur_eigq); ok [B] uint8
+        or None.  Writes the batch's prior arrays; -> sqrt_H [B, 36] (device)."""
+        torch = self.torch
+
+        def dev(a, dtype):
+            if a is None or torch.is_tensor(a):
+                return a
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to(self.dev)
+
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+        dH, dg, ok = dev(dH, np.float64), dev(dg, np.float64), dev(ok, np.uint8)
+        sH = torch.zeros((self.B, 36), dtype=torch.float64, device=self.dev)
+        self._chk(self.L.liw_batch_marg_eig_probe(self.h, C.byref(self.b), self._wsp(), C.c_int(int(variant)), ptr(dH), ptr(dg), ptr(ok),
+                                                  ptr(sH), self._stream()))
+        return sH
+
     # ---- results
     def states(self):
         return self.t["x"].cpu().numpy().reshape(self.B, self.n, 15)

@@ -779,6 +779,23 @@ int liw_batch_marg_schur(liw_ctx* c, const liw_batch* b, void* ws, double* sqrt_
     HIPCHK(c, hipGetLastError());
     return LIW_OK;
 }
+/* test hook, see include/liw_window.h */
+int liw_batch_marg_eig_probe(liw_ctx* c, const liw_batch* b, void* ws, int variant, const double* Delta_H, const double* Delta_g,
+                             const unsigned char* ok, double* sqrt_H, void* stream) {
+    if (!c) return LIW_EINVAL;
+    if (!Delta_H || !Delta_g) return fail(c, LIW_EINVAL, "liw_batch_marg_eig_probe: Delta_H / Delta_g");
+    if (variant < 0 || variant > 2) return fail(c, LIW_EINVAL, "liw_batch_marg_eig_probe: variant must be 0, 1 or 2");
+    NEEDDEV(c);
+    if (int r = check_batch(c, b, 2)) return r;
+    MargEigProbeArgs p{};
+    p.m.B = b->B; p.m.n = b->n; p.m.x = b->x;
+    p.m.prior_X = b->prior_X; p.m.prior_J = b->prior_J; p.m.prior_R = b->prior_R; p.m.has_prior = b->has_prior;
+    p.m.w = make_view(ws, b->B, b->n, b->history_records); p.m.sqrt_H = sqrt_H;
+    p.dH = Delta_H; p.dg = Delta_g; p.ok = ok;
+    launch_marg_eig_probe(p, variant, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return LIW_OK;
+}
 int liw_batch_export_dense(liw_ctx* c, const liw_batch* b, int mode, int buf, void* ws, double* H, double* g, double* cost, void* stream) {
     NEEDDEV(c);
     if (int r = check_batch(c, b, min_frames(mode))) return r;

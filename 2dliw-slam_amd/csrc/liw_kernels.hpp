@@ -375,6 +375,10 @@ void launch_lm_finish(const StepArgs& a, hipStream_t s);
 void launch_export_dense(const ExportArgs& a, hipStream_t s);
 void launch_laser_expand(int B, int n, bool both, int compact, const double* PL, double* out, hipStream_t s);   // records of either format -> 128-slot records
 void launch_marg_schur(const MargArgs& a, hipStream_t s);
+// test hook (liw_batch_marg_eig_probe): the eigen square root alone.  m as liw_batch_marg_schur fills it (Delta_H / Delta_g outputs unset);
+// dH [B][225] row-major, dg [B][15] in the reference's sign, ok [B] or null (all 1); variant 0 jacobi15_wave, 1 jacobi15_block, 2 k_marg_schur_eigq
+struct MargEigProbeArgs { MargArgs m; const double* dH; const double* dg; const unsigned char* ok; };
+void launch_marg_eig_probe(const MargEigProbeArgs& p, int variant, hipStream_t s);
 
 // batched pre-integration (k_preint.hip)
 struct PreintNoise { double q_na[3], q_nw[3], q_nba[3], q_nbw[3], wheel_cov[3]; };

@@ -306,6 +306,20 @@ int liw_batch_marg_linearize(liw_ctx* ctx, const liw_batch* b, void* ws, void* s
 int liw_batch_marg_schur(liw_ctx* ctx, const liw_batch* b, void* ws, double* sqrt_H, double* Delta_H, double* Delta_g, void* stream);
 /* dense export of the assembled normal equations of buffer `buf` (tests / liw_linearize) */
 int liw_batch_export_dense(liw_ctx* ctx, const liw_batch* b, int mode, int buf, void* ws, double* H, double* g, double* cost, void* stream);
+/* Test hook (tests/test_gpu_marg_eig.py; no reference counterpart): the LAST stage of a marginalisation alone — the 15 x 15 eigen square
+ * root of solver.cpp:390-402 — on a caller's Delta_H / Delta_g (device arrays), one launch on `stream`, nothing synchronises.  The new
+ * prior goes to the batch's prior_X / prior_J / prior_R / has_prior as liw_batch_marg_schur writes it (prior_X = the last frame's state
+ * of b->x; sqrt_H [B][36] optional); a window with ok[b] == 0 is treated as one whose chain failed: every byte of its prior stays.
+ * variant selects the implementation: 2 = k_marg_schur_eigq, the production kernel of batches above 256 windows, unchanged, on a
+ * hand-over record written for it into the windows' factorisation scratch in `ws`; 1 = jacobi15_block + marg_tail as k_marg_schur4
+ * runs them (four waves per window: batches up to 256 windows, the single-window path); 0 = jacobi15_wave + marg_tail as k_marg_schur
+ * runs them (LIW_MARG_EIG=1).  LIW_EINVAL, with nothing written, for a null Delta_H / Delta_g or another variant (reported before
+ * LIW_ENODEV); the batch is checked as for liw_batch_marg_schur. */
+int liw_batch_marg_eig_probe(liw_ctx* ctx, const liw_batch* b, void* ws, int variant,
+                             const double* Delta_H /*[B][225] row-major, need not be symmetric*/,
+                             const double* Delta_g /*[B][15], reference sign*/,
+                             const unsigned char* ok /*[B], NULL = all 1; 0 = as a failed chain*/,
+                             double* sqrt_H /*[B][36] or NULL*/, void* stream);
 /* timing hook for bench.py: average device time (ms) of the last `liw_batch_solve`'s linearise launches,
  * measured with hipEvents on `stream` (0 if timing was not enabled) */
 int liw_set_timing(liw_ctx* ctx, int enable);
