@@ -191,7 +191,8 @@ __global__ void k_pg_scale_damp(int n, int np, int ld, const double* H, const do
 
 // ---------------------------------------------------------------------------------------------- blocked Cholesky, NB = 64
 // diagonal block: lane j owns column j (a[r] = A[r][j]); step k broadcasts the pivot and column k with v_readlane;
-// afterwards lane j holds row j of L in a[0..j].  status[0] != 0 when a pivot is not positive.
+// afterwards lane j holds row j of L in a[0..j].  status[0] != 0 when a pivot is not positive and finite (+inf passes `> 0`, and
+// 1 / sqrt(inf) = 0 then turns the column into inf * 0 = NaN behind a clean status).
 __global__ __launch_bounds__(64, 1) void k_potrf64(double* A, int ld, int k0, int* status) {
     const int lane = threadIdx.x & 63;
     double* B = A + (size_t)k0 * ld + k0;
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(64, 1) void k_potrf64(double* A, int ld, int k0, in
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
         const double piv = rdl64(a[k], k);
-        if (!(piv > 0.0)) ok = false;
+        if (!(piv > 0.0) || !isfinite(piv)) ok = false;
         const double inv = 1.0 / sqrt(piv);
         const double wk = a[k] * inv;          // lane j >= k: A[k][j] / sqrt(piv) = L[j][k]
         a[k] = wk;
@@ -530,6 +531,9 @@ using namespace liw;
 struct PgCall {
     liw_ctx* c; const liw_pg_params* pg; int N; double* poses; int n_seq; const int* seq_idx; const double* seq_tf12; int n_loop; const int* loop_idx;
     const double* loop_tf12; int max_iters; liw_summary* summary; double* H_out; double* g_out; double* cost_out;
+    // step probe (liw_posegraph_step): one linear solve at `poses` with the caller's radius on path step_path, no LM loop
+    bool step = false; double step_radius = 0.0; int step_path = 0; double* y_out = nullptr; double* scale_out = nullptr; double* dgn_out = nullptr;
+    int* solved_out = nullptr;
 };
 static int pg_run(const PgCall& q);
 
@@ -540,6 +544,13 @@ int liw_posegraph_solve(liw_ctx* c, const liw_pg_params* pg, int N, double* pose
 int liw_posegraph_linearize(liw_ctx* c, const liw_pg_params* pg, int N, const double* poses, int n_seq, const int* seq_idx, const double* seq_tf12, int n_loop,
                             const int* loop_idx, const double* loop_tf12, double* H, double* g, double* cost) {
     return pg_run(PgCall{c, pg, N, const_cast<double*>(poses), n_seq, seq_idx, seq_tf12, n_loop, loop_idx, loop_tf12, 0, nullptr, H, g, cost ? cost : (double*)nullptr});
+}
+int liw_posegraph_step(liw_ctx* c, const liw_pg_params* pg, int N, const double* poses, int n_seq, const int* seq_idx, const double* seq_tf12, int n_loop,
+                       const int* loop_idx, const double* loop_tf12, double radius, int path, double* y, double* scale, double* dgn, int* solved) {
+    if (!y || !solved || (path != 0 && path != 1) || !(radius > 0.0)) return liw_ctx_fail(c, LIW_EINVAL, "liw_posegraph_step: bad argument");
+    PgCall q{c, pg, N, const_cast<double*>(poses), n_seq, seq_idx, seq_tf12, n_loop, loop_idx, loop_tf12, 0, nullptr, nullptr, nullptr, nullptr};
+    q.step = true; q.step_radius = radius; q.step_path = path; q.y_out = y; q.scale_out = scale; q.dgn_out = dgn; q.solved_out = solved;
+    return pg_run(q);
 }
 
 static int pg_run(const PgCall& q) {
@@ -572,6 +583,10 @@ static int pg_run(const PgCall& q) {
     // sparse path: the sequential edges must be the chain k -> k+1 (what keyframe_manager builds, :444-453)
     bool sparse = !linearize_only && n_seq == N - 1 && N >= 4 && !std::getenv("LIW_PG_DENSE");
     for (int e = 0; e < n_seq && sparse; ++e) if (eidx[2 * e] != e || eidx[2 * e + 1] != e + 1) sparse = false;
+    if (q.step) {
+        if (q.step_path == 1 && !sparse) return liw_ctx_fail(c, LIW_EINVAL, "liw_posegraph_step: this graph does not take the sparse path");
+        if (q.step_path == 0) sparse = false;
+    }
     std::vector<int> sep, sepidx(N, -1), segs;
     if (sparse) {
         std::vector<char> is_sep(N, 0);
@@ -666,38 +681,14 @@ static int pg_run(const PgCall& q) {
         return m;
     };
 
-    // ---- Ceres trust-region Levenberg-Marquardt (defaults; SURVEY Appendix B): constants and rules of liw_lm_rules.hpp
-    const int K = max_iters > 0 ? max_iters : 50;
-    double radius = kInitRadius, decrease_factor = 2.0, x_cost = 0.0;
-    int reuse_diagonal = 0;
-    liw_summary sum{};
-    if (int r = evaluate(x, dx, true, &x_cost)) return r;
-    if (linearize_only) {   // dense tangent-space normal equations (lower triangle mirrored), constant key frame = identity block
-        if (q.cost_out) *q.cost_out = x_cost;
-        if (q.g_out) std::memcpy(q.g_out, g.data(), sizeof(double) * n);
-        if (q.H_out) {
-            std::vector<double> Hp((size_t)np * np);
-            if (hipMemcpy(Hp.data(), dH.p, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToHost) != hipSuccess) return liw_ctx_fail(c, LIW_EHIP, "hipMemcpy");
-            for (int i = 0; i < n; ++i) for (int j = 0; j <= i; ++j) q.H_out[(size_t)i * n + j] = q.H_out[(size_t)j * n + i] = Hp[(size_t)i * np + j];
-        }
-        return LIW_OK;
-    }
-    sum.initial_cost = x_cost;
-    for (int i = 0; i < n; ++i) scale[i] = is_const(i) ? 1.0 : 1.0 / (1.0 + std::sqrt(Hdiag[i]));
-    double x_norm = 0.0;
-    for (int i = 0; i < n; ++i) if (!is_const(i)) x_norm += x[i] * x[i];
-    x_norm = std::sqrt(x_norm);
-    double gmax = gradient_max_norm();
-    int iteration = 0, invalid_steps = 0, termination = 0, successful = 0;
-    bool last_successful = true;
-    while (!termination) {
-        if (iteration >= K) { termination = 4; break; }   // (K >= 1: never at iteration zero)
-        if ((termination = lm_gradient_term(iteration == 0, last_successful, gmax, radius > kMinRadius))) break;
-        ++iteration;
+    // the rhs S g and the LM diagonal of an iteration, and its linear solve (S H S + diag(dgn) / radius) y = S g on the path of this call:
+    // uploads, launches, status read-back.  The LM loop and the step probe both go through these two.
+    auto scaled_gradient_and_diagonal = [&](bool new_diagonal) {
         for (int i = 0; i < n; ++i) gs[i] = is_const(i) ? 0.0 : g[i] * scale[i];
-        if (!reuse_diagonal)
+        if (new_diagonal)
             for (int i = 0; i < n; ++i) dgn[i] = is_const(i) ? 0.0 : std::min(std::max(Hdiag[i] * scale[i] * scale[i], kMinDiag), kMaxDiag);
-        reuse_diagonal = 1;
+    };
+    auto linear_solve = [&](double radius, bool& solved) -> int {
         up(dscale, scale.data(), sizeof(double) * n); up(ddgn, dgn.data(), sizeof(double) * n);
         std::fill(y.begin(), y.end(), 0.0);
         std::memcpy(y.data(), gs.data(), sizeof(double) * n);
@@ -726,8 +717,53 @@ static int pg_run(const PgCall& q) {
         (void)hipMemcpyAsync(y.data(), drhs.p, sizeof(double) * np, hipMemcpyDeviceToHost, s);
         (void)hipMemcpyAsync(&st, dst.p, sizeof(int), hipMemcpyDeviceToHost, s);
         if (hipStreamSynchronize(s) != hipSuccess) return liw_ctx_fail(c, LIW_EHIP, "pose graph solve");
-        bool solved = st == 0 && st2 == 0;
+        solved = st == 0 && st2 == 0;
         for (int i = 0; i < n && solved; ++i) if (!std::isfinite(y[i])) solved = false;
+        return LIW_OK;
+    };
+
+    // ---- Ceres trust-region Levenberg-Marquardt (defaults; SURVEY Appendix B): constants and rules of liw_lm_rules.hpp
+    const int K = max_iters > 0 ? max_iters : 50;
+    double radius = kInitRadius, decrease_factor = 2.0, x_cost = 0.0;
+    int reuse_diagonal = 0;
+    liw_summary sum{};
+    if (int r = evaluate(x, dx, true, &x_cost)) return r;
+    if (linearize_only) {   // dense tangent-space normal equations (lower triangle mirrored), constant key frame = identity block
+        if (q.cost_out) *q.cost_out = x_cost;
+        if (q.g_out) std::memcpy(q.g_out, g.data(), sizeof(double) * n);
+        if (q.H_out) {
+            std::vector<double> Hp((size_t)np * np);
+            if (hipMemcpy(Hp.data(), dH.p, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToHost) != hipSuccess) return liw_ctx_fail(c, LIW_EHIP, "hipMemcpy");
+            for (int i = 0; i < n; ++i) for (int j = 0; j <= i; ++j) q.H_out[(size_t)i * n + j] = q.H_out[(size_t)j * n + i] = Hp[(size_t)i * np + j];
+        }
+        return LIW_OK;
+    }
+    sum.initial_cost = x_cost;
+    for (int i = 0; i < n; ++i) scale[i] = is_const(i) ? 1.0 : 1.0 / (1.0 + std::sqrt(Hdiag[i]));
+    if (q.step) {   // the probe: the first iteration's scaling and diagonal, one solve at the caller's radius
+        scaled_gradient_and_diagonal(true);
+        bool solved = false;
+        if (int r = linear_solve(q.step_radius, solved)) return r;
+        for (int i = 0; i < n; ++i) q.y_out[i] = is_const(i) ? 0.0 : y[i];
+        if (q.scale_out) std::memcpy(q.scale_out, scale.data(), sizeof(double) * n);
+        if (q.dgn_out) std::memcpy(q.dgn_out, dgn.data(), sizeof(double) * n);
+        *q.solved_out = solved ? 1 : 0;
+        return LIW_OK;
+    }
+    double x_norm = 0.0;
+    for (int i = 0; i < n; ++i) if (!is_const(i)) x_norm += x[i] * x[i];
+    x_norm = std::sqrt(x_norm);
+    double gmax = gradient_max_norm();
+    int iteration = 0, invalid_steps = 0, termination = 0, successful = 0;
+    bool last_successful = true;
+    while (!termination) {
+        if (iteration >= K) { termination = 4; break; }   // (K >= 1: never at iteration zero)
+        if ((termination = lm_gradient_term(iteration == 0, last_successful, gmax, radius > kMinRadius))) break;
+        ++iteration;
+        scaled_gradient_and_diagonal(!reuse_diagonal);
+        reuse_diagonal = 1;
+        bool solved = false;
+        if (int r = linear_solve(radius, solved)) return r;
         // model cost change with (A + D^2) y = g_s, step = -y:  (y'g_s + y'D^2 y) / 2
         double model_cost_change = 0.0;
         if (solved) {

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-PG_EXPORTS = ["liw_posegraph_solve", "liw_posegraph_linearize", "liw_dense_spd_solve"]
+PG_EXPORTS = ["liw_posegraph_solve", "liw_posegraph_linearize", "liw_posegraph_step", "liw_dense_spd_solve"]
 
 
 class PgParamsC(C.Structure):
@@ -74,6 +74,21 @@ class PoseGraph:
         self._chk(self.L.liw_posegraph_linearize(self.h, C.byref(ps), C.c_int(x.shape[0]), _pd(x), C.c_int(si.shape[0]), _pi(si), _pd(st), C.c_int(nl),
                                                  _pi(li), _pd(lt), _pd(H), _pd(g), C.byref(cost)))
         return H, g, cost.value
+
+    def step(self, pg, poses, seq_idx, seq_tf12, loop_idx=None, loop_tf12=None, radius=1e4, path=0):
+        """One linear solve of solve() (liw_posegraph_step): (y [6N], scale [6N], dgn [6N], solved) of
+        (S H S + diag(dgn) / radius) y = S g at `poses`; path 0 dense, 1 sparse (LiwError where solve() would not take it)."""
+        x = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
+        si, st = np.ascontiguousarray(seq_idx, dtype=np.int32).reshape(-1, 2), np.ascontiguousarray(seq_tf12, dtype=np.float64).reshape(-1, 12)
+        nl = 0 if loop_idx is None else len(loop_idx)
+        li = np.ascontiguousarray(loop_idx if nl else np.zeros((1, 2)), dtype=np.int32).reshape(-1, 2)
+        lt = np.ascontiguousarray(loop_tf12 if nl else np.zeros((1, 12)), dtype=np.float64).reshape(-1, 12)
+        n = 6 * x.shape[0]
+        y, scale, dgn, solved = np.zeros(n), np.zeros(n), np.zeros(n), C.c_int(0)
+        ps = pg_struct(pg)
+        self._chk(self.L.liw_posegraph_step(self.h, C.byref(ps), C.c_int(x.shape[0]), _pd(x), C.c_int(si.shape[0]), _pi(si), _pd(st), C.c_int(nl),
+                                            _pi(li), _pd(lt), C.c_double(radius), C.c_int(path), _pd(y), _pd(scale), _pd(dgn), C.byref(solved)))
+        return y, scale, dgn, solved.value
 
     def dense_spd_solve(self, A, b):
         A, b = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)

@@ -33,8 +33,18 @@ int liw_posegraph_solve(liw_ctx* ctx, const liw_pg_params* pg, int N, double* po
  * (any output may be NULL); the constant key frame has an identity block and a zero gradient */
 int liw_posegraph_linearize(liw_ctx* ctx, const liw_pg_params* pg, int N, const double* poses, int n_seq, const int* seq_idx, const double* seq_tf12,
                             int n_loop, const int* loop_idx, const double* loop_tf12, double* H, double* g, double* cost);
+/* one linear solve of the solver above, laid bare (tests): linearises at `poses`, forms the Jacobi scaling `scale` and the LM diagonal `dgn`
+ * as the first iteration does, and solves (S H S + diag(dgn) / radius) y = S g once with the caller's radius, through the same uploads,
+ * launches and status read-back as every iteration of liw_posegraph_solve.  path 0: the dense factorisation of the 6N x 6N matrix;
+ * path 1: chain segments eliminated, dense factorisation of the separators (LIW_EINVAL where liw_posegraph_solve would not take it).
+ * y [6N] (zeros for the constant key frame), scale / dgn [6N] (either may be NULL), *solved = 0 when a pivot was not positive and finite
+ * or y is not finite — the step the LM loop would call invalid; the call still returns LIW_OK then. */
+int liw_posegraph_step(liw_ctx* ctx, const liw_pg_params* pg, int N, const double* poses, int n_seq, const int* seq_idx, const double* seq_tf12,
+                       int n_loop, const int* loop_idx, const double* loop_tf12, double radius, int path,
+                       double* y, double* scale, double* dgn, int* solved);
 /* the dense SPD solver underneath (blocked Cholesky + triangular solves on the device), for tests and other callers:
- * A [n][n] row-major host (only the lower triangle is read), b [n] -> x [n].  Returns LIW_ESTATE if A is not positive definite. */
+ * A [n][n] row-major host (only the lower triangle is read), b [n] -> x [n].  Returns LIW_ESTATE if A is not positive definite: a pivot that is
+ * not positive or not finite (zero, negative, NaN, +inf), so LIW_OK never comes with a NaN that the matrix put into x. */
 int liw_dense_spd_solve(liw_ctx* ctx, int n, const double* A, const double* b, double* x);
 
 #ifdef __cplusplus
