@@ -31,12 +31,8 @@ using namespace liw;
 
 using IsoD = Iso<double>;
 
-enum { PH_IDLE = 0, PH_SOLVE = 1, PH_CAND = 2, PH_ASM = 3, PH_INIT = 4 };
 // LM state of a group (head of its work area)
-struct Lm {
-    double radius, dec, x_cost, x_norm, gmax, mcc, init_cost, step_norm;
-    int iter, invalid, succ, last_ok, term, reuse, done, phase, N, ne, used, anyfixed;
-};
+struct Lm : PgLmCore { int N, ne, used, anyfixed; };
 static_assert(sizeof(Lm) <= 256, "the LM state has 256 bytes");
 
 struct Wk {   // a group's work area
@@ -53,8 +49,8 @@ __device__ __forceinline__ Wk work_of(char* store, const Lay& L, int g) {
     w.Z = (double*)(W + L.w_Z); w.Hr = (double*)(W + L.w_Hr); w.rhs = (double*)(W + L.w_rhs);
     return w;
 }
-__device__ __forceinline__ bool robot_on(const unsigned char* a, int b) { return !a || a[b] != 0; }
 
+// plain-double transforms: the products below are liw_lie_mul's, so these do not go through Iso<CR> as liw::tf_of_pose / pose_of_tf do
 __device__ __forceinline__ IsoD load_iso(const double* T) { return cast_iso<double>(T, T + 9); }
 __device__ __forceinline__ void store_iso(const IsoD& A, double* T) {
     for (int k = 0; k < 9; ++k) T[k] = A.R.m[k];
@@ -161,30 +157,11 @@ __device__ __forceinline__ void linearize(const Wk& w, const Noise& noise, int n
         const double* xi = x + (size_t)i * 6;
         const double* xj = x + (size_t)j * 6;
         double* Y = w.Ye + (size_t)(on ? e : 0) * 78;
-        if (on && d < 13) {
-            LJ pi[3], qi[3], pj[3], qj[3], res[6];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                pi[k] = LJ(xi[k], d == k ? 1.0 : 0.0);
-                qi[k] = LJ(xi[3 + k], d == 3 + k ? 1.0 : 0.0);
-                pj[k] = LJ(xj[k], d == 6 + k ? 1.0 : 0.0);
-                qj[k] = LJ(xj[3 + k], d == 9 + k ? 1.0 : 0.0);
-            }
-            edge_res<LJ>(w.Z + (size_t)e * 36, 1.0, noise.J, pi, qi, pj, qj, res);
-#pragma unroll
-            for (int r = 0; r < 6; ++r) Y[r * 13 + d] = d < 12 ? res[r].d : res[r].v;
-        }
+        if (on) pg_edge_column(w.Z + (size_t)e * 36, 1.0, noise.J, xi, xj, d, true, Y);
         __syncthreads();
         if (on && d < 12) {   // local parameterisation: J_theta <- J_theta * dPlus/ddelta  (lane = (row r, pose side))
             const int r = d % 6, side = d / 6;
-            double Pq[9];
-            if (plus_jac((side ? xj : xi) + 3, Pq)) {
-                double* row = &Y[r * 13 + 6 * side + 3];
-                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
-                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
-                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
-                row[0] = t0; row[1] = t1; row[2] = t2;
-            }
+            pg_row_times_plus_jac(&Y[r * 13 + 6 * side + 3], (side ? xj : xi) + 3);
         }
         __syncthreads();
     }
@@ -202,15 +179,7 @@ __device__ __forceinline__ void assemble(const Wk& w, int N, int ne, int wave, i
                 int side;
                 if (w.enode[3 * e] == k) side = 0; else if (w.enode[3 * e + 1] == k) side = 1; else continue;
                 const double* Y = w.Ye + (size_t)e * 78;
-                double sm = 0.0;
-                if (lane < 36) {
-#pragma unroll
-                    for (int t = 0; t < 6; ++t) sm += Y[t * 13 + 6 * side + r] * Y[t * 13 + 6 * side + c];
-                } else if (lane < 42) {
-#pragma unroll
-                    for (int t = 0; t < 6; ++t) sm += Y[t * 13 + 6 * side + (lane - 36)] * Y[t * 13 + 12];
-                }
-                acc += sm;
+                acc += pg_node_edge(Y, side, lane);
             }
         if (is_const && lane < 36) acc = r == c ? 1.0 : 0.0;
         if (lane < 36) w.Dd[(size_t)k * 36 + lane] = acc;
@@ -249,44 +218,11 @@ __device__ __forceinline__ void finish(int* hdr, const Wk& w, int N, int iter, i
 // wave 0: cost / norms of a new point, termination 1 / 4 / 5, the LM diagonal (k_fpg_head)
 __device__ __forceinline__ void head(int* hdr, const Wk& w, int max_iters, double* T_g_w, liw_summary* summary_g, int lane) {
     Lm s = *w.lm;
-    const int N = s.N, n = 6 * N;
-    if (s.phase == PH_INIT) {
-        s.x_cost = cost_of(w, s.ne, lane);
-        s.init_cost = s.x_cost;
-        for (int i = lane; i < n; i += 64) w.scale[i] = w.cst[i / 6] ? 1.0 : 1.0 / (1.0 + sqrt(w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7]));
-    }
-    if (s.phase == PH_INIT || s.phase == PH_ASM) {
-        double sq = 0.0, m = 0.0;
-        for (int i = lane; i < n; i += 64)
-            if (!w.cst[i / 6]) sq += w.x[i] * w.x[i];
-        s.x_norm = sqrt(wave_sum(sq));
-        for (int f = lane; f < N; f += 64) {   // max |x - Plus(x, -g)|
-            if (w.cst[f]) continue;
-            double ng[6], xp[6];
-            for (int k = 0; k < 6; ++k) ng[k] = -w.gd[f * 6 + k];
-            plus6(w.x + (size_t)f * 6, ng, xp);
-            for (int k = 0; k < 6; ++k) m = max_skip_nan(m, fabs(w.x[f * 6 + k] - xp[k]));
-        }
-        s.gmax = wave_max(m);
-    }
-    int term = 0;
-    if (lm_cap_reached(s.iter, max_iters, s.phase == PH_INIT)) term = 4;
-    else term = lm_gradient_term(s.iter == 0, s.last_ok != 0, s.gmax, s.radius > kMinRadius);
+    const int term = pg_lm_head(s, PgConstFlags{w.cst}, [&] { return cost_of(w, s.ne, lane); }, s.N, max_iters, w.x, w.gd, w.Dd, w.scale, w.dgn, lane);
     if (term) {
         finish(hdr, w, s.N, s.iter, s.succ, s.init_cost, s.x_cost, term, T_g_w, summary_g, lane);
         return;
     }
-    ++s.iter;
-    if (!s.reuse)
-        for (int i = lane; i < n; i += 64) {
-            const double sc = w.scale[i];
-            double v = w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7] * sc * sc;   // clamped as std::min(std::max(v, lo), hi) does: a NaN stays
-            v = (v < kMinDiag) ? kMinDiag : v;
-            v = (kMaxDiag < v) ? kMaxDiag : v;
-            w.dgn[i] = w.cst[i / 6] ? 0.0 : v;
-        }
-    s.reuse = 1;
-    s.phase = PH_SOLVE;
     if (lane == 0) *w.lm = s;
 }
 
@@ -336,75 +272,21 @@ __device__ __forceinline__ bool reduced(const Wk& w, double* A, int N, int ne, i
 // wave 0: step validity, model cost change, Plus into the candidate, step norm; termination 6 (k_fpg_decide1)
 __device__ __forceinline__ void decide1(int* hdr, const Wk& w, bool chol_ok, double* T_g_w, liw_summary* summary_g, int lane) {
     Lm s = *w.lm;
-    const int N = s.N, n = 6 * N;
-    bool fin = true;
-    for (int i = lane; i < n; i += 64) fin = fin && isfinite(w.y[i]);
-    const bool solved = chol_ok && __ballot(!fin) == 0ull;
-    // model cost change with (A + D^2) y = g_s, step = -y:  (y'g_s + y'D^2 y) / 2
-    double mcc = 0.0;
-    if (solved) {
-        double ytg = 0.0, dsum = 0.0;
-        for (int i = lane; i < n; i += 64) {
-            if (w.cst[i / 6]) continue;
-            const double yi = w.y[i];
-            ytg += yi * (w.gd[i] * w.scale[i]);
-            dsum += w.dgn[i] / s.radius * yi * yi;
-        }
-        mcc = 0.5 * (wave_sum(ytg) + wave_sum(dsum));
-    }
-    if (!lm_step_valid(solved, mcc)) {
-        if (lm_gives_up(s.invalid++)) {
-            finish(hdr, w, s.N, s.iter - 1, s.succ, s.init_cost, s.x_cost, 6, T_g_w, summary_g, lane);
-            return;
-        }
-        lm_step_rejected(s.radius, s.dec, s.reuse);
-        s.last_ok = 0;
-        s.phase = PH_IDLE;
-        if (lane == 0) *w.lm = s;
+    const int term = pg_lm_decide1(s, PgConstFlags{w.cst}, chol_ok, s.N, w.x, w.cand, w.y, w.scale, w.dgn, w.gd, lane);
+    if (term > 0) {
+        finish(hdr, w, s.N, s.iter, s.succ, s.init_cost, s.x_cost, term, T_g_w, summary_g, lane);
         return;
     }
-    s.invalid = 0;
-    s.mcc = mcc;
-    double sq = 0.0;
-    for (int f = lane; f < N; f += 64) {
-        if (w.cst[f]) continue;
-        double dl[6], xc[6];
-        for (int k = 0; k < 6; ++k) dl[k] = -w.y[f * 6 + k] * w.scale[f * 6 + k];
-        plus6(w.x + (size_t)f * 6, dl, xc);
-        for (int k = 0; k < 6; ++k) {
-            w.cand[f * 6 + k] = xc[k];
-            const double df = w.x[f * 6 + k] - xc[k];
-            sq += df * df;
-        }
-    }
-    s.step_norm = sqrt(wave_sum(sq));
-    s.phase = PH_CAND;
     if (lane == 0) *w.lm = s;
 }
 
 // wave 0: candidate cost, termination 2 / 3, rho, accept / reject, radius (k_fpg_decide2)
 __device__ __forceinline__ void decide2(int* hdr, const Wk& w, double* T_g_w, liw_summary* summary_g, int lane) {
     Lm s = *w.lm;
-    const int n = 6 * s.N;
-    double cc = cost_of(w, s.ne, lane);
-    if (!isfinite(cc)) cc = kFailedEvalCost;
-    const int term = lm_candidate_term(s.step_norm, s.x_norm, s.x_cost, cc);
+    const int term = pg_lm_decide2(s, cost_of(w, s.ne, lane), s.N, w.x, w.cand, lane);
     if (term) {
         finish(hdr, w, s.N, s.iter, s.succ, s.init_cost, s.x_cost, term, T_g_w, summary_g, lane);
         return;
-    }
-    const double rho = (s.x_cost - cc) / s.mcc;
-    if (lm_accepts(rho)) {
-        for (int i = lane; i < n; i += 64) w.x[i] = w.cand[i];
-        s.x_cost = cc;
-        lm_step_accepted(rho, s.radius, s.dec, s.reuse);
-        ++s.succ;
-        s.last_ok = 1;
-        s.phase = PH_ASM;
-    } else {
-        lm_step_rejected(s.radius, s.dec, s.reuse);
-        s.last_ok = 0;
-        s.phase = PH_IDLE;
     }
     if (lane == 0) *w.lm = s;
 }
@@ -488,9 +370,8 @@ __global__ __launch_bounds__(256) void k_ggraph_solve(char* store, Lay L, Noise 
     }
     if (tid == 0) {
         Lm s;
-        s.radius = kInitRadius; s.dec = 2.0; s.x_cost = 0.0; s.x_norm = 0.0; s.gmax = 0.0; s.mcc = 0.0; s.init_cost = 0.0; s.step_norm = 0.0;
-        s.iter = 0; s.invalid = 0; s.succ = 0; s.last_ok = 1; s.term = 0; s.reuse = 0; s.done = 0; s.phase = PH_INIT; s.N = N; s.ne = ne; s.used = used;
-        s.anyfixed = w.lm->anyfixed;
+        pg_lm_start(s, 0);
+        s.N = N; s.ne = ne; s.used = used; s.anyfixed = w.lm->anyfixed;
         *w.lm = s;
         hdr[H_SKIPPED] = ne - used; hdr[H_NODES] = N; hdr[H_USED] = used;
     }
@@ -587,8 +468,6 @@ __global__ __launch_bounds__(256) void k_ggate(char* store, Lay L, Noise noise, 
 }
 
 // ------------------------------------------------------------------------------------------------------------- launches
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-
 int launch_reset(char* store, const Lay& L, const unsigned char* gmask, hipStream_t s) {
     hipLaunchKernelGGL(k_ggraph_reset, dim3(L.G), dim3(256), 0, s, store, L, gmask);
     return launched();

@@ -30,12 +30,8 @@ namespace liw_gjoint_dev {
 
 using namespace liw;
 
-enum { PH_IDLE = 0, PH_SOLVE = 1, PH_CAND = 2, PH_ASM = 3, PH_INIT = 4 };
 // LM state of a group (head of its work area)
-struct Lm {
-    double radius, dec, x_cost, x_norm, gmax, mcc, init_cost, step_norm;
-    int iter, invalid, succ, last_ok, term, reuse, done, phase, ns, N, nl, status, nm, cn, ran;
-};
+struct Lm : PgLmCore { int ns, N, nl, status, nm, cn, ran; };
 static_assert(sizeof(Lm) <= 256, "the LM state has 256 bytes");
 
 struct Wk {   // a group's work area
@@ -56,16 +52,8 @@ __device__ __forceinline__ Wk work_of(char* store, const Lay& L, int g) {
 }
 __device__ __forceinline__ int* header_of(char* store, const Lay& L, int g) { return (int*)(store + L.hdr_off + (size_t)g * kHeaderBytes); }
 __device__ __forceinline__ const char* robot_of(const In& in, const Lay& L, int r) { return in.fpg + (size_t)r * L.f_robot_bytes; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int nkf_of(const In& in, const Lay& L, int r) { return clampi(((const int*)robot_of(in, L, r))[0], 0, L.K); }
 __device__ __forceinline__ int nloop_of(const In& in, const Lay& L, int r) { return clampi(((const int*)robot_of(in, L, r))[1], 0, L.RL); }
-
-__device__ __forceinline__ Iso<CR> load_tf(const double* tf) { return cast_iso<CR>(tf, tf + 9); }
-__device__ __forceinline__ Iso<CR> tf_of_pose(const double* ps) { return make_tf(V3<CR>(ps[0], ps[1], ps[2]), V3<CR>(ps[3], ps[4], ps[5])); }
-__device__ __forceinline__ void pose_of_tf(const Iso<CR>& T, double* ps) {   // log_SE3: p = t, q = log_SO3(R)
-    const V3<CR> q = log_SO3(T.R);
-    ps[0] = T.t.x.v; ps[1] = T.t.y.v; ps[2] = T.t.z.v; ps[3] = q.x.v; ps[4] = q.y.v; ps[5] = q.z.v;
-}
 
 // ------------------------------------------------------------------------------------------------------------- setup
 __global__ __launch_bounds__(64) void k_gj_setup(char* store, Lay L, In in, liw_summary* summary) {
@@ -188,9 +176,8 @@ __global__ __launch_bounds__(64) void k_gj_setup(char* store, Lay L, In in, liw_
         hdr[H_SEQ] = counted || lfull ? N - nm : 0; hdr[H_OWN] = counted || lfull ? nlo : 0; hdr[H_USED] = counted || lfull ? cused : 0;
         hdr[H_SKIPPED] = counted || lfull ? ne - cused : 0; hdr[H_SEPS] = counted ? ns : 0; hdr[H_SOLVED] = solve; hdr[H_CONST] = counted ? w.moff[cmem] : 0;
         Lm s;
-        s.radius = kInitRadius; s.dec = 2.0; s.x_cost = 0.0; s.x_norm = 0.0; s.gmax = 0.0; s.mcc = 0.0; s.init_cost = 0.0; s.step_norm = 0.0;
-        s.iter = 0; s.invalid = 0; s.succ = 0; s.last_ok = 1; s.term = 0; s.reuse = 0; s.done = solve ? 0 : 1; s.phase = PH_INIT; s.ns = ns; s.N = N; s.nl = nl;
-        s.status = 0; s.nm = nm; s.cn = counted ? w.moff[cmem] : 0; s.ran = solve;
+        pg_lm_start(s, solve ? 0 : 1);
+        s.ns = ns; s.N = N; s.nl = nl; s.status = 0; s.nm = nm; s.cn = counted ? w.moff[cmem] : 0; s.ran = solve;
         *w.lm = s;
         if (!solve) {
             liw_summary sm;
@@ -257,30 +244,11 @@ __global__ __launch_bounds__(64) void k_gj_linearize(char* store, Lay L, In in, 
         const double* x = which ? w.cand : w.x;
         const double* xi = x + (size_t)i * 6;
         const double* xj = x + (size_t)j * 6;
-        if (on && d < 13) {
-            LJ pi[3], qi[3], pj[3], qj[3], res[6];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                pi[k] = LJ(xi[k], d == k ? 1.0 : 0.0);
-                qi[k] = LJ(xi[3 + k], d == 3 + k ? 1.0 : 0.0);
-                pj[k] = LJ(xj[k], d == 6 + k ? 1.0 : 0.0);
-                qj[k] = LJ(xj[3 + k], d == 9 + k ? 1.0 : 0.0);
-            }
-            edge_res<LJ>(tf, weight, noise.J, pi, qi, pj, qj, res);
-#pragma unroll
-            for (int r = 0; r < 6; ++r) Y[grp][r * 13 + d] = d < 12 ? res[r].d : res[r].v;
-        }
+        if (on) pg_edge_column(tf, weight, noise.J, xi, xj, d, true, Y[grp]);
         __syncthreads();
         if (on && d < 12) {   // local parameterisation: J_theta <- J_theta * dPlus/ddelta  (lane = (row r, pose side))
             const int r = d % 6, side = d / 6;
-            double Pq[9];
-            if (plus_jac((side ? xj : xi) + 3, Pq)) {
-                double* row = &Y[grp][r * 13 + 6 * side + 3];
-                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
-                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
-                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
-                row[0] = t0; row[1] = t1; row[2] = t2;
-            }
+            pg_row_times_plus_jac(&Y[grp][r * 13 + 6 * side + 3], (side ? xj : xi) + 3);
         }
         __syncthreads();
         if (on && d < 13)
@@ -296,25 +264,10 @@ __global__ __launch_bounds__(64) void k_gj_linearize(char* store, Lay L, In in, 
         const bool on = slot < slots && !w.lm->done && w.lm->phase == want && f < w.lm->N;
         const double* x = which ? w.cand : w.x;
         double* Yl = &Y[0][0] + sub * 16;
-        if (on && dir < 7) {
-            const double* s_ = x + (size_t)f * 6;
-            LJ p[3], q[3], res[2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { p[k] = LJ(s_[k], dir == k ? 1.0 : 0.0); q[k] = LJ(s_[3 + k], dir == 3 + k ? 1.0 : 0.0); }
-            pg_ground_res<LJ>(P, p, q, res);
-            Yl[dir] = (dir < 6 ? res[0].d : res[0].v) * noise.ground_on_p;
-            Yl[7 + dir] = (dir < 6 ? res[1].d : res[1].v) * noise.ground_on_q;
-        }
+        if (on) pg_ground_column(P, noise.ground_on_p, noise.ground_on_q, x + (size_t)f * 6, dir, true, Yl);
         __syncthreads();
         if (on && dir < 2) {
-            double Pq[9];
-            if (plus_jac(x + (size_t)f * 6 + 3, Pq)) {
-                double* row = Yl + dir * 7 + 3;
-                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
-                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
-                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
-                row[0] = t0; row[1] = t1; row[2] = t2;
-            }
+            pg_row_times_plus_jac(Yl + dir * 7 + 3, x + (size_t)f * 6 + 3);
         }
         __syncthreads();
         if (on && dir < 7) {
@@ -338,8 +291,7 @@ __global__ __launch_bounds__(64) void k_gj_assemble(char* store, Lay L) {
     const bool is_const = i == cn;
     const bool prev = has_prev(w, i), next = i + 1 < N && has_prev(w, i + 1);
     if (!is_const) {
-        if (lane < 36) acc = Yg[(size_t)i * 14 + r] * Yg[(size_t)i * 14 + c] + Yg[(size_t)i * 14 + 7 + r] * Yg[(size_t)i * 14 + 7 + c];
-        else if (lane < 42) acc = Yg[(size_t)i * 14 + (lane - 36)] * Yg[(size_t)i * 14 + 6] + Yg[(size_t)i * 14 + 7 + (lane - 36)] * Yg[(size_t)i * 14 + 13];
+        acc = pg_node_ground(Yg + (size_t)i * 14, lane);
     }
     // incident edges in edge order: the sequential edge into i (side 1), the one out of i (side 0), then the loops that name i
     const int n_inc = 2 + nl;
@@ -354,22 +306,10 @@ __global__ __launch_bounds__(64) void k_gj_assemble(char* store, Lay L) {
         }
         const double* Y = Ye + (size_t)e * 78;
         if (!is_const) {
-            double sm = 0.0;
-            if (lane < 36) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) sm += Y[k * 13 + 6 * side + r] * Y[k * 13 + 6 * side + c];
-            } else if (lane < 42) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) sm += Y[k * 13 + 6 * side + (lane - 36)] * Y[k * 13 + 12];
-            }
-            acc += sm;
+            acc += pg_node_edge(Y, side, lane);
         }
         if (side == 0 && lane < 36) {   // H[index1, index2](r, c) = sum_k J1[k][r] J2[k][c]; zero against the constant node
-            double o = 0.0;
-            if (!is_const && j != cn) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) o += Y[k * 13 + r] * Y[k * 13 + 6 + c];
-            }
+            const double o = !is_const && j != cn ? pg_edge_cross(Y, lane) : 0.0;
             if (t == 1) w.Os[(size_t)i * 36 + lane] = o;
             else w.Lb[(size_t)(t - 2) * 36 + lane] = o;
         }
@@ -413,45 +353,13 @@ __global__ __launch_bounds__(64) void k_gj_head(char* store, Lay L, int max_iter
     Wk w = work_of(store, L, g);
     if (w.lm->done) return;
     Lm s = *w.lm;
-    const int N = s.N, n = 6 * N, cn = s.cn;
-    if (s.phase == PH_INIT) {
-        s.x_cost = cost_of(L, w, N, s.nl, cn, lane);
-        s.init_cost = s.x_cost;
-        for (int i = lane; i < n; i += 64) w.scale[i] = i / 6 == cn ? 1.0 : 1.0 / (1.0 + sqrt(w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7]));
-    }
-    if (s.phase == PH_INIT || s.phase == PH_ASM) {
-        double sq = 0.0, m = 0.0;
-        for (int i = lane; i < n; i += 64)
-            if (i / 6 != cn) sq += w.x[i] * w.x[i];
-        s.x_norm = sqrt(wave_sum(sq));
-        for (int f = lane; f < N; f += 64) {   // max |x - Plus(x, -g)|
-            if (f == cn) continue;
-            double ng[6], xp[6];
-            for (int k = 0; k < 6; ++k) ng[k] = -w.gd[f * 6 + k];
-            plus6(w.x + (size_t)f * 6, ng, xp);
-            for (int k = 0; k < 6; ++k) m = max_skip_nan(m, fabs(w.x[f * 6 + k] - xp[k]));
-        }
-        s.gmax = wave_max(m);
-    }
-    int term = 0;
-    if (lm_cap_reached(s.iter, max_iters, s.phase == PH_INIT)) term = 4;
-    else term = lm_gradient_term(s.iter == 0, s.last_ok != 0, s.gmax, s.radius > kMinRadius);
+    const int term = pg_lm_head(s, PgConstNode{s.cn}, [&] { return cost_of(L, w, s.N, s.nl, s.cn, lane); }, s.N, max_iters, w.x, w.gd, w.Dd, w.scale, w.dgn,
+                                lane);
     if (term) {
         if (lane == 0) *w.lm = s;
         finish(store, L, g, w, term, summary, lane);
         return;
     }
-    ++s.iter;
-    if (!s.reuse)
-        for (int i = lane; i < n; i += 64) {
-            const double sc = w.scale[i];
-            double v = w.Dd[(size_t)(i / 6) * 36 + (i % 6) * 7] * sc * sc;   // clamped as std::min(std::max(v, lo), hi) does: a NaN stays
-            v = (v < kMinDiag) ? kMinDiag : v;
-            v = (kMaxDiag < v) ? kMaxDiag : v;
-            w.dgn[i] = i / 6 == cn ? 0.0 : v;
-        }
-    s.reuse = 1;
-    s.phase = PH_SOLVE;
     s.status = 0;
     if (lane == 0) *w.lm = s;
 }
@@ -471,60 +379,14 @@ __global__ __launch_bounds__(64) void k_gj_seg_elim(char* store, Lay L) {
 // work-group per group: the separators' system A y = g_s, Cholesky, both solves, scatter
 __global__ __launch_bounds__(256) void k_gj_reduced(char* store, Lay L, int lds_doubles) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = blockIdx.x, tid = threadIdx.x;
     Wk w = work_of(store, L, g);
     if (w.lm->done || w.lm->phase != PH_SOLVE) return;
-    const int ns = w.lm->ns, nr = 6 * ns, nl = w.lm->nl, cn = w.lm->cn;
-    const int tri_n = nr * (nr + 1) / 2;
-    double* A = tri_n <= lds_doubles ? lds : w.Hr;   // the same instructions either way
+    const int ns = w.lm->ns, nr = 6 * ns;
+    double* A = nr * (nr + 1) / 2 <= lds_doubles ? lds : w.Hr;   // the same instructions either way
     double* rhs = w.rhs;
-    const double radius = w.lm->radius;
-    const double *Dd = w.Dd, *gd = w.gd, *Os = w.Os, *scale = w.scale, *dgn = w.dgn, *Sred = w.Sred;
-    const int *sep = w.sep, *nmem = w.nmem;
-    for (int e = tid; e < tri_n; e += 256) A[e] = 0.0;
-    __syncthreads();
-    for (int t = wave; t < ns; t += 4) {
-        const int f = sep[t], r = lane / 6, c = lane % 6;
-        const double* sf = scale + (size_t)f * 6;
-        const bool is_const = f == cn;
-        // neighbours in the same chain; segments with interior nodes
-        const bool lchain = t > 0 && nmem[sep[t - 1]] == nmem[f], rchain = t + 1 < ns && nmem[sep[t + 1]] == nmem[f];
-        const bool left = lchain && sep[t] - sep[t - 1] > 1, right = rchain && sep[t + 1] - sep[t] > 1;
-        if (lane < 36) {
-            double v = is_const ? (r == c ? 1.0 : 0.0) : Dd[(size_t)f * 36 + lane] * sf[r] * sf[c] + (r == c ? dgn[(size_t)f * 6 + c] / radius : 0.0);
-            if (!is_const) {
-                if (right) v += Sred[(size_t)t * PG_SEG + lane];
-                if (left) v += Sred[(size_t)(t - 1) * PG_SEG + 72 + lane];
-            }
-            if (r >= c) A[tri(t * 6 + r, t * 6 + c)] = v;
-            if (lchain) {   // block (t, t-1): direct edge when the separators are chain neighbours, else the segment's fill; none across chains
-                const int fa = sep[t - 1];
-                const double o = left ? Sred[(size_t)(t - 1) * PG_SEG + 36 + lane] : Os[(size_t)fa * 36 + c * 6 + r] * scale[(size_t)fa * 6 + c] * sf[r];
-                A[tri(t * 6 + r, (t - 1) * 6 + c)] = (is_const || fa == cn) ? 0.0 : o;
-            }
-        } else if (lane < 42) {
-            const int k = lane - 36;
-            double v = is_const ? 0.0 : gd[(size_t)f * 6 + k] * sf[k];
-            if (!is_const) {
-                if (right) v += Sred[(size_t)t * PG_SEG + 108 + k];
-                if (left) v += Sred[(size_t)(t - 1) * PG_SEG + 114 + k];
-            }
-            rhs[t * 6 + k] = v;
-        }
-    }
-    __syncthreads();
-    if (wave == 0 && lane < 36) {   // own loop and cross edges, in list order by one wave (several edges may share a block)
-        const int r = lane / 6, c = lane % 6;
-        for (int e = 0; e < nl; ++e) {
-            const int i1 = w.lidx[2 * e], i2 = w.lidx[2 * e + 1];
-            if (i1 == cn || i2 == cn || i1 == i2) continue;
-            const int t1 = w.sepidx[i1], t2 = w.sepidx[i2];
-            const double v = w.Lb[(size_t)e * 36 + lane] * scale[(size_t)i1 * 6 + r] * scale[(size_t)i2 * 6 + c];   // H[i1, i2](r, c)
-            if (t1 > t2) A[tri(t1 * 6 + r, t2 * 6 + c)] += v;
-            else A[tri(t2 * 6 + c, t1 * 6 + r)] += v;
-        }
-    }
-    __syncthreads();
+    const int* sep = w.sep;
+    pg_reduced_system(A, rhs, ns, w.lm->nl, w.lm->cn, sep, w.sepidx, w.lidx, w.nmem, w.Dd, w.gd, w.Os, w.Lb, w.Sred, w.scale, w.dgn, w.lm->radius, tid);
 #include "k_pg_chol_body.inc"
     for (int e = tid; e < nr; e += 256) w.y[(size_t)sep[e / 6] * 6 + e % 6] = rhs[e];
     if (!ok && tid == 0) atomicOr(&w.lm->status, 1);
@@ -545,52 +407,9 @@ __global__ __launch_bounds__(64) void k_gj_decide1(char* store, Lay L, liw_summa
     Wk w = work_of(store, L, g);
     if (w.lm->done || w.lm->phase != PH_SOLVE) return;
     Lm s = *w.lm;
-    const int N = s.N, n = 6 * N, cn = s.cn;
-    bool fin = true;
-    for (int i = lane; i < n; i += 64) fin = fin && isfinite(w.y[i]);
-    const bool solved = s.status == 0 && __ballot(!fin) == 0ull;
-    // model cost change with (A + D^2) y = g_s, step = -y:  (y'g_s + y'D^2 y) / 2
-    double mcc = 0.0;
-    if (solved) {
-        double ytg = 0.0, dsum = 0.0;
-        for (int i = lane; i < n; i += 64) {
-            if (i / 6 == cn) continue;
-            const double yi = w.y[i];
-            ytg += yi * (w.gd[i] * w.scale[i]);
-            dsum += w.dgn[i] / s.radius * yi * yi;
-        }
-        mcc = 0.5 * (wave_sum(ytg) + wave_sum(dsum));
-    }
-    if (!lm_step_valid(solved, mcc)) {
-        if (lm_gives_up(s.invalid++)) {
-            --s.iter;
-            if (lane == 0) *w.lm = s;
-            finish(store, L, g, w, 6, summary, lane);
-            return;
-        }
-        lm_step_rejected(s.radius, s.dec, s.reuse);
-        s.last_ok = 0;
-        s.phase = PH_IDLE;
-        if (lane == 0) *w.lm = s;
-        return;
-    }
-    s.invalid = 0;
-    s.mcc = mcc;
-    double sq = 0.0;
-    for (int f = lane; f < N; f += 64) {
-        if (f == cn) continue;
-        double dl[6], xc[6];
-        for (int k = 0; k < 6; ++k) dl[k] = -w.y[f * 6 + k] * w.scale[f * 6 + k];
-        plus6(w.x + (size_t)f * 6, dl, xc);
-        for (int k = 0; k < 6; ++k) {
-            w.cand[f * 6 + k] = xc[k];
-            const double df = w.x[f * 6 + k] - xc[k];
-            sq += df * df;
-        }
-    }
-    s.step_norm = sqrt(wave_sum(sq));
-    s.phase = PH_CAND;
+    const int term = pg_lm_decide1(s, PgConstNode{s.cn}, s.status == 0, s.N, w.x, w.cand, w.y, w.scale, w.dgn, w.gd, lane);
     if (lane == 0) *w.lm = s;
+    if (term > 0) finish(store, L, g, w, term, summary, lane);
 }
 
 __global__ __launch_bounds__(64) void k_gj_decide2(char* store, Lay L, liw_summary* summary) {
@@ -598,26 +417,10 @@ __global__ __launch_bounds__(64) void k_gj_decide2(char* store, Lay L, liw_summa
     Wk w = work_of(store, L, g);
     if (w.lm->done || w.lm->phase != PH_CAND) return;
     Lm s = *w.lm;
-    const int N = s.N, n = 6 * N;
-    double cc = cost_of(L, w, N, s.nl, s.cn, lane);
-    if (!isfinite(cc)) cc = kFailedEvalCost;
-    const int term = lm_candidate_term(s.step_norm, s.x_norm, s.x_cost, cc);
+    const int term = pg_lm_decide2(s, cost_of(L, w, s.N, s.nl, s.cn, lane), s.N, w.x, w.cand, lane);
     if (term) {
         finish(store, L, g, w, term, summary, lane);
         return;
-    }
-    const double rho = (s.x_cost - cc) / s.mcc;
-    if (lm_accepts(rho)) {
-        for (int i = lane; i < n; i += 64) w.x[i] = w.cand[i];
-        s.x_cost = cc;
-        lm_step_accepted(rho, s.radius, s.dec, s.reuse);
-        ++s.succ;
-        s.last_ok = 1;
-        s.phase = PH_ASM;
-    } else {
-        lm_step_rejected(s.radius, s.dec, s.reuse);
-        s.last_ok = 0;
-        s.phase = PH_IDLE;
     }
     if (lane == 0) *w.lm = s;
 }
@@ -650,8 +453,6 @@ __global__ __launch_bounds__(64) void k_gj_finish(char* store, Lay L, In in) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- launches
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-
 int launch_solve(char* store, const Lay& L, const Noise& noise, const DevParams& P, const In& in, int max_iters, int check_every, int lds_cap_doubles,
                  liw_summary* summary, hipStream_t s) {
     const int K = max_iters > 0 ? max_iters : 50;

@@ -1,6 +1,6 @@
 // k_pg_chol_body.inc — right-looking Cholesky of a packed lower triangle and both triangular solves, by a work-group of 256 threads:
-// the text that k_fpg_reduced (k_posegraph_batch.hip) and k_ggraph_solve (k_group_graph.hip) share, so that both run the same
-// instructions.  In scope where it is included: double* A (the triangle, order nr), double* rhs, int nr, int tid; it defines
+// the text that k_fpg_reduced (k_posegraph_batch.hip), k_gj_reduced (k_group_joint.hip) and k_ggraph_solve (k_group_graph.hip) share, so
+// that all run the same instructions.  In scope where it is included: double* A (the triangle, order nr), double* rhs, int nr, int tid; it defines
 // bool ok (false when a pivot is not positive and finite) and leaves rhs <- A^-1 rhs.
     // right-looking Cholesky, a column per step; every thread reads the same pivot
     bool ok = true;

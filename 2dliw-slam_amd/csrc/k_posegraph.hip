@@ -48,30 +48,11 @@ __global__ __launch_bounds__(64) void k_pg_linearize(int N, int E, const double*
         const int i = on ? eidx[e * 2] : 0, j = on ? eidx[e * 2 + 1] : 0;
         const double* xi = x + (size_t)i * 6;
         const double* xj = x + (size_t)j * 6;
-        if (on && (d == 12 || (jac && d < 12))) {
-            LJ pi[3], qi[3], pj[3], qj[3], res[6];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                pi[k] = LJ(xi[k], d == k ? 1.0 : 0.0);
-                qi[k] = LJ(xi[3 + k], d == 3 + k ? 1.0 : 0.0);
-                pj[k] = LJ(xj[k], d == 6 + k ? 1.0 : 0.0);
-                qj[k] = LJ(xj[3 + k], d == 9 + k ? 1.0 : 0.0);
-            }
-            edge_res<LJ>(etf + (size_t)e * 12, ew[e], noise.J, pi, qi, pj, qj, res);
-#pragma unroll
-            for (int r = 0; r < 6; ++r) Y[grp][r * 13 + d] = d < 12 ? res[r].d : res[r].v;
-        }
+        if (on) pg_edge_column(etf + (size_t)e * 12, ew[e], noise.J, xi, xj, d, jac != 0, Y[grp]);
         __syncthreads();
         if (on && jac && d < 12) {   // local parameterisation: J_theta <- J_theta * dPlus/ddelta  (lane = (row r, pose which))
             const int r = d % 6, which = d / 6;
-            double Pq[9];
-            if (plus_jac((which ? xj : xi) + 3, Pq)) {
-                double* row = &Y[grp][r * 13 + 6 * which + 3];
-                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
-                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
-                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
-                row[0] = t0; row[1] = t1; row[2] = t2;
-            }
+            pg_row_times_plus_jac(&Y[grp][r * 13 + 6 * which + 3], (which ? xj : xi) + 3);
         }
         __syncthreads();
         if (on && d < 13)
@@ -83,25 +64,10 @@ __global__ __launch_bounds__(64) void k_pg_linearize(int N, int E, const double*
         const int i = ((int)blockIdx.x - edge_blocks) * 8 + sub;
         const bool on = i < N;
         double* Yl = &Y[0][0] + sub * 16;
-        if (on && (dir == 6 || (jac && dir < 6))) {
-            const double* s_ = x + (size_t)i * 6;
-            LJ p[3], q[3], res[2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { p[k] = LJ(s_[k], dir == k ? 1.0 : 0.0); q[k] = LJ(s_[3 + k], dir == 3 + k ? 1.0 : 0.0); }
-            pg_ground_res<LJ>(P, p, q, res);
-            Yl[dir] = (dir < 6 ? res[0].d : res[0].v) * noise.ground_on_p;
-            Yl[7 + dir] = (dir < 6 ? res[1].d : res[1].v) * noise.ground_on_q;
-        }
+        if (on) pg_ground_column(P, noise.ground_on_p, noise.ground_on_q, x + (size_t)i * 6, dir, jac != 0, Yl);
         __syncthreads();
         if (on && jac && dir < 2) {
-            double Pq[9];
-            if (plus_jac(x + (size_t)i * 6 + 3, Pq)) {
-                double* row = Yl + dir * 7 + 3;
-                const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
-                const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
-                const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
-                row[0] = t0; row[1] = t1; row[2] = t2;
-            }
+            pg_row_times_plus_jac(Yl + dir * 7 + 3, x + (size_t)i * 6 + 3);
         }
         __syncthreads();
         if (on && dir < 7) {
@@ -137,20 +103,11 @@ __global__ __launch_bounds__(64) void k_pg_assemble(int N, int ld, const int* in
     double acc = 0.0;
     const bool is_const = i == const_pose;
     if (!is_const) {
-        if (lane < 36) acc = Yg[(size_t)i * 14 + r] * Yg[(size_t)i * 14 + c] + Yg[(size_t)i * 14 + 7 + r] * Yg[(size_t)i * 14 + 7 + c];
-        else if (lane < 42) acc = Yg[(size_t)i * 14 + (lane - 36)] * Yg[(size_t)i * 14 + 6] + Yg[(size_t)i * 14 + 7 + (lane - 36)] * Yg[(size_t)i * 14 + 13];
+        acc = pg_node_ground(Yg + (size_t)i * 14, lane);
         for (int t = inc_off[i]; t < inc_off[i + 1]; ++t) {
             const int e = inc[t] >> 1, side = inc[t] & 1;
             const double* Y = Ye + (size_t)e * 78;
-            double s = 0.0;
-            if (lane < 36) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) s += Y[k * 13 + 6 * side + r] * Y[k * 13 + 6 * side + c];
-            } else if (lane < 42) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) s += Y[k * 13 + 6 * side + (lane - 36)] * Y[k * 13 + 12];
-            }
-            acc += s;
+            acc += pg_node_edge(Y, side, lane);
             // off-diagonal block H[j, i] of the pair (i, j), j > i (lower triangle): added by the wave of the LOWER key frame only, whichever
             // side of the edge it is, in the order of its incidence list (= edge order).  Any number of edges between the same pair —
             // in either direction — sums in that one order, by one wave: bit-reproducible without atomics (round 6; until then the side-0
@@ -424,30 +381,17 @@ __global__ __launch_bounds__(64) void k_pg_assemble_blocks(int N, int n_seq, con
     double acc = 0.0;
     const bool is_const = i == const_pose;
     if (!is_const) {
-        if (lane < 36) acc = Yg[(size_t)i * 14 + r] * Yg[(size_t)i * 14 + c] + Yg[(size_t)i * 14 + 7 + r] * Yg[(size_t)i * 14 + 7 + c];
-        else if (lane < 42) acc = Yg[(size_t)i * 14 + (lane - 36)] * Yg[(size_t)i * 14 + 6] + Yg[(size_t)i * 14 + 7 + (lane - 36)] * Yg[(size_t)i * 14 + 13];
+        acc = pg_node_ground(Yg + (size_t)i * 14, lane);
     }
     for (int t = inc_off[i]; t < inc_off[i + 1]; ++t) {
         const int e = inc[t] >> 1, side = inc[t] & 1;
         const double* Y = Ye + (size_t)e * 78;
         if (!is_const) {
-            double sm = 0.0;
-            if (lane < 36) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) sm += Y[k * 13 + 6 * side + r] * Y[k * 13 + 6 * side + c];
-            } else if (lane < 42) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) sm += Y[k * 13 + 6 * side + (lane - 36)] * Y[k * 13 + 12];
-            }
-            acc += sm;
+            acc += pg_node_edge(Y, side, lane);
         }
         if (side == 0 && lane < 36) {   // H[index1, index2](r, c) = sum_k J1[k][r] J2[k][c]; zero against the constant key frame
             const int j = eidx[e * 2 + 1];
-            double o = 0.0;
-            if (!is_const && j != const_pose) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) o += Y[k * 13 + r] * Y[k * 13 + 6 + c];
-            }
+            const double o = !is_const && j != const_pose ? pg_edge_cross(Y, lane) : 0.0;
             if (e < n_seq) Os[(size_t)i * 36 + lane] = o;
             else Lb[(size_t)(e - n_seq) * 36 + lane] = o;
         }

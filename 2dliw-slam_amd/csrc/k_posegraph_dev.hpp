@@ -1,7 +1,9 @@
 // k_posegraph_dev.hpp — the per-edge, per-key-frame and per-segment device code of the pose graph, shared by the single-graph solver
-// (k_posegraph.hip) and the fleet solver (k_posegraph_batch.hip): edge_factor / ground_factor residuals, the so3 Plus Jacobian, and the
-// wave-per-segment chain elimination and back-substitution.  Moved here from k_posegraph.hip line for line; the two segment routines
-// are the bodies of k_pg_seg_elim / k_pg_seg_backsub with the segment's arrays as arguments, so both solvers run the same instructions.
+// (k_posegraph.hip), the fleet solver (k_posegraph_batch.hip), the group graph (k_group_graph.hip) and the joint graph of a group
+// (k_group_joint.hip): edge_factor / ground_factor residuals, the so3 Plus Jacobian, what a lane of a linearisation or assembly block
+// does (pg_edge_column, pg_ground_column, pg_row_times_plus_jac, pg_node_ground / pg_node_edge / pg_edge_cross), and the
+// wave-per-segment chain elimination and back-substitution: the bodies of k_pg_seg_elim / k_pg_seg_backsub with the segment's arrays as
+// arguments, so all solvers run the same instructions.
 #pragma once
 #include "liw_kernels.hpp"
 
@@ -53,6 +55,72 @@ __device__ __forceinline__ void pg_ground_res(const DevParams& P, const T* p_, c
     V3<T> z_axis(tf_w_o.R(0, 2), tf_w_o.R(1, 2), tf_w_o.R(2, 2));
     T sinn = norm(cross(z_axis, ABC));
     res[1] = T(P.ground_q_info) * dasin(sinn);
+}
+
+// ---- the lanes of a block.  A kernel keeps its slot arithmetic, its phase tests, its barriers and its stores; these are what a lane does.
+// local parameterisation of three rotation columns of a Jacobian row: row <- row * dPlus/ddelta at the rotation vector q
+__device__ __forceinline__ void pg_row_times_plus_jac(double* row, const double* q) {
+    double Pq[9];
+    if (plus_jac(q, Pq)) {
+        const double t0 = row[0] * Pq[0] + row[1] * Pq[3] + row[2] * Pq[6];
+        const double t1 = row[0] * Pq[1] + row[1] * Pq[4] + row[2] * Pq[7];
+        const double t2 = row[0] * Pq[2] + row[1] * Pq[5] + row[2] * Pq[8];
+        row[0] = t0; row[1] = t1; row[2] = t2;
+    }
+}
+// lane d of an edge's sixteen writes column d of Y [6][13] = [J | r]: the dual direction d of (p_i, q_i, p_j, q_j) for d < 12 (only when
+// jac), the value for d = 12
+__device__ __forceinline__ void pg_edge_column(const double* tf12, double weight, const double* Jn, const double* xi, const double* xj, int d, bool jac,
+                                               double* Y) {
+    if (!(d == 12 || (jac && d < 12))) return;
+    LJ pi[3], qi[3], pj[3], qj[3], res[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        pi[k] = LJ(xi[k], d == k ? 1.0 : 0.0);
+        qi[k] = LJ(xi[3 + k], d == 3 + k ? 1.0 : 0.0);
+        pj[k] = LJ(xj[k], d == 6 + k ? 1.0 : 0.0);
+        qj[k] = LJ(xj[3 + k], d == 9 + k ? 1.0 : 0.0);
+    }
+    edge_res<LJ>(tf12, weight, Jn, pi, qi, pj, qj, res);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) Y[r * 13 + d] = d < 12 ? res[r].d : res[r].v;
+}
+// lane dir of a node's eight writes column dir of Yl [2][7] = [J | r] of its ground factor: direction dir < 6 (only when jac), value 6
+__device__ __forceinline__ void pg_ground_column(const DevParams& P, double on_p, double on_q, const double* s_, int dir, bool jac, double* Yl) {
+    if (!(dir == 6 || (jac && dir < 6))) return;
+    LJ p[3], q[3], res[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { p[k] = LJ(s_[k], dir == k ? 1.0 : 0.0); q[k] = LJ(s_[3 + k], dir == 3 + k ? 1.0 : 0.0); }
+    pg_ground_res<LJ>(P, p, q, res);
+    Yl[dir] = (dir < 6 ? res[0].d : res[0].v) * on_p;
+    Yl[7 + dir] = (dir < 6 ? res[1].d : res[1].v) * on_q;
+}
+// A wave gathers a node's 6x6 block of J'J (lanes 0..35: entry (lane / 6, lane % 6)) and its J'r (lanes 36..41): what the node's ground
+// block Yg [2][7] and side `side` of an incident edge's Y [6][13] add for this lane, and for lanes 0..35 the edge's block H[index1, index2]
+__device__ __forceinline__ double pg_node_ground(const double* Yg, int lane) {
+    const int r = lane / 6, c = lane % 6;
+    if (lane < 36) return Yg[r] * Yg[c] + Yg[7 + r] * Yg[7 + c];
+    if (lane < 42) return Yg[lane - 36] * Yg[6] + Yg[7 + (lane - 36)] * Yg[13];
+    return 0.0;
+}
+__device__ __forceinline__ double pg_node_edge(const double* Y, int side, int lane) {
+    const int r = lane / 6, c = lane % 6;
+    double s = 0.0;
+    if (lane < 36) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s += Y[k * 13 + 6 * side + r] * Y[k * 13 + 6 * side + c];
+    } else if (lane < 42) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s += Y[k * 13 + 6 * side + (lane - 36)] * Y[k * 13 + 12];
+    }
+    return s;
+}
+__device__ __forceinline__ double pg_edge_cross(const double* Y, int lane) {   // sum_k J1[k][r] J2[k][c]
+    const int r = lane / 6, c = lane % 6;
+    double o = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o += Y[k * 13 + r] * Y[k * 13 + 6 + c];
+    return o;
 }
 
 // every PG_STRIDE-th key frame of the chain is a separator (k_posegraph.hip, "sparse path")

@@ -1,6 +1,6 @@
 """The joint pose graph of a group on the MI355X (include/liw_group_joint.h, group_joint.FleetGroupJoint) on the cases of
 tests/group_joint_cases.py: structure and flags against the restatement, x0 against liw_lie_* of the device's own inputs, the solve
-against the oracle at the bars of tests/test_gpu_posegraph_batch.py, the single-member group against FleetBackEnd.solve, the claim
+against the oracle at the bars of tests/test_gpu_posegraph_batch.py (also with a constant node that is not node 0), the single-member group against FleetBackEnd.solve, the claim
 against FleetGroupGraph.solve's rigid alignment, bit-identity (alone, at other indices, tiled, two runs, check_every, work area), a NaN
 group among healthy ones, what must stay untouched, and the pipeline FleetLoopDetector.push -> FleetBackEnd.push ->
 FleetGroupGraph.push -> FleetGroupJoint.push -> FleetGroupMap.render end to end."""
@@ -35,7 +35,8 @@ class Rig:
     """detector (for its handle only), back-end holding the cases' graphs, aligner in the cases' state, the group graph holding the cases'
     cross edges, and the joint graph; `tiles` copies of the thirteen robots (robot r of tile t is r + 13 t, its group g + 5 t)"""
 
-    def __init__(self, liw, synth, mods, tiles=1, guard=0, max_members=jc.MAX_MEMBERS, max_nodes=jc.MAX_NODES, max_loops=jc.MAX_LOOPS, pg=None, cross=None):
+    def __init__(self, liw, synth, mods, tiles=1, guard=0, max_members=jc.MAX_MEMBERS, max_nodes=jc.MAX_NODES, max_loops=jc.MAX_LOOPS, pg=None, cross=None,
+                 fixed=None):
         import torch
         gg, gj = mods
         F = jc.fleet()
@@ -49,7 +50,7 @@ class Rig:
             if jc.NKF[r % jc.B]:
                 self.fb.load_graph(r, jc.backend_graph(r % jc.B))
         self.group_of = [g + jc.G * t for t in range(tiles) for g in jc.GROUP_OF]
-        self.linked, self.fixed = list(jc.LINKED) * tiles, list(jc.FIXED) * tiles
+        self.linked, self.fixed = list(jc.LINKED) * tiles, list(jc.FIXED if fixed is None else fixed) * tiles   # the aligner's anchors are these
         self.al = liw.FleetGroupAligner(self.fl, self.group_of, {r: F["W"][r % jc.B] for r in range(B) if self.fixed[r]}, 9, xc.MAX_RMS)
         self.al.linked.copy_(torch.tensor(self.linked, dtype=torch.uint8))
         self.al.via[torch.tensor([bool(l and not f) for l, f in zip(self.linked, self.fixed)], device=self.al.dev)] = 0
@@ -212,6 +213,39 @@ def test_solve_against_the_oracle(liw, synth, mods, pyoracle, cap, ground_q):
         assert R.j.last_summary(g) == s
         if cap == 0:
             assert s["termination"] in (1, 2, 3), s
+    R.close()
+
+
+# the anchors moved off the first member: robot 1 in group A (constant node 8 of 30), robot 4 in group B (constant node 60 of 66: the
+# strided loops of a wave take a second pass and the constant node lies in the last full one).  Robot 5 cannot be it: it has one key
+# frame, and the oracle's constant node is index1 of a sequential edge.
+OTHER_FIXED = [0, 1, 0, 0, 1, 0, 0, 1, 1, 0, 0, 1, 0]
+
+
+def test_solve_with_a_constant_node_that_is_not_node_zero(liw, synth, mods, pyoracle):
+    """test_solve_against_the_oracle's assertions at its bars, for the two groups whose constant member is not their first one"""
+    x0 = _x0_rows(liw, synth, mods)          # x0 = T_g_w * P does not depend on who is fixed
+    cap = 20
+    pg = liw.posegraph.office_pg_params()
+    orc = _CACHE.setdefault("orc", pyoracle.Oracle(synth.office_params()))
+    R = Rig(liw, synth, mods, pg=pg, fixed=OTHER_FIXED)
+    R.solve(max_iters=cap)
+    sm, rows = R.j.summaries(), R.rows()
+    for g, cn, N, r0 in ((0, 8, 30, 1), (1, 60, 66, 4)):
+        S = jc.structure(g, fixed=OTHER_FIXED)
+        assert (S["const_node"], S["flags"]["nodes"], S["const_member"]) == (cn, N, r0)
+        fl = R.j.flags(g)
+        assert {k: fl[k] for k in FLAG_KEYS} == S["flags"], (g, fl, S["flags"])
+        xo, so = jc.oracle_solve(pyoracle, orc, pg, g, max_iters=cap, fixed=OTHER_FIXED)
+        s, x = sm[g], R.group_rows(g, rows)
+        print("fixed robot %d (node %d of %d) group %d device %s\n%42s %s\n   |x - oracle| %.3e" % (r0, cn, N, g, s, "oracle", so, np.abs(x - xo).max()))
+        assert (s["iterations"], s["successful"], s["termination"]) == (so["iterations"], so["successful"], so["termination"]), (g, s, so)
+        assert abs(s["initial_cost"] - so["initial_cost"]) <= 1e-9 * so["initial_cost"], g
+        assert abs(s["final_cost"] - so["final_cost"]) <= 1e-6 * max(1.0, so["final_cost"]), g
+        assert np.abs(x - xo).max() <= 1e-6 * max(1.0, np.abs(xo).max()), g
+        assert rows[r0, 0].tobytes() == x0[r0, 0].tobytes(), g                     # the constant node: bit for bit x0
+        assert rows[r0, 1].tobytes() != x0[r0, 1].tobytes(), g                     # the node after it moved
+        assert R.j.last_summary(g) == s
     R.close()
 
 
